@@ -17,10 +17,19 @@ ids of every rank are gathered to rank 0 with RCCL (ncclGather over xGMI)
 inside the timed step.
 
 value = audio seconds transcribed per wall second over all ranks (= 1/RTF for
-one clip on one GPU); ms_per_step is the max over ranks.  The N = 1 line also
-carries the per-stage device times, the dominant kernel's roofline (HIP
-events, live), every other single-GPU config of BASELINE.json measured in the
-same run (`configs`), and the CPU restatement timed on the host cores.
+one clip on one GPU); ms_per_step is the max over ranks.  A plain run sets up,
+warms up, times --steps steps and prints the line, with the per-stage device
+times of the last step (HIP events the step records anyway).  --full adds
+what takes runs of its own: the dominant kernel's roofline and the top encoder
+kernels (HIP events, live), every other single-GPU config of BASELINE.json
+(`configs`), and the CPU restatement timed on the host cores.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(float32): `tokens` [clips][n_decode], the ids the step hands its caller
+(world > 1: every rank's, [world * clips][n_decode], -1 padded), and rank 0's
+`encoder_out` [clips][n_ctx][n_state] and `mel` [clips][n_mels][n_len], the
+intermediate results the ids follow from.  Inputs are synthetic and seeded, so
+two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -60,6 +69,35 @@ EXTRA_CONFIGS = (
     ("c4_shard_base_x8", "base", 8, 0, 3, "configs[3]'s per-GPU shard: base f16, 8 x 30 s clips on one GPU"),
     ("c5_large_v3_beam5", "large-v3", 1, 5, 2, "configs[4]: large-v3 f16, one 30 s clip, beam_size 5, 1 GPU"),
 )
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all arrays together
+
+
+def capped(arr, max_bytes: int):
+    """arr as float32, or — when that is larger than max_bytes — a fixed sample
+    of its elements (flat indices drawn once with seed 0, ascending)."""
+    import numpy as np
+    arr = np.asarray(arr, dtype=np.float32)
+    n = max_bytes // 4
+    if arr.size <= n:
+        return arr
+    idx = np.sort(np.random.default_rng(0).choice(arr.size, n, replace=False))
+    return arr.reshape(-1)[idx]
+
+
+def dump_outputs(dirname: str, ctx, tokens) -> None:
+    """The last timed step's results as dirname/<name>.npy (module docstring)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    enc = np.stack([ctx.encoder_out(c) for c in range(ctx.n_clips)])
+    mel = np.stack([ctx.mel(c) for c in range(ctx.n_clips)])
+    arrays = {"tokens": capped(tokens, 1 << 20), "mel": capped(mel, 15 << 20)}
+    arrays["encoder_out"] = capped(enc, DUMP_MAX_BYTES - (16 << 20))
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log(f"outputs of the last timed step in {dirname}: "
+        + ", ".join(f"{k}{list(a.shape)}" for k, a in arrays.items()))
 
 
 def log(msg):
@@ -362,9 +400,8 @@ def run_rank(args, rank: int, world: int, local: int) -> None:
         def step():
             ctx.run_staged(n_decode=args.n_decode, beam_size=args.beam)
             if world > 1:
-                ctx.dist_gather_tokens()  # every rank's ids to rank 0's host (ncclGather, then D2H)
-            else:
-                ctx.tokens()  # the ids the caller consumes, on the host (wmi_get_tokens: D2H)
+                return ctx.dist_gather_tokens()  # every rank's ids to rank 0's host (ncclGather, then D2H)
+            return ctx.tokens()  # the ids the caller consumes, on the host (wmi_get_tokens: D2H)
 
     for i in range(args.warmup):
         step()
@@ -373,8 +410,9 @@ def run_rank(args, rank: int, world: int, local: int) -> None:
         ctx.dist_barrier()
     group.barrier()
     t0 = time.perf_counter()
+    out = None
     for i in range(args.steps):
-        step()
+        out = step()
     if ctx is not None and world > 1:
         ctx.dist_barrier()
     t1 = time.perf_counter()
@@ -424,13 +462,17 @@ def run_rank(args, rank: int, world: int, local: int) -> None:
     if args.dry_run:
         result["dry_run"] = True
         result["cpu_baseline"] = None
+        if args.dump_outputs:
+            log("--dump-outputs: a dry run computes nothing, no file written")
         group.close()
         print(json.dumps(result), flush=True)
         return
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, out[0].reshape(-1, args.n_decode) if world > 1 else out)
     tm = ctx.timings()
     kernels, kb_alg = {}, {}
-    for k, (bound, name) in KERNELS.items():
+    for k, (bound, name) in KERNELS.items() if args.full else ():
         try:
             kb = ctx.bench_kernel(k, 3 if k == 14 else 50)
         except Exception as e:  # e.g. the persistent decoder not eligible for this shape
@@ -470,15 +512,16 @@ def run_rank(args, rank: int, world: int, local: int) -> None:
         "roofline": roof,
         "encoder_mfma": {"gflop": round(ef / 1e9, 2), "tflops": round(ef / (enc_ms * 1e-3) / 1e12, 1),
                          "frac": round(ef / (enc_ms * 1e-3) / 1e12 / MFMA_F16_PEAK_TFS, 4)},
-        "whole_step": {"alg_bytes": step_bytes, "ms": round(ms_step, 3),
-                       "GB/s": round(step_bytes / (ms_step * 1e-3) / 1e9, 1),
-                       "frac": round(step_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
-        "kernels": kernels,
     })
+    if args.full:  # (both need the kernels' own timed launches above)
+        result["whole_step"] = {"alg_bytes": step_bytes, "ms": round(ms_step, 3),
+                                "GB/s": round(step_bytes / (ms_step * 1e-3) / 1e9, 1),
+                                "frac": round(step_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+        result["kernels"] = kernels
     ctx.close()
     ctx = None
     headline = world == 1 and args.model == "base" and cpg == 1 and args.beam == 0
-    if world == 1 and (args.configs == "all" or (args.configs == "auto" and headline)):
+    if args.full and world == 1 and (args.configs == "all" or (args.configs == "auto" and headline)):
         import wmi
         configs = {}
         for cname, model, clips, beam, steps, what in EXTRA_CONFIGS:
@@ -489,7 +532,7 @@ def run_rank(args, rank: int, world: int, local: int) -> None:
                 log(f"config {cname} failed: {e}")
                 configs[cname] = {"workload": what, "error": str(e)}
         result["configs"] = configs
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         log("timing the CPU restatement (bounded sample)")
         result["cpu_baseline"] = cpu_baseline(synth.model_path(args.model), synth.synth_pcm_f32(30.0, 1234),
                                               args.n_decode, args.cpu_min_seconds, args.cpu_max_seconds)
@@ -509,10 +552,18 @@ def main():
                     help="clips per rank (default 1 at one GPU, 8 with --gpus > 1: configs[3]'s 64 = 8 x 8)")
     ap.add_argument("--n-decode", type=int, default=128)
     ap.add_argument("--beam", type=int, default=0, help="beam width (0 = greedy; C5 uses 5)")
-    ap.add_argument("--roofline-kernel", type=int, default=14, choices=sorted(KERNELS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (tokens, encoder_out, mel)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also time the roofline and encoder kernels on their own, measure "
+                         "BASELINE.json's other single-GPU configs and time the CPU restatement (see --configs, "
+                         "--no-cpu-baseline); without it the run ends with the headline line")
+    ap.add_argument("--roofline-kernel", type=int, default=14, choices=sorted(KERNELS),
+                    help="with --full: the kernel `roofline` reports")
     ap.add_argument("--configs", default="auto", choices=("auto", "all", "none"),
-                    help="also measure BASELINE.json's other single-GPU configs (auto: with the headline run)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: also measure BASELINE.json's other single-GPU configs (auto: with the "
+                         "headline run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU restatement out")
     ap.add_argument("--cpu-min-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-max-seconds", type=float, default=30.0)
     ap.add_argument("--launch-deadline", type=float, default=1500.0,

@@ -4,7 +4,7 @@ SQ_VALU_MFMA_BUSY_CYCLES counts 32 cycles per v_mfma_f32_32x32x16_f16 (summed
 over SIMDs); GRBM_GUI_ACTIVE is summed over the 8 XCDs (MI355X_MICROARCH.md).
 util_profiled = busy / (GRBM_GUI_ACTIVE / 8 x 1024 SIMDs) over the profiled
 dispatch; util_live = busy / (live avg duration x 2.4 GHz x 1024), the live
-duration being bench.py's hipEvent average from the bench JSON.
+duration being bench.py's hipEvent average (`kernels`) from a `bench.py --full` line.
 Usage: mfma_summary.py GPURUN_OUT_PREFIX BENCH_JSON OUT_JSON"""
 import collections
 import csv

@@ -8,7 +8,7 @@
 # steps (outputs under gpurun_out/, prefixed TAG):
 #   tests[=K]          pytest -m gpu (optionally -k K): TAG_tests.log
 #   smoke              __graft_entry__.smoke(): TAG_smoke.log
-#   bench[=ARGS]       bench.py ARGS (default: the driver's line, all configs + CPU baseline): TAG_bench.json
+#   bench[=ARGS]       bench.py ARGS (default --full: the headline line plus kernel rooflines, all configs + CPU baseline): TAG_bench.json
 #   trace=MODEL:ROWS   decoder phase trace (WMI_PTRACE) of a greedy run: TAG_trace_MODEL_ROWS.log
 #   beamtrace=MODEL:K  the same for a K-beam search (16 steps): TAG_beamtrace_MODEL_K.log
 #   prof               rocprofv3 kernel-trace summary of the base bench: TAG_prof/
@@ -39,7 +39,7 @@ for step in "$@"; do
       timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > ${O}_smoke.log 2>&1 || exit 1
       tail -n 1 ${O}_smoke.log ;;
     bench)
-      timeout -k 10 800 python3 bench.py $arg > ${O}_bench.json 2> ${O}_bench.err || exit 1
+      timeout -k 10 800 python3 bench.py ${arg:---full} > ${O}_bench.json 2> ${O}_bench.err || exit 1
       python3 -c "
 import json; d=json.load(open('${O}_bench.json')); print('bench', d['value'], d['stage_ms'], (d.get('roofline') or {}).get('frac'))
 [print(' ', k, v.get('audio_s_per_s'), v.get('decode_ms'), v.get('encoder_ms'), (v.get('roofline') or {}).get('frac')) for k, v in d.get('configs', {}).items()]" ;;
