@@ -105,6 +105,46 @@ int wmi_set_audio_ctx(wmi_context *ctx, int n_audio_ctx);
  * terminated) into buf, *len = byte count; WMI_E_NO_SPACE if cap too small. */
 int wmi_token_to_bytes(const wmi_context *ctx, int32_t id, char *buf, size_t cap, size_t *len);
 
+/* ---- language and task ------------------------------------------------ */
+
+/* Languages are indexed in whisper.cpp's order (en = 0, zh = 1, ... yue =
+ * 99); the language token of index i is sot + 1 + i.  A multilingual file has
+ * 99 languages (100 from large-v3 on), an English-only (.en) file none.
+ *
+ * The settings live on the context until changed; the defaults are language
+ * 0 and transcribe.  They select the prompt [SOT, language, task, NOT] of
+ * wmi_decode_greedy, wmi_decode_beam, wmi_full, wmi_run_staged,
+ * wmi_run_staged_beam and wmi_transcribe (wmi_decode_logits and
+ * wmi_decode_timestamps take explicit tokens).  With WMI_LANG_AUTO a clip's
+ * language is detected on the device at the start of the decode and its token
+ * goes into the prompt there, without a host round trip; wmi_transcribe
+ * detects once, on the first window, and keeps that language.  On an
+ * English-only file any language other than 0, WMI_LANG_AUTO, translate and
+ * wmi_detect_language return WMI_E_INVALID_ARG. */
+#define WMI_LANG_AUTO (-1)
+enum wmi_task { WMI_TASK_TRANSCRIBE = 0, WMI_TASK_TRANSLATE = 1 };
+
+/* Language table (host only, no context or device). */
+int wmi_lang_index(const char *code, int32_t *index);   /* unknown code: WMI_E_INVALID_ARG */
+const char *wmi_lang_code(int index);                   /* NULL outside [0, 100) */
+int wmi_lang_count(const wmi_context *ctx, int32_t *n); /* 0 / 99 / 100 */
+
+/* clip in [0, max_clips), or -1 = every clip; lang = index or WMI_LANG_AUTO
+ * (an index >= the file's language count: WMI_E_INVALID_ARG). */
+int wmi_set_language(wmi_context *ctx, int clip, int lang);
+int wmi_set_task(wmi_context *ctx, int task);
+
+/* One decoder step on [SOT] for every encoded clip.  lang[n_clips] = most
+ * probable language (ties: lowest index).  probs (optional) is
+ * [n_clips][n_lang] f32: the softmax over the language logits, computed in
+ * double.  Changes no setting. */
+int wmi_detect_language(wmi_context *ctx, int32_t *lang, float *probs);
+
+/* Language index the last decode / transcribe used for `clip` (before any:
+ * the explicit setting, or WMI_LANG_AUTO).  *p (optional) = its detection
+ * probability, or -1 if the language was set explicitly. */
+int wmi_get_language(const wmi_context *ctx, int clip, int32_t *lang, float *p);
+
 /* ---- audio input and text output --------------- */
 
 /* hound::WavReader::open(path) + samples::<i16>() (main.rs:2067-2068):
@@ -135,8 +175,9 @@ int wmi_pcm_to_mel_batch(wmi_context *ctx, int n_clips, const float *const *pcm,
 int wmi_encode(wmi_context *ctx, int n_threads, int mel_offset);
 
 /* Greedy decode (the reference declares the decoder but has
- * no forward pass).  Prompt = [SOT] (.en) or [SOT, lang(en), transcribe],
- * then NOT.  Generates up to max_tokens ids per clip; stops a clip at EOT
+ * no forward pass).  Prompt = [SOT] (.en) or [SOT, language, task] as set
+ * by wmi_set_language / wmi_set_task (default: en, transcribe; each clip its
+ * own language), then NOT.  Generates up to max_tokens ids per clip; stops a clip at EOT
  * unless suppress_eot != 0 (then exactly max_tokens).  tokens is
  * [n_clips][max_tokens]; n_tokens[c] = ids written for clip c. */
 int wmi_decode_greedy(wmi_context *ctx, int max_tokens, int suppress_eot,
@@ -257,7 +298,9 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * persistent decoder's grid per row count (int32 [9], host; -1 = not sized
  * yet, 0 = kernel chain), 18 = the encoder GELU epilogues' threshold (f32,
  * host: f16 inputs at or above it are computed, the rest read ggml's table;
- * +inf with WMI_GELU_CALC=0). */
+ * +inf with WMI_GELU_CALC=0), 19 = the prompt of the last timestamp window
+ * (wmi_transcribe / wmi_decode_timestamps; int32, host copy: the first
+ * bytes / 4 tokens, entries past its length are -1). */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

@@ -230,6 +230,21 @@ struct wmi_context {
     struct Segment { int64_t t0, t1; int first, count; std::string text; };
     std::vector<Segment> segments;      // result_all (main.rs:353) of the last transcribe
     std::vector<TsRec> seg_tokens;      // their tokens, in order
+    std::vector<int32_t> ts_prompt;     // prompt of the last timestamp window (debug read 19)
+    // language and task (wmi_set_language / wmi_set_task).  While every clip
+    // is language 0 and the task transcribe (lang_default), the decode
+    // entries enqueue what they always did; otherwise the block's prompt rows
+    // are written on the device (k_prompt_feed) from d_lang, which holds the
+    // explicit settings and, for AUTO clips, what k_lang_detect found
+    int n_lang = 0;                     // 0 (.en) / 99 / 100
+    int task = WMI_TASK_TRANSCRIBE;
+    std::vector<int32_t> lang_set;      // [max_clips] index or WMI_LANG_AUTO
+    std::vector<int32_t> lang_used;     // [max_clips] language of the last decode / transcribe
+    std::vector<float> lang_p;          // [max_clips] its detection probability (-1: set explicitly)
+    bool lang_default = true, lang_any_auto = false;
+    int32_t *d_lang = nullptr;          // one allocation: d_lang, d_lang_auto, d_lang_det [max_clips] each,
+    int32_t *d_lang_auto = nullptr, *d_lang_det = nullptr;
+    float *d_lang_p = nullptr, *d_lang_probs = nullptr;  // then p [max_clips], probs [max_clips][n_lang]
     uint32_t *derr = nullptr;
     size_t sync_bytes = 0;
     int s_stride = 0, n_chunks_max = 0;
@@ -639,12 +654,21 @@ int prompt_tokens(const wmi_context *ctx, int32_t *out) {
     int n = 0;
     out[n++] = ctx->sp.sot;
     if (ctx->sp.is_multilingual) {
-        out[n++] = ctx->sp.sot + 1;  // <|en|>
-        out[n++] = ctx->sp.transcribe;
+        out[n++] = ctx->sp.sot + 1;  // <|en|> (another language: k_prompt_feed writes each clip's token here)
+        out[n++] = ctx->task == WMI_TASK_TRANSLATE ? ctx->sp.translate : ctx->sp.transcribe;
     }
     out[n++] = ctx->sp.not_;
     return n;
 }
+
+// whisper.cpp's g_lang order: the language token of index i is sot + 1 + i
+const char *const kLangCodes[LANG_MAX] = {
+    "en", "zh", "de", "es", "ru", "ko", "fr", "ja", "pt", "tr", "pl", "ca", "nl", "ar", "sv", "it", "id", "hi", "fi", "vi",
+    "he", "uk", "el", "ms", "cs", "ro", "da", "hu", "ta", "no", "th", "ur", "hr", "bg", "lt", "la", "mi", "ml", "cy", "sk",
+    "te", "fa", "lv", "bn", "sr", "az", "sl", "kn", "et", "mk", "br", "eu", "is", "hy", "ne", "mn", "bs", "kk", "sq", "sw",
+    "gl", "mr", "pa", "si", "km", "sn", "yo", "so", "af", "oc", "ka", "be", "tg", "sd", "gu", "am", "yi", "lo", "uz", "fo",
+    "ht", "ps", "tk", "nn", "mt", "sa", "lb", "my", "bo", "tl", "mg", "as", "tt", "haw", "ln", "ha", "ba", "jw", "su", "yue",
+};
 
 // ---------------------------------------------------------------------------
 // device arena planning
@@ -1704,6 +1728,162 @@ void split_second(wmi_context *ctx, PersistArgs &p1, int B1, int Gh) {
     p1.nres = (ctx->hp.n_vocab + Gh - 1) / Gh;
 }
 
+// device arrays of the language settings, allocated with the first setting
+// that leaves the default (or the first detection)
+int ensure_lang_buffers(wmi_context *ctx) {
+    if (ctx->d_lang) return WMI_OK;
+    const size_t mc = (size_t)ctx->max_clips;
+    const size_t bytes = mc * 4 * 4 + mc * (size_t)ctx->n_lang * 4;
+    void *p = nullptr;
+    HIPCHK(ctx, hipMalloc(&p, bytes));
+    HIPCHK(ctx, hipMemset(p, 0, bytes));
+    ctx->d_lang = (int32_t *)p;
+    ctx->d_lang_auto = ctx->d_lang + mc;
+    ctx->d_lang_det = ctx->d_lang_auto + mc;
+    ctx->d_lang_p = (float *)(ctx->d_lang_det + mc);
+    ctx->d_lang_probs = ctx->d_lang_p + mc;
+    ctx->clear_graphs();
+    return WMI_OK;
+}
+
+// after a setting changed: the default / AUTO flags, and the explicit
+// languages and AUTO flags into d_lang / d_lang_auto
+int upload_lang(wmi_context *ctx) {
+    const size_t mc = (size_t)ctx->max_clips;
+    bool def = ctx->task == WMI_TASK_TRANSCRIBE, any_auto = false;
+    for (size_t c = 0; c < mc; ++c) {
+        def = def && ctx->lang_set[c] == 0;
+        any_auto = any_auto || ctx->lang_set[c] == WMI_LANG_AUTO;
+    }
+    ctx->lang_default = def;
+    ctx->lang_any_auto = any_auto;
+    if (def && !ctx->d_lang) return WMI_OK;
+    int rc = ensure_lang_buffers(ctx);
+    if (rc) return rc;
+    std::vector<int32_t> h(2 * mc);
+    for (size_t c = 0; c < mc; ++c) {
+        h[c] = ctx->lang_set[c] < 0 ? 0 : ctx->lang_set[c];
+        h[mc + c] = ctx->lang_set[c] == WMI_LANG_AUTO ? 1 : 0;
+    }
+    HIPCHK(ctx, hipMemcpy(ctx->d_lang, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    return WMI_OK;
+}
+
+// Language detection of every encoded clip: per block of up to 8 rows one
+// decoder step on [SOT] (the persistent decoder on its full grid, logits into
+// dlogits, no token recorded; or the kernel chain), then k_lang_detect.
+// Enqueues only; zeroes the error word, which the caller reads after its own
+// launches (a decode that follows must not zero it again).
+// The detection step is a plain greedy step: rows are consecutive clips and
+// nothing samples.  It must never be enqueued in beam or timestamp mode
+// (beam_k / ts_mode select the beam rows' shared cross K/V, their kv_src
+// history and the beam / timestamp kernels in enqueue_dec_step and
+// persist_args).  run_beam re-enters itself, and so this function, with
+// beam_k still set after a persistent fallback, so both are cleared here
+// for the duration of the call.
+int run_lang_detect(wmi_context *ctx) {
+    struct Plain {
+        wmi_context *c; int beam_k; bool ts_mode;
+        ~Plain() { c->beam_k = beam_k; c->ts_mode = ts_mode; }
+    } plain{ctx, ctx->beam_k, ctx->ts_mode};
+    ctx->beam_k = 0;
+    ctx->ts_mode = false;
+    const wmi_hparams &hp = ctx->hp;
+    const int Bt = ctx->enc_clips;
+    if (ctx->enc_T <= 0 || Bt < 1) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
+    if (ctx->n_lang < 1) return set_err(ctx, WMI_E_INVALID_ARG, "language detection on an English-only model");
+    int rc = ensure_lang_buffers(ctx);
+    if (rc) return rc;
+    rc = ensure_decode_buffers(ctx, 8, 1);
+    if (rc) return rc;
+    for (int b0 = 0; b0 < Bt; b0 += 8) {
+        const int B = Bt - b0 < 8 ? Bt - b0 : 8;
+        const int G = persist_grid_for(ctx, B);
+        ResetArgs ra{};
+        auto zero = [&](void *p, size_t bytes) {
+            ra.ptr[ra.n] = p;
+            ra.bytes[ra.n++] = bytes;
+        };
+        ra.dfeed = ctx->dfeed;
+        ra.n_feed = 8;
+        for (int b = 0; b < 8; ++b) ra.feed[b] = ctx->sp.sot;
+        if (b0 == 0) zero(ctx->derr, 4);
+        zero(ctx->dstate, sizeof(DecState));
+        zero(ctx->damax, 8 * AMAX_SHARDS * 8);
+        zero(ctx->dsync, ctx->sync_bytes);
+        if (G > 0) zero(ctx->d_xg, ctx->xg_bytes);
+        HIPCHK(ctx, launch_dec_reset(ctx->stream, ra));
+        if (G > 0) {
+            PersistArgs pa = persist_args(ctx, b0, B, G, 1, 1, 0, 1);
+            pa.n_steps = 1;
+            pa.out_stride = 0;  // (record no token: dtokens holds decode results)
+            pa.logits_out = ctx->dlogits;
+            pa.lg_stride = 0;   // (not into the WMI_LOGITS_ALL capture)
+            HIPCHK(ctx, launch_dec_persist(ctx->stream, pa, G));
+        } else {
+            rc = run_dec_steps(ctx, b0, B, 1, 1, 0, 1, 0, 1);
+            if (rc) return rc;
+        }
+        LangArgs la{};
+        la.logits = ctx->dlogits; la.V = hp.n_vocab; la.first = ctx->sp.sot + 1; la.n_lang = ctx->n_lang;
+        la.b0 = b0; la.B = B; la.is_auto = ctx->d_lang_auto; la.lang = ctx->d_lang; la.det = ctx->d_lang_det;
+        la.p = ctx->d_lang_p; la.probs = ctx->d_lang_probs;
+        HIPCHK(ctx, launch_lang_detect(ctx->stream, la));
+    }
+    return WMI_OK;
+}
+
+// run_lang_detect, waited for; a persistent exchange timeout re-runs it on the chain
+int run_lang_detect_sync(wmi_context *ctx) {
+    int rc = run_lang_detect(ctx);
+    if (rc) return rc;
+    uint32_t err = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&err, ctx->derr, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (persist_fallback(ctx, err)) return run_lang_detect_sync(ctx);
+    if (err) return dec_err(ctx, err);
+    return WMI_OK;
+}
+
+// the prompt rows of a decoder block with each row's language token
+// (k_prompt_feed): greedy rows are clips clip0.. (clip_step 1), beam rows the
+// hypotheses of clip0 (clip_step 0)
+int enqueue_prompt_feed(wmi_context *ctx, const int32_t *prompt, int np, int clip0, int clip_step) {
+    PromptFeedArgs fa{};
+    fa.feed = ctx->dfeed; fa.np = np; fa.rows = 8;
+    for (int i = 0; i < np; ++i) fa.prompt[i] = prompt[i];
+    fa.sot = ctx->sp.sot; fa.lang = ctx->d_lang; fa.n_lang = ctx->n_lang;
+    fa.clip0 = clip0; fa.clip_step = clip_step; fa.n_clips = ctx->enc_clips;
+    HIPCHK(ctx, launch_prompt_feed(ctx->stream, fa));
+    return WMI_OK;
+}
+
+// after a decode that did not take the default prompt: the languages it used
+// (and the detection probabilities of the AUTO clips) to the host records
+int record_lang_used(wmi_context *ctx) {
+    const size_t mc = (size_t)ctx->max_clips;
+    if (ctx->lang_default || !ctx->d_lang) {
+        for (size_t c = 0; c < mc; ++c) { ctx->lang_used[c] = 0; ctx->lang_p[c] = -1.0f; }
+        return WMI_OK;
+    }
+    if (!ctx->lang_any_auto) {  // explicit settings only: the host knows them
+        for (size_t c = 0; c < mc; ++c) { ctx->lang_used[c] = ctx->lang_set[c]; ctx->lang_p[c] = -1.0f; }
+        return WMI_OK;
+    }
+    std::vector<int32_t> lg(mc);
+    std::vector<float> p(mc);
+    HIPCHK(ctx, hipMemcpyAsync(lg.data(), ctx->d_lang, mc * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(p.data(), ctx->d_lang_p, mc * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t c = 0; c < mc; ++c) {
+        const bool au = ctx->lang_set[c] == WMI_LANG_AUTO;
+        if (au && (int)c >= ctx->enc_clips) continue;  // no clip decoded in this slot
+        ctx->lang_used[c] = lg[c];
+        ctx->lang_p[c] = au ? p[c] : -1.0f;
+    }
+    return WMI_OK;
+}
+
 // greedy decode of every encoded clip; tokens stay in ctx->dtokens
 // ([enc_clips][n_gen]); returns after enqueueing (no sync) unless early stop.
 int run_greedy(wmi_context *ctx, int n_gen, int suppress_eot, bool early_stop, std::vector<int32_t> *host_tokens,
@@ -1719,6 +1899,14 @@ int run_greedy(wmi_context *ctx, int n_gen, int suppress_eot, bool early_stop, s
     if (rc) return rc;
     if (host_tokens) host_tokens->assign((size_t)Bt * n_gen, 0);
     if (host_counts) host_counts->assign(Bt, n_gen);
+    // a language or task other than the default: detect the AUTO clips'
+    // languages first, then every block's prompt rows are written on the
+    // device behind its reset (no host synchronisation in between)
+    const bool lang_feed = !ctx->lang_default, detect = lang_feed && ctx->lang_any_auto;
+    if (detect) {
+        rc = run_lang_detect(ctx);
+        if (rc) return rc;
+    }
     for (int b0 = 0; b0 < Bt; b0 += 8) {
         const int B = Bt - b0 < 8 ? Bt - b0 : 8;
         const int total_steps = np + n_gen - 1;
@@ -1732,13 +1920,13 @@ int run_greedy(wmi_context *ctx, int n_gen, int suppress_eot, bool early_stop, s
             ra.ptr[ra.n] = p;
             ra.bytes[ra.n++] = bytes;
         };
-        if (b0 == 0) {
+        if (b0 == 0 && !lang_feed) {
             ra.dfeed = ctx->dfeed;
             ra.n_feed = 8 * np;
             for (int b = 0; b < 8; ++b)
                 for (int i = 0; i < np; ++i) ra.feed[b * np + i] = prompt[i];
-            zero(ctx->derr, 4);
         }
+        if (b0 == 0 && !detect) zero(ctx->derr, 4);  // (run_lang_detect zeroed it)
         zero(ctx->dstate, sizeof(DecState));
         zero(ctx->damax, 8 * AMAX_SHARDS * 8);
         zero(ctx->dsync, ctx->sync_bytes);
@@ -1748,6 +1936,10 @@ int run_greedy(wmi_context *ctx, int n_gen, int suppress_eot, bool early_stop, s
             zero(ctx->dstate2, sizeof(DecState));
         }
         HIPCHK(ctx, launch_dec_reset(ctx->stream, ra));
+        if (lang_feed) {
+            rc = enqueue_prompt_feed(ctx, prompt, np, b0, 1);
+            if (rc) return rc;
+        }
         int done_steps = 0;
         while (done_steps < total_steps) {
             int chunk = total_steps - done_steps;
@@ -1756,6 +1948,7 @@ int run_greedy(wmi_context *ctx, int n_gen, int suppress_eot, bool early_stop, s
                 PersistArgs p0 = persist_args(ctx, b0, B1, Gh, np, np, suppress_eot, n_gen);
                 PersistArgs p1 = persist_args(ctx, b0 + B1, B - B1, Gh, np, np, suppress_eot, n_gen);
                 split_second(ctx, p1, B1, Gh);
+                if (lang_feed) p1.feed += (size_t)B1 * np;  // (its rows' own prompts; by default every row's is the same)
                 p0.nres = p1.nres;
                 p0.n_steps = p1.n_steps = chunk;
                 if (ctx->d_ptrace && done_steps == 0 && b0 == 0) p0.ptrace = ctx->d_ptrace;
@@ -1823,7 +2016,7 @@ int run_greedy(wmi_context *ctx, int n_gen, int suppress_eot, bool early_stop, s
             (*host_counts)[b] = cnt;
         }
     }
-    return WMI_OK;
+    return record_lang_used(ctx);
 }
 
 bool valid(const wmi_context *ctx) { return ctx != nullptr && ctx->d_model != nullptr; }
@@ -1849,6 +2042,7 @@ int run_ts_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt
     }
     int rc = ensure_decode_buffers(ctx, np, 1);
     if (rc) return rc;
+    ctx->ts_prompt = prompt;
     HIPCHK(ctx, hipMemcpyAsync(ctx->dfeed, prompt.data(), (size_t)np * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->dstate, 0, sizeof(DecState), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->damax, 0, 8 * AMAX_SHARDS * 8, ctx->stream));
@@ -1919,14 +2113,32 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
     const int n_ctx = ctx->cur_ctx > 0 ? ctx->cur_ctx : hp.n_audio_ctx;
     const int window = 2 * n_ctx, beg = ctx->sp.beg, eot = ctx->sp.eot;
     const int n_max = std::min(max_tokens, hp.n_text_ctx / 2 - 4);
-    std::vector<int32_t> init{ctx->sp.sot};
-    if (ctx->sp.is_multilingual) { init.push_back(ctx->sp.sot + 1); init.push_back(ctx->sp.transcribe); }
+    // clip 0's language and the task; AUTO: detected once, on the first
+    // window (as whisper.cpp does), and kept for every later window
+    int lang = ctx->lang_set[0];
+    float lang_p = -1.0f;
+    std::vector<int32_t> init;
     std::vector<int32_t> past;
     ctx->segments.clear();
     ctx->seg_tokens.clear();
     for (int64_t seek = 0; seek < n_len;) {
         int rc = run_encode(ctx, (int)seek);
         if (rc) return rc;
+        if (init.empty()) {
+            if (lang == WMI_LANG_AUTO) {
+                rc = run_lang_detect_sync(ctx);
+                if (rc) return rc;
+                HIPCHK(ctx, hipMemcpy(&lang, ctx->d_lang_det, 4, hipMemcpyDeviceToHost));
+                HIPCHK(ctx, hipMemcpy(&lang_p, ctx->d_lang_p, 4, hipMemcpyDeviceToHost));
+            }
+            init.push_back(ctx->sp.sot);
+            if (ctx->sp.is_multilingual) {
+                init.push_back(ctx->sp.sot + 1 + lang);
+                init.push_back(ctx->task == WMI_TASK_TRANSLATE ? ctx->sp.translate : ctx->sp.transcribe);
+            }
+            ctx->lang_used[0] = lang;
+            ctx->lang_p[0] = lang_p;
+        }
         std::vector<int32_t> prompt;
         if (!past.empty()) {
             prompt.push_back(ctx->sp.prev);
@@ -1998,10 +2210,18 @@ int run_beam(wmi_context *ctx, int K, int n_gen, int suppress_eot, bool early_st
                        hp.n_text_ctx);
     int rc = ensure_decode_buffers(ctx, 8 * np, 1);
     if (rc) return rc;
-    std::vector<int32_t> feed(8 * np);
-    for (int b = 0; b < 8; ++b)
-        for (int i = 0; i < np; ++i) feed[b * np + i] = prompt[i];
-    HIPCHK(ctx, hipMemcpy(ctx->dfeed, feed.data(), feed.size() * 4, hipMemcpyHostToDevice));
+    // (a language or task other than the default: as in run_greedy, with the
+    // K prompt rows written per clip)
+    const bool lang_feed = !ctx->lang_default, detect = lang_feed && ctx->lang_any_auto;
+    if (!lang_feed) {
+        std::vector<int32_t> feed(8 * np);
+        for (int b = 0; b < 8; ++b)
+            for (int i = 0; i < np; ++i) feed[b * np + i] = prompt[i];
+        HIPCHK(ctx, hipMemcpy(ctx->dfeed, feed.data(), feed.size() * 4, hipMemcpyHostToDevice));
+    } else if (detect) {
+        rc = run_lang_detect(ctx);
+        if (rc) return rc;
+    }
     BeamState init{};
     init.n_active = 1;
     if (out_tokens) out_tokens->assign(Bt, {});
@@ -2009,8 +2229,12 @@ int run_beam(wmi_context *ctx, int K, int n_gen, int suppress_eot, bool early_st
     ctx->beam_k = K;
     ctx->beam_max_tokens = n_gen;
     struct Reset { wmi_context *c; ~Reset() { c->beam_k = 0; } } reset{ctx};
-    HIPCHK(ctx, hipMemsetAsync(ctx->derr, 0, 4, ctx->stream));
+    if (!detect) HIPCHK(ctx, hipMemsetAsync(ctx->derr, 0, 4, ctx->stream));  // (run_lang_detect zeroed it)
     for (int clip = 0; clip < Bt; ++clip) {
+        if (lang_feed) {
+            rc = enqueue_prompt_feed(ctx, prompt, np, clip, 0);
+            if (rc) return rc;
+        }
         HIPCHK(ctx, hipMemsetAsync(ctx->dstate, 0, sizeof(DecState), ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(ctx->dsync, 0, ctx->sync_bytes, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(ctx->dbstate, &init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
@@ -2109,7 +2333,7 @@ int run_beam(wmi_context *ctx, int K, int n_gen, int suppress_eot, bool early_st
         if (out_tokens) (*out_tokens)[clip] = seq;
         if (out_scores) (*out_scores)[clip] = score;
     }
-    return WMI_OK;
+    return record_lang_used(ctx);
 }
 
 }  // namespace
@@ -2176,6 +2400,10 @@ static int wmi_init_from_file_impl(const char *path, int device, int max_clips, 
     ctx->hp = pm.hp;
     ctx->wf32 = pm.hp.f16 % 1000 == 0;
     init_specials(pm.hp.n_vocab, ctx->sp);
+    ctx->n_lang = ctx->sp.is_multilingual ? std::min(LANG_MAX, std::max(0, ctx->sp.translate - (ctx->sp.sot + 1))) : 0;
+    ctx->lang_set.assign(max_clips, 0);
+    ctx->lang_used.assign(max_clips, 0);
+    ctx->lang_p.assign(max_clips, -1.0f);
     // id_to_token incl. extra-token names (main.rs:442-467)
     ctx->vocab = std::move(pm.vocab);
     for (int32_t i = (int32_t)ctx->vocab.size(); i < pm.hp.n_vocab; ++i) {
@@ -2261,6 +2489,7 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->d_expfb) (void)hipFree(ctx->d_expfb);
     if (ctx->d_ptrace) (void)hipFree(ctx->d_ptrace);
     if (ctx->d_lgall) (void)hipFree(ctx->d_lgall);
+    if (ctx->d_lang) (void)hipFree(ctx->d_lang);
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -2286,6 +2515,70 @@ int wmi_set_audio_ctx(wmi_context *ctx, int n_audio_ctx) {
     if (n_audio_ctx < 0 || n_audio_ctx > ctx->hp.n_audio_ctx)
         return set_err(ctx, WMI_E_INVALID_ARG, "audio ctx %d outside [0, %d]", n_audio_ctx, ctx->hp.n_audio_ctx);
     ctx->cur_ctx = n_audio_ctx;
+    return WMI_OK;
+}
+
+// ---- language and task ------------------------------------------------------
+int wmi_lang_index(const char *code, int32_t *index) {
+    if (!code || !index) return set_err(nullptr, WMI_E_INVALID_ARG, "null argument");
+    for (int i = 0; i < LANG_MAX; ++i)
+        if (strcmp(code, kLangCodes[i]) == 0) { *index = i; return WMI_OK; }
+    return set_err(nullptr, WMI_E_INVALID_ARG, "unknown language code \"%.16s\"", code);
+}
+
+const char *wmi_lang_code(int index) { return index >= 0 && index < LANG_MAX ? kLangCodes[index] : nullptr; }
+
+int wmi_lang_count(const wmi_context *ctx, int32_t *n) {
+    if (!ctx || !n) return WMI_E_INVALID_ARG;
+    *n = ctx->n_lang;
+    return WMI_OK;
+}
+
+static int wmi_set_language_impl(wmi_context *ctx, int clip, int lang) {
+    if (!valid(ctx)) return WMI_E_INVALID_ARG;
+    if (clip < -1 || clip >= ctx->max_clips)
+        return set_err(ctx, WMI_E_INVALID_ARG, "clip %d outside [-1, %d)", clip, ctx->max_clips);
+    if (ctx->n_lang == 0 && lang != 0)
+        return set_err(ctx, WMI_E_INVALID_ARG, "language %d on an English-only model (only 0 = en)", lang);
+    if (lang != WMI_LANG_AUTO && (lang < 0 || lang >= std::max(1, ctx->n_lang)))
+        return set_err(ctx, WMI_E_INVALID_ARG, "language index %d outside [0, %d)", lang, std::max(1, ctx->n_lang));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    for (int c = 0; c < ctx->max_clips; ++c)
+        if (clip < 0 || c == clip) {
+            ctx->lang_set[c] = lang;
+            ctx->lang_used[c] = lang;  // (AUTO: until a decode detects it)
+            ctx->lang_p[c] = -1.0f;
+        }
+    return upload_lang(ctx);
+}
+
+static int wmi_set_task_impl(wmi_context *ctx, int task) {
+    if (!valid(ctx)) return WMI_E_INVALID_ARG;
+    if (task != WMI_TASK_TRANSCRIBE && task != WMI_TASK_TRANSLATE) return set_err(ctx, WMI_E_INVALID_ARG, "task %d", task);
+    if (task == WMI_TASK_TRANSLATE && ctx->n_lang == 0)
+        return set_err(ctx, WMI_E_INVALID_ARG, "translate on an English-only model");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ctx->task = task;
+    return upload_lang(ctx);
+}
+
+static int wmi_detect_language_impl(wmi_context *ctx, int32_t *lang, float *probs) {
+    if (!valid(ctx) || !lang) return WMI_E_INVALID_ARG;
+    if (ctx->n_lang == 0) return set_err(ctx, WMI_E_INVALID_ARG, "language detection on an English-only model");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = run_lang_detect_sync(ctx);
+    if (rc) return rc;
+    const size_t nc = (size_t)ctx->enc_clips;
+    HIPCHK(ctx, hipMemcpy(lang, ctx->d_lang_det, nc * 4, hipMemcpyDeviceToHost));
+    if (probs) HIPCHK(ctx, hipMemcpy(probs, ctx->d_lang_probs, nc * ctx->n_lang * 4, hipMemcpyDeviceToHost));
+    return WMI_OK;
+}
+
+int wmi_get_language(const wmi_context *ctx, int clip, int32_t *lang, float *p) {
+    if (!ctx || !lang) return WMI_E_INVALID_ARG;
+    if (clip < 0 || clip >= ctx->max_clips) return WMI_E_INVALID_ARG;
+    *lang = ctx->lang_used[clip];
+    if (p) *p = ctx->lang_p[clip];
     return WMI_OK;
 }
 
@@ -2831,6 +3124,12 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
             memcpy(out, &v, std::min(sizeof v, bytes));
             return WMI_OK;
         }
+        case 19: {  // host: the prompt of the last timestamp window (int32; -1 past its length)
+            const size_t have19 = ctx->ts_prompt.size() * 4;
+            memset(out, 0xff, bytes);
+            memcpy(out, ctx->ts_prompt.data(), std::min(have19, bytes));
+            return WMI_OK;
+        }
         case 11: {  // host: decodes re-run on the kernel chain after a persistent exchange timeout
             const int32_t v = ctx->n_fallbacks;
             memcpy(out, &v, std::min(sizeof v, bytes));
@@ -3010,6 +3309,18 @@ int wmi_run_staged_beam(wmi_context *ctx, int mel_offset, int n_decode, int beam
 
 int wmi_dist_gather_tokens(wmi_context *ctx, int32_t *out, size_t cap) {
     return guarded(ctx, [&] { return wmi_dist_gather_tokens_impl(ctx, out, cap); });
+}
+
+int wmi_set_language(wmi_context *ctx, int clip, int lang) {
+    return guarded(ctx, [&] { return wmi_set_language_impl(ctx, clip, lang); });
+}
+
+int wmi_set_task(wmi_context *ctx, int task) {
+    return guarded(ctx, [&] { return wmi_set_task_impl(ctx, task); });
+}
+
+int wmi_detect_language(wmi_context *ctx, int32_t *lang, float *probs) {
+    return guarded(ctx, [&] { return wmi_detect_language_impl(ctx, lang, probs); });
 }
 
 }  // extern "C"

@@ -285,6 +285,37 @@ struct TsArgs {
 };
 hipError_t launch_ts_sample(hipStream_t s, const TsArgs &a);
 
+// ---- language detection and per-clip prompts --------------------------------
+// (the language token of index i is sot + 1 + i; whisper.cpp's g_lang order)
+constexpr int LANG_MAX = 100;
+// One wave per row of a decoder block over the logits of its [SOT] step:
+// p_i = exp((double)l_i - (double)max) / sum over the n_lang language logits
+// (k_ts_sample's convention), argmax by ts_key (ties: lowest index).
+struct LangArgs {
+    const float *logits;     // [B][V], row b = clip b0 + b
+    int V, first, n_lang;    // language logits [first, first + n_lang), n_lang <= LANG_MAX
+    int b0, B;
+    const int32_t *is_auto;  // [max_clips] != 0: the clip's language setting is AUTO
+    int32_t *lang;           // [max_clips] language the clip's prompt takes (written for AUTO clips only)
+    int32_t *det;            // [max_clips] detected language
+    float *p;                // [max_clips] its probability
+    float *probs;            // [max_clips][n_lang]
+};
+hipError_t launch_lang_detect(hipStream_t s, const LangArgs &a);
+// feed[b * np + i] = prompt[i], slot 1 = sot + 1 + lang[clip of row b] with
+// clip = min(clip0 + b * clip_step, n_clips - 1): greedy rows are consecutive
+// clips (clip_step 1), beam rows the hypotheses of one clip (clip_step 0)
+struct PromptFeedArgs {
+    int32_t *feed;           // [rows][np]
+    int np, rows;
+    int32_t prompt[8];
+    int sot;
+    const int32_t *lang;     // [max_clips]
+    int n_lang;
+    int clip0, clip_step, n_clips;
+};
+hipError_t launch_prompt_feed(hipStream_t s, const PromptFeedArgs &a);
+
 struct DecEmbedArgs {
     const uint16_t *te;      // [V][n]
     const float *pe;         // [n_text_ctx][n]

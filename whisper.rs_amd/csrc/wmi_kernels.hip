@@ -2708,6 +2708,63 @@ hipError_t launch_ts_sample(hipStream_t s, const TsArgs &a) {
     return hipGetLastError();
 }
 
+// ---- language detection: one wave per row over its n_lang language logits ---
+// (at most two logits a lane; registers and cross-lane reductions only)
+__global__ __launch_bounds__(64) void k_lang_detect(LangArgs a) {
+    const int b = blockIdx.x, lane = threadIdx.x, clip = a.b0 + b;
+    const float *l = a.logits + (size_t)b * a.V + a.first;
+    const bool h0 = lane < a.n_lang, h1 = lane + 64 < a.n_lang;
+    const float v0 = h0 ? l[lane] : -INFINITY, v1 = h1 ? l[lane + 64] : -INFINITY;
+    unsigned long long k = h0 ? ts_key(v0, lane) : 0ull;
+    if (h1) k = u64max(k, ts_key(v1, lane + 64));
+    k = wave_max_u64(k);
+    const float mx = wave_max(fmaxf(v0, v1));
+    const double e0 = h0 ? exp((double)v0 - (double)mx) : 0.0, e1 = h1 ? exp((double)v1 - (double)mx) : 0.0;
+    const double Z = wave_sum(e0 + e1);
+    float *pr = a.probs + (size_t)clip * a.n_lang;
+    if (h0) pr[lane] = (float)(e0 / Z);
+    if (h1) pr[lane + 64] = (float)(e1 / Z);
+    int id = ts_key_id(k);
+    if (id < 0 || id >= a.n_lang) id = 0;  // (no finite key: NaN-only logits)
+    if (lane == (id & 63)) {
+        a.det[clip] = id;
+        a.p[clip] = (float)((id < 64 ? e0 : e1) / Z);
+        if (a.is_auto[clip]) a.lang[clip] = id;
+    }
+}
+
+hipError_t launch_lang_detect(hipStream_t s, const LangArgs &a) {
+    if (a.B < 1 || a.B > DEC_ROWS || a.n_lang < 1 || a.n_lang > LANG_MAX || a.first < 0 || a.first + a.n_lang > a.V ||
+        a.b0 < 0)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_lang_detect, dim3(a.B), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+// the block's prompt rows, each with its clip's language token
+__global__ __launch_bounds__(64) void k_prompt_feed(PromptFeedArgs a) {
+    for (int i = threadIdx.x; i < a.rows * a.np; i += 64) {
+        const int b = i / a.np, j = i - b * a.np;
+        int32_t v = a.prompt[j];
+        if (j == 1) {
+            int clip = a.clip0 + b * a.clip_step;
+            clip = clip < a.n_clips ? clip : a.n_clips - 1;
+            int lg = a.lang[clip];
+            lg = lg < 0 || lg >= a.n_lang ? 0 : lg;
+            v = a.sot + 1 + lg;
+        }
+        a.feed[i] = v;
+    }
+}
+
+hipError_t launch_prompt_feed(hipStream_t s, const PromptFeedArgs &a) {
+    if (a.np < 2 || a.np > 8 || a.rows < 1 || a.rows > DEC_ROWS || a.n_clips < 1 || a.clip0 < 0 || a.clip0 >= a.n_clips ||
+        a.n_lang < 1 || a.n_lang > LANG_MAX)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_prompt_feed, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
 // records the token produced by the last step (the in-step record happens in
 // the first layer's QKV prologue): one wave per clip
 __global__ __launch_bounds__(64) void k_dec_record(DecEmbedArgs a) {

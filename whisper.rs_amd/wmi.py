@@ -61,6 +61,8 @@ EXPORTS = (
     "wmi_init_from_file", "wmi_free", "wmi_strerror", "wmi_last_error", "wmi_last_error_global",
     "wmi_get_hparams", "wmi_get_special_tokens", "wmi_set_audio_ctx", "wmi_token_to_bytes",
     "wmi_read_wav", "wmi_pcm16_to_f32", "wmi_tokens_to_text",
+    "wmi_lang_index", "wmi_lang_code", "wmi_lang_count", "wmi_set_language", "wmi_set_task", "wmi_detect_language",
+    "wmi_get_language",
     "wmi_decode_timestamps", "wmi_transcribe", "wmi_get_segment", "wmi_get_segment_tokens",
     "wmi_pcm_to_mel", "wmi_pcm_to_mel_batch", "wmi_encode", "wmi_decode_greedy", "wmi_decode_logits",
     "wmi_decode_beam", "wmi_full", "wmi_stage_pcm", "wmi_run_staged", "wmi_run_staged_beam", "wmi_get_tokens", "wmi_get_timings", "wmi_sync",
@@ -127,6 +129,14 @@ def lib():
         L.wmi_read_wav.argtypes = [C.c_char_p, vp, sz, C.POINTER(sz), C.POINTER(i32), C.POINTER(i32)]
         L.wmi_pcm16_to_f32.argtypes = [vp, sz, vp]
         L.wmi_tokens_to_text.argtypes = [vp, vp, C.c_int, C.c_char_p, sz, C.POINTER(sz)]
+        L.wmi_lang_index.argtypes = [C.c_char_p, C.POINTER(i32)]
+        L.wmi_lang_code.argtypes = [C.c_int]
+        L.wmi_lang_code.restype = C.c_char_p
+        L.wmi_lang_count.argtypes = [vp, C.POINTER(i32)]
+        L.wmi_set_language.argtypes = [vp, C.c_int, C.c_int]
+        L.wmi_set_task.argtypes = [vp, C.c_int]
+        L.wmi_detect_language.argtypes = [vp, vp, vp]
+        L.wmi_get_language.argtypes = [vp, C.c_int, C.POINTER(i32), C.POINTER(C.c_float)]
         L.wmi_decode_timestamps.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(i32)]
         L.wmi_transcribe.argtypes = [vp, vp, sz, C.c_int, C.POINTER(i32)]
         L.wmi_get_segment.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, sz,
@@ -179,6 +189,24 @@ def decode_alg_bytes(hp: dict, rows: int, steps: int, beam: bool = False, q5: bo
     _raise(lib().wmi_decode_alg_bytes(C.byref(h), rows, steps, int(bool(beam)), int(bool(q5)), C.byref(b),
                                       C.byref(f)))
     return b.value, f.value
+
+
+LANG_AUTO = -1
+TASKS = {"transcribe": 0, "translate": 1}
+
+
+def lang_index(code: str) -> int:
+    """Index of a language code ("en" = 0 ... "yue" = 99); the language token
+    is sot + 1 + index.  Raises InvalidArgument on an unknown code."""
+    i = C.c_int32()
+    _raise(lib().wmi_lang_index(code.encode(), C.byref(i)))
+    return i.value
+
+
+def lang_code(index: int):
+    """Code of a language index, or None outside [0, 100)."""
+    c = lib().wmi_lang_code(int(index))
+    return None if c is None else c.decode()
 
 
 def convert_integer_to_float_audio(samples) -> np.ndarray:
@@ -257,6 +285,40 @@ class WhisperContext:
         """exp_n_audio_ctx (main.rs:362, 1803-1807); 0 restores n_audio_ctx."""
         _raise(lib().wmi_set_audio_ctx(self._h, n), self._h)
         self.n_ctx = n or self.hparams["n_audio_ctx"]
+
+    # --- language and task ---------------------------------------------------
+    def n_lang(self) -> int:
+        """Languages of the model: 0 (.en), 99, or 100 (large-v3)."""
+        n = C.c_int32()
+        _raise(lib().wmi_lang_count(self._h, C.byref(n)), self._h)
+        return n.value
+
+    def set_language(self, lang, clip: int = -1) -> None:
+        """lang: a code ("de"), an index, or None = detect per clip at decode
+        time (WMI_LANG_AUTO); clip -1 = every clip.  Holds until changed."""
+        if lang is None:
+            lang = LANG_AUTO
+        elif isinstance(lang, str):
+            lang = lang_index(lang)
+        _raise(lib().wmi_set_language(self._h, clip, int(lang)), self._h)
+
+    def set_task(self, task) -> None:
+        """"transcribe" (default) or "translate"."""
+        _raise(lib().wmi_set_task(self._h, TASKS[task] if isinstance(task, str) else int(task)), self._h)
+
+    def detect_language(self):
+        """(ids [n_clips], probs [n_clips][n_lang]) of the encoded clips."""
+        ids = np.zeros(self.n_clips, np.int32)
+        probs = np.zeros((self.n_clips, self.n_lang()), np.float32)
+        _raise(lib().wmi_detect_language(self._h, _ptr(ids), _ptr(probs)), self._h)
+        return ids, probs
+
+    def language(self, clip: int = 0):
+        """(index, p) the last decode / transcribe used for clip; p is the
+        detection probability, or -1 if the language was set explicitly."""
+        i, p = C.c_int32(), C.c_float()
+        _raise(lib().wmi_get_language(self._h, clip, C.byref(i), C.byref(p)), self._h)
+        return i.value, p.value
 
     def token_to_str(self, tid: int) -> bytes:
         """id_to_token (main.rs:578-592, 442-467)."""
