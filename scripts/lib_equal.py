@@ -1,6 +1,8 @@
 """Bitwise comparison of two builds of the library (scripts/build_variant.sh)
 on the encoder output and the persistent decoder: greedy ids and last-step
-logits of base (1 clip and 8 clips), micro and small.  Usage: lib_equal.py LIB_A LIB_B (run on the gpurun box)."""
+logits of base (1 clip and 8 clips), micro and small; then micro's beam
+search, timestamp window, teacher-forced logits and language detection, so
+every kind of decode run is compared.  Usage: lib_equal.py LIB_A LIB_B (needs the GPU)."""
 import os
 import subprocess
 import sys
@@ -33,6 +35,33 @@ def run_one(out):
         ctx.close()
         res[f"{model}_{nc}_tok"] = toks
         res[f"{model}_{nc}_lg"] = lg
+    # the other decode kinds, on micro (audio ctx 64, 2 s clips): a 2-beam
+    # search, a timestamp window, teacher-forced logits, and language
+    # detection on the language fixture model (tests/test_language.py) if the
+    # model cache holds it
+    os.environ.pop("WMI_PERSIST_LOGITS", None)
+    pcm = [synth.synth_pcm_f32(2.0, 1234 + i) for i in range(2)]
+    ctx = wmi.WhisperContext.new(synth.model_path("micro"), 0, max_clips=2)
+    ctx.set_audio_ctx(64)
+    ctx.pcm_to_mel_batch(pcm)
+    ctx.encode(1, 0)
+    sp = ctx.special
+    for i, (tk, sc) in enumerate(ctx.decode_beam(2, 8, suppress_eot=True)):
+        res[f"beam_tok{i}"], res[f"beam_score{i}"] = tk, np.float64(sc)
+    prompt = [sp["sot"]] + ([sp["sot"] + 1, sp["transcribe"]] if sp["multilingual"] else [])
+    ts = ctx.decode_timestamps(prompt, 6)
+    res["ts_ids"] = np.array([[t["id"], t["tid"]] for t in ts])
+    res["ts_p"] = np.array([[t["p"], t["pt"], t["ptsum"]] for t in ts], np.float32)
+    res["forced_lg"] = ctx.decode_logits((prompt + [sp["not"], 11, 23, 37, 41, 53])[:6], 1)
+    ctx.close()
+    lang = os.path.join(os.environ["WMI_MODEL_CACHE"], "ggml-micro-lang-51865.bin")
+    if os.path.exists(lang):
+        ctx = wmi.WhisperContext.new(lang, 0, max_clips=2)
+        ctx.set_audio_ctx(64)
+        ctx.pcm_to_mel_batch([synth.synth_pcm_tones(2.0, 1234 + i) for i in range(2)])
+        ctx.encode(1, 0)
+        res["lang_ids"], res["lang_probs"] = ctx.detect_language()
+        ctx.close()
     np.savez(out, **res)
 
 

@@ -964,6 +964,56 @@ def test_persistent_beam_matches_chain(wmi, model_cache):
     assert abs(out[0][1] - out[1][1]) < 1e-2, (out[0][1], out[1][1])  # the oracle tests' bound
 
 
+@pytest.mark.parametrize("persist", ["1", "0"])
+def test_no_state_leaks_between_decode_kinds(wmi, micro_model, persist):
+    """One context runs a timestamp window, a greedy decode, a beam search,
+    teacher-forced logits, then the greedy decode and the timestamp window
+    again: every result is bitwise what the same call gives on a fresh
+    context (so no kind leaves step state, sampler state or a decode mode
+    behind), on the persistent decoder and on the kernel chain."""
+    clips = [synth.synth_pcm_f32(2.0, 70 + i) for i in range(2)]
+
+    def new_ctx():
+        ctx = _ctx_with_env(wmi, micro_model, {"WMI_PERSIST": persist}, max_clips=2)
+        ctx.set_audio_ctx(64)
+        ctx.pcm_to_mel_batch(clips)
+        ctx.encode(1, 0)
+        return ctx
+
+    def ts(ctx):
+        sp = ctx.special
+        prompt = [sp["sot"]] + ([sp["sot"] + 1, sp["transcribe"]] if sp["multilingual"] else [])
+        got = ctx.decode_timestamps(prompt, 6)
+        return [np.array([[g["id"], g["tid"]] for g in got]),
+                np.array([[g["p"], g["pt"], g["ptsum"]] for g in got], np.float32)]
+
+    def greedy(ctx):
+        return ctx.decode_greedy(10)
+
+    def beam(ctx):
+        return [a for tk, sc in ctx.decode_beam(2, 8) for a in (tk, np.float64(sc))]
+
+    def forced(ctx):
+        return [ctx.decode_logits(np.concatenate([_prompt(ctx), [11, 23, 37, 41]])[:6], 1)]
+
+    fresh = {}
+    for kind in (ts, greedy, beam, forced):
+        ctx = new_ctx()
+        try:
+            fresh[kind] = kind(ctx)
+        finally:
+            ctx.close()
+    ctx = new_ctx()
+    try:
+        for kind in (ts, greedy, beam, forced, greedy, ts):
+            got = kind(ctx)
+            assert len(got) == len(fresh[kind])
+            for g, f in zip(got, fresh[kind]):
+                np.testing.assert_array_equal(g, f, err_msg=kind.__name__)
+    finally:
+        ctx.close()
+
+
 def test_reference_checksums(wmi, micro_model, oracle_micro):
     """The reference's stage sums from the HIP path (WMI_CHECKSUMS=1) against
     the oracle's: model-only and host sums exactly, the two mel sums within

@@ -221,10 +221,7 @@ struct wmi_context {
     BeamState *dbstate = nullptr;
     int32_t *dkvsrc = nullptr, *dhist_par = nullptr, *dhist_tok = nullptr;
     std::vector<int32_t> kvsrc_init;
-    int beam_k = 0;             // > 0 while enqueueing a beam-search step
-    int beam_max_tokens = 0;
     // timestamp decoding (wmi_transcribe / wmi_decode_timestamps)
-    bool ts_mode = false;       // enqueueing steps with the timestamp sampler
     int32_t *dts_tok = nullptr; // [8] token the sampler chose for the next step
     TsRec *dts_rec = nullptr;   // [n_text_ctx] per generated token
     struct Segment { int64_t t0, t1; int first, count; std::string text; };
@@ -278,7 +275,6 @@ struct wmi_context {
     // decode graph cache
     struct Graph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
     std::map<std::string, Graph> graphs;  // captured decoder steps by configuration
-    int self_mk = 512;                    // key capacity of the self-attention launch being enqueued
     void clear_graphs() {
         for (auto &kv : graphs) {
             if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
@@ -1336,24 +1332,60 @@ int run_encode(wmi_context *ctx, int mel_offset) {
 }
 
 
-// one decoder step for clips [b0, b0 + B) of the encoded batch
-// beam-step kernel arguments of the current beam search
-BeamArgs beam_args(wmi_context *ctx, int feed_len, int suppress_eot) {
+// What a sequence of decoder steps is enqueued for.  Every function that
+// enqueues steps takes the run's descriptor; the context holds no decode mode.
+//   RUN_GREEDY  rows are consecutive clips; the argmax of a step feeds the next
+//               and is recorded in dtokens ([.][out_stride])
+//   RUN_BEAM    rows are the K hypotheses of clip b0; k_beam_step follows a step
+//   RUN_TS      one row; the timestamp sampler (k_ts_sample) follows a step
+//   RUN_FORCED  the feed supplies every token (teacher forcing, the [SOT] step
+//               of language detection): each step's logits stay in dlogits and
+//               nothing is recorded
+enum RunKind { RUN_GREEDY, RUN_BEAM, RUN_TS, RUN_FORCED };
+struct DecRun {
+    RunKind kind = RUN_GREEDY;
+    int b0 = 0, B = 1;            // clips [b0, b0 + B) of the encoded batch (beam: clip b0, B = K rows)
+    int feed_len = 1, feed_stride = 1, suppress_eot = 0, out_stride = 1;
+    int K = 0, max_tokens = 0;    // beam width and token limit (RUN_BEAM)
+    int mk = 512;                 // key capacity of the self-attention launch being enqueued (run_dec_steps)
+};
+
+// beam-step kernel arguments of a beam run
+BeamArgs beam_args(wmi_context *ctx, const DecRun &run) {
     const wmi_hparams &hp = ctx->hp;
     BeamArgs ba{};
-    ba.logits = ctx->dlogits; ba.V = hp.n_vocab; ba.K = ctx->beam_k; ba.suppress_id = suppress_eot ? ctx->sp.eot : -1;
-    ba.eot = ctx->sp.eot; ba.feed_len = feed_len; ba.max_tokens = ctx->beam_max_tokens; ba.tctx = hp.n_text_ctx;
+    ba.logits = ctx->dlogits; ba.V = hp.n_vocab; ba.K = run.K; ba.suppress_id = run.suppress_eot ? ctx->sp.eot : -1;
+    ba.eot = ctx->sp.eot; ba.feed_len = run.feed_len; ba.max_tokens = run.max_tokens; ba.tctx = hp.n_text_ctx;
     ba.st = ctx->dstate; ba.parts = ctx->dbparts; ba.bs = ctx->dbstate; ba.kv_src = ctx->dkvsrc;
     ba.hist_parent = ctx->dhist_par; ba.hist_tok = ctx->dhist_tok;
     return ba;
 }
 
-int enqueue_dec_step(wmi_context *ctx, int b0, int B, int feed_len, int feed_stride, int suppress_eot, int out_stride) {
+// timestamp-sampler arguments of a timestamp run
+TsArgs ts_args(wmi_context *ctx, const DecRun &run) {
+    TsArgs ta{};
+    ta.logits = ctx->dlogits; ta.V = ctx->hp.n_vocab; ta.beg = ctx->sp.beg; ta.eot = ctx->sp.eot; ta.sot = ctx->sp.sot;
+    ta.solm = ctx->sp.solm; ta.not_ = ctx->sp.not_; ta.feed_len = run.feed_len; ta.max_rec = ctx->hp.n_text_ctx;
+    ta.st = ctx->dstate; ta.tok_out = ctx->dts_tok; ta.rec = ctx->dts_rec;
+    return ta;
+}
+
+// the kernel that follows a step's logits: the run kind's sampler, if any
+// (after the last kernel of a chain step, after a one-step persistent launch)
+int enqueue_step_tail(wmi_context *ctx, const DecRun &run) {
+    if (run.kind == RUN_TS) HIPCHK(ctx, launch_ts_sample(ctx->stream, ts_args(ctx, run)));
+    if (run.kind == RUN_BEAM) HIPCHK(ctx, launch_beam_step(ctx->stream, beam_args(ctx, run)));
+    return WMI_OK;
+}
+
+// one decoder step of the run on the kernel chain
+int enqueue_dec_step(wmi_context *ctx, const DecRun &run) {
     const wmi_hparams &hp = ctx->hp;
     const int n = hp.n_text_state, H = hp.n_text_head, T = ctx->enc_T, Bt = ctx->enc_clips;
+    const int b0 = run.b0, B = run.B;
     hipStream_t s = ctx->stream;
     const float qs = powf((float)n / (float)H, -0.25f);
-    const bool beam = ctx->beam_k > 0;
+    const bool beam = run.kind == RUN_BEAM, ts = run.kind == RUN_TS;
     // per layer: [LN+QKV (+embed at l=0)] [self-attn] [Wo+res] [LN+Wcq+cross scores]
     //            [cross softmax+PV] [Wco+res] [LN+W0+GELU] [W1+res]; then LN+logits+argmax
     // residual stream: dx, or with the fused output projection alternating
@@ -1383,14 +1415,14 @@ int enqueue_dec_step(wmi_context *ctx, int b0, int B, int feed_len, int feed_str
         g.qscale = qs; g.out16 = ctx->dq16; g.ldo = n; g.kcache = kc; g.vcache = vc; g.n_text_ctx = hp.n_text_ctx;
         g.st = ctx->dstate;
         if (l == 0) {
-            g.te = ctx->te; g.pe = ctx->d_pe; g.feed = ctx->dfeed; g.feed_len = feed_len; g.feed_stride = feed_stride;
+            g.te = ctx->te; g.pe = ctx->d_pe; g.feed = ctx->dfeed; g.feed_len = run.feed_len; g.feed_stride = run.feed_stride;
             if (f32) { g.te32 = W32(ctx->te); g.te = nullptr; }
-            g.amax = ctx->damax; g.tokens_out = ctx->dtokens + (size_t)b0 * out_stride; g.out_stride = out_stride;
+            g.amax = ctx->damax; g.tokens_out = ctx->dtokens + (size_t)b0 * run.out_stride; g.out_stride = run.out_stride;
             g.x_out = X[cur];
             if (beam) {
                 g.tokens_out = nullptr;
                 g.beam_tok = ctx->dbstate->tok;
-            } else if (ctx->ts_mode) {
+            } else if (ts) {
                 g.tokens_out = nullptr;
                 g.beam_tok = ctx->dts_tok;
             }
@@ -1398,7 +1430,7 @@ int enqueue_dec_step(wmi_context *ctx, int b0, int B, int feed_len, int feed_str
         HIPCHK(ctx, launch_dec_gemv(s, DEC_QKV, g));
         DecAttnArgs at{}; at.tune = &ctx->tune;
         at.q = ctx->dq16; at.K = kc; at.V = vc; at.clip_stride = (int64_t)hp.n_text_ctx * n; at.M_fixed = 0;
-        at.mk = ctx->self_mk; at.err = ctx->derr;
+        at.mk = run.mk; at.err = ctx->derr;
         at.st = ctx->dstate; at.S = ctx->dS; at.s_stride = ctx->s_stride; at.cmax = ctx->dcmax;
         at.opart = ctx->dopart; at.n_chunks = 1; at.exp_tab = ctx->exp_tab; at.n_exp = ctx->n_exp;
         at.H = H; at.n = n; at.B = B;
@@ -1466,22 +1498,11 @@ int enqueue_dec_step(wmi_context *ctx, int b0, int B, int feed_len, int feed_str
     g.x = X[cur]; g.ln_w = ctx->dln_w; g.ln_b = ctx->dln_b; g.W = ctx->te; g.N = hp.n_vocab; g.K = n; g.B = B;
     g.Wq5 = ctx->use_q5 ? ctx->te5 : nullptr;
     g.W32 = W32(ctx->te);
-    g.out32 = ctx->dlogits; g.amax = ctx->damax; g.suppress_id = suppress_eot ? ctx->sp.eot : -1;
+    g.out32 = ctx->dlogits; g.amax = ctx->damax; g.suppress_id = run.suppress_eot ? ctx->sp.eot : -1;
     g.st_advance = ctx->dstate;
-    if (beam || ctx->ts_mode) g.amax = nullptr;
+    if (beam || ts) g.amax = nullptr;
     HIPCHK(ctx, launch_dec_gemv(s, DEC_LOGITS, g));
-    if (ctx->ts_mode) {
-        TsArgs ta{};
-        ta.logits = ctx->dlogits; ta.V = hp.n_vocab; ta.beg = ctx->sp.beg; ta.eot = ctx->sp.eot; ta.sot = ctx->sp.sot;
-        ta.solm = ctx->sp.solm; ta.not_ = ctx->sp.not_; ta.feed_len = feed_len; ta.max_rec = hp.n_text_ctx;
-        ta.st = ctx->dstate; ta.tok_out = ctx->dts_tok; ta.rec = ctx->dts_rec;
-        HIPCHK(ctx, launch_ts_sample(s, ta));
-    }
-    if (beam) {
-        BeamArgs ba = beam_args(ctx, feed_len, suppress_eot);
-        HIPCHK(ctx, launch_beam_step(s, ba));
-    }
-    return WMI_OK;
+    return enqueue_step_tail(ctx, run);
 }
 
 int ensure_decode_buffers(wmi_context *ctx, int feed_elems, size_t token_elems) {
@@ -1526,19 +1547,31 @@ bool persist_fallback(wmi_context *ctx, uint32_t err) {
     return true;
 }
 
-// run `steps` decoder steps for clips [b0, b0+B), the first at position pos0,
-// via captured hipGraphs: one per configuration and self-attention key
-// capacity, so a chunk is split where pos + 1 crosses 64 / 128 / 256
-int run_dec_steps(wmi_context *ctx, int b0, int B, int feed_len, int feed_stride, int suppress_eot, int out_stride,
-                  int pos0, int steps) {
+// The end of a decode run: wait for the stream and read the device error
+// word.  WMI_OK, an error, or RERUN_ON_CHAIN: the persistent decoder timed
+// out and the caller enqueues the whole run again (now on the kernel chain).
+constexpr int RERUN_ON_CHAIN = -1;
+int finish_run(wmi_context *ctx) {
+    uint32_t err = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&err, ctx->derr, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (persist_fallback(ctx, err)) return RERUN_ON_CHAIN;
+    return err ? dec_err(ctx, err) : WMI_OK;
+}
+
+// run `steps` decoder steps of the run, the first at position pos0, via
+// captured hipGraphs: one per configuration and self-attention key capacity,
+// so a chunk is split where pos + 1 crosses 64 / 128 / 256
+int run_dec_steps(wmi_context *ctx, const DecRun &run0, int pos0, int steps) {
+    DecRun run = run0;
     for (int done = 0; done < steps;) {
         const int mk = self_mk_for(pos0 + done + 1);
         int n = steps - done;
         if (mk < 512 && pos0 + done + n > mk) n = mk - (pos0 + done);
-        ctx->self_mk = mk;
+        run.mk = mk;
         if (!ctx->use_graph) {
             for (int i = 0; i < n; ++i) {
-                int rc = enqueue_dec_step(ctx, b0, B, feed_len, feed_stride, suppress_eot, out_stride);
+                int rc = enqueue_dec_step(ctx, run);
                 if (rc) return rc;
             }
             done += n;
@@ -1549,15 +1582,16 @@ int run_dec_steps(wmi_context *ctx, int b0, int B, int feed_len, int feed_stride
         for (int reps : {ctx->tune.graph_steps, 1}) {  // (base: 1 -> 8 steps 31.4 -> 30.9 ms)
             if (reps < 1 || (reps > 1 && n < reps)) continue;
             char key[192];
-            snprintf(key, sizeof key, "%d/%d/%d/%d/%d/%d/%d/%d/%p/%p/%d/%d/%d/%d/%d", b0, B, feed_len, feed_stride,
-                     suppress_eot, out_stride, ctx->enc_T, ctx->enc_clips, (void *)ctx->dfeed, (void *)ctx->dtokens,
-                     ctx->beam_k, ctx->beam_max_tokens, mk, (int)ctx->ts_mode, reps);
+            // (a forced step enqueues what a greedy step does: they share graphs)
+            snprintf(key, sizeof key, "%d/%d/%d/%d/%d/%d/%d/%d/%p/%p/%d/%d/%d/%d/%d", run.b0, run.B, run.feed_len,
+                     run.feed_stride, run.suppress_eot, run.out_stride, ctx->enc_T, ctx->enc_clips, (void *)ctx->dfeed,
+                     (void *)ctx->dtokens, run.K, run.max_tokens, mk, (int)(run.kind == RUN_TS), reps);
             auto it = ctx->graphs.find(key);
             if (it == ctx->graphs.end()) {
                 if (ctx->graphs.size() >= 32) ctx->clear_graphs();
                 HIPCHK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
                 int rc = 0;
-                for (int r = 0; r < reps && !rc; ++r) rc = enqueue_dec_step(ctx, b0, B, feed_len, feed_stride, suppress_eot, out_stride);
+                for (int r = 0; r < reps && !rc; ++r) rc = enqueue_dec_step(ctx, run);
                 hipGraph_t graph = nullptr;
                 hipError_t ce = hipStreamEndCapture(ctx->stream, &graph);
                 if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
@@ -1655,11 +1689,15 @@ int persist_grid_for(wmi_context *ctx, int B) {
     return ctx->persist_G[B];
 }
 
-// launch arguments of the persistent decoder for rows [b0, b0 + B)
-PersistArgs persist_args(wmi_context *ctx, int b0, int B, int G, int feed_len, int feed_stride, int suppress_eot,
-                         int out_stride) {
+// launch arguments of the persistent decoder for the run's rows on G
+// workgroups: a greedy launch of several steps as it stands (the caller sets
+// n_steps); any other kind runs one step per launch, logits into dlogits for
+// the kernel or the copy that follows, no token recorded
+PersistArgs persist_args(wmi_context *ctx, const DecRun &run, int G) {
     const wmi_hparams &hp = ctx->hp;
     const int n = hp.n_text_state, H = hp.n_text_head, T = ctx->enc_T;
+    const int b0 = run.b0, B = run.B, out_stride = run.out_stride;
+    const bool beam = run.kind == RUN_BEAM;
     PersistArgs a{};
     a.layers = ctx->d_players; a.te = ctx->te; a.pe = ctx->d_pe; a.dln_w = ctx->dln_w; a.dln_b = ctx->dln_b;
     a.gelu_tab = ctx->gelu_tab; a.exp_tab = ctx->exp_tab; a.n_exp = ctx->n_exp; a.exp_fb = ctx->d_expfb;
@@ -1676,10 +1714,10 @@ PersistArgs persist_args(wmi_context *ctx, int b0, int B, int G, int feed_len, i
     // (the shared tasks run on 128-key chunks, one round of the grid: when
     // H * ceil(T / 128) exceeds G — a smaller grid, a part with fewer CUs —
     // the launch takes the per-row tasks instead of a rejected configuration)
-    const int rows_t = ctx->beam_k > 0 && n > 768 && ctx->use_xshare && (int64_t)H * ((T + 127) / 128) <= G ? 1 : B;
+    const int rows_t = beam && n > 768 && ctx->use_xshare && (int64_t)H * ((T + 127) / 128) <= G ? 1 : B;
     // (the one-row instance's tasks hold two 128-key sub-chunks: cl <= 256;
     // more tasks than workgroups then take several rounds of the grid)
-    const int cl_max = B == 1 && ctx->beam_k == 0 ? 256 : 512;
+    const int cl_max = B == 1 && !beam ? 256 : 512;
     int cl = 128;
     while (cl < cl_max &&
            ((int64_t)rows_t * H * ((T + cl - 1) / cl) > G || (int64_t)B * H * ((T + cl - 1) / cl) > PX_TASKS))
@@ -1688,9 +1726,9 @@ PersistArgs persist_args(wmi_context *ctx, int b0, int B, int G, int feed_len, i
     a.nch = (T + cl - 1) / cl;
     a.xshare = rows_t == 1 && B > 1 ? 1 : 0;
     a.qscale = powf((float)n / (float)H, -0.25f);
-    a.st = ctx->dstate; a.feed = ctx->dfeed; a.feed_len = feed_len; a.feed_stride = feed_stride;
+    a.st = ctx->dstate; a.feed = ctx->dfeed; a.feed_len = run.feed_len; a.feed_stride = run.feed_stride;
     a.tokens_out = ctx->dtokens + (size_t)b0 * out_stride; a.out_stride = out_stride;
-    a.cur_tok = ctx->d_curtok; a.suppress_id = suppress_eot ? ctx->sp.eot : -1;
+    a.cur_tok = ctx->d_curtok; a.suppress_id = run.suppress_eot ? ctx->sp.eot : -1;
     a.xg = ctx->d_xg; a.err = ctx->derr;
     a.nres = ctx->persist_nres[B];
     a.vreg = ctx->persist_vreg ? 1 : 0;
@@ -1710,22 +1748,128 @@ PersistArgs persist_args(wmi_context *ctx, int b0, int B, int G, int feed_len, i
     // (profiles/r03/q5_ab.txt); WMI_PERSIST_Q5=0 selects the f16 copies
     const bool have5 = ctx->use_q5 && !ctx->dec.empty() && ctx->dec[0].wqkv5;
     a.q5 = have5 && ctx->persist_q5 != 0 ? 1 : 0;
+    if (run.kind == RUN_GREEDY) return a;
+    a.n_steps = 1;
+    a.logits_out = ctx->dlogits;  // (the kind's sampler or the caller reads this step's rows)
+    a.lg_stride = 0;              // (not into the WMI_LOGITS_ALL capture)
+    if (beam) {  // rows = the beam slots of clip b0; the beam kernels select between launches
+        a.beam = 1;
+        a.cur_tok = ctx->dbstate->tok;
+        a.kv_src = ctx->dkvsrc;
+        a.kv_src_stride = hp.n_text_ctx;
+        a.tokens_out = ctx->dtokens;  // (unused: no argmax in beam mode)
+    } else {
+        a.out_stride = 0;  // (record no token: dtokens holds decode results)
+        // the timestamp sampler picks the next token into dts_tok, which the next launch feeds
+        if (run.kind == RUN_TS) a.cur_tok = ctx->dts_tok;
+    }
     return a;
 }
 
-// the second half-grid launch of a split block (rows B1.. of the block): its
-// own exchange block and step state, self-attention cache rows B1.., argmax
-// carry and logits rows B1..; every workgroup owns twice the vocabulary rows
-// of the full grid, so as many of them stay resident as the LDS holds
-void split_second(wmi_context *ctx, PersistArgs &p1, int B1, int Gh) {
-    const size_t row = (size_t)ctx->hp.n_text_ctx * ctx->hp.n_text_state;
-    p1.xg = ctx->d_xg2;
-    p1.st = ctx->dstate2;
-    p1.kcache = ctx->kcache + B1 * row;
-    p1.vcache = ctx->vcache + B1 * row;
-    p1.cur_tok = ctx->d_curtok + B1;
-    if (ctx->persist_logits && !ctx->d_lgall) p1.logits_out += (size_t)B1 * ctx->hp.n_vocab;  // (dlogits rows B1..)
-    p1.nres = (ctx->hp.n_vocab + Gh - 1) / Gh;
+// Zero the state a run (or its next 8-row block) starts from, in one launch:
+// the error word once per run (`first` block, unless language detection has
+// run in front and zeroed it: the caller reads the word after its own
+// launches), step state, argmax shards, chain sync words, and the exchange
+// blocks of a persistent grid G (and of the split grids Gh).  A feed of up to
+// 64 words rides in the launch; a longer one is copied.
+int reset_run(wmi_context *ctx, bool first, int G, int Gh, bool err_cleared, const int32_t *feed, int n_feed) {
+    ResetArgs ra{};
+    auto zero = [&](void *p, size_t bytes) {
+        ra.ptr[ra.n] = p;
+        ra.bytes[ra.n++] = bytes;
+    };
+    if (feed && n_feed <= 64) {
+        ra.dfeed = ctx->dfeed;
+        ra.n_feed = n_feed;
+        for (int i = 0; i < n_feed; ++i) ra.feed[i] = feed[i];
+    } else if (feed) {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->dfeed, feed, (size_t)n_feed * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (first && !err_cleared) zero(ctx->derr, 4);
+    zero(ctx->dstate, sizeof(DecState));
+    zero(ctx->damax, 8 * AMAX_SHARDS * 8);
+    zero(ctx->dsync, ctx->sync_bytes);
+    if (G > 0) zero(ctx->d_xg, ctx->xg_bytes);
+    if (Gh > 0) {
+        zero(ctx->d_xg2, ctx->xg_bytes);
+        zero(ctx->dstate2, sizeof(DecState));
+    }
+    HIPCHK(ctx, launch_dec_reset(ctx->stream, ra));
+    return WMI_OK;
+}
+
+// The persistent grids of a run of B rows: G (0: kernel chain), and for a
+// greedy block of at least split_rows rows the half grids Gh (0: one launch)
+struct RunGrid { int G, Gh; };
+RunGrid run_grid(wmi_context *ctx, const DecRun &run) {
+    const int G = persist_grid_for(ctx, run.B);
+    const bool split = run.kind == RUN_GREEDY && G > 0 && ctx->split_rows > 1 && run.B >= ctx->split_rows;
+    return {G, split ? persist_split_grid(ctx->hp.n_text_state, G) : 0};
+}
+
+// Advance the run by `steps` steps from position pos0: a greedy run's steps in
+// one persistent launch (two concurrent half-grid launches when split), any
+// other kind's one per launch, each followed by the kind's tail kernel; or,
+// without a persistent grid, the kernel chain
+int advance_run(wmi_context *ctx, const DecRun &run, RunGrid gr, int pos0, int steps) {
+    const wmi_hparams &hp = ctx->hp;
+    const int G = gr.G, Gh = gr.Gh;
+    if (G <= 0) return run_dec_steps(ctx, run, pos0, steps);
+    if (run.kind != RUN_GREEDY) {
+        for (int i = 0; i < steps; ++i) {
+            PersistArgs pa = persist_args(ctx, run, G);
+            const int s_all = pos0 + i;
+            // WMI_PTRACE: step s of a beam search's clip 0 stamps slot s (its
+            // phase A then includes the launch gap and the beam kernels)
+            if (run.kind == RUN_BEAM && ctx->d_ptrace && run.b0 == 0 && s_all < hp.n_text_ctx)
+                pa.ptrace = ctx->d_ptrace + (size_t)s_all * (hp.n_text_layer + 1) * 32 * 2;
+            HIPCHK(ctx, launch_dec_persist(ctx->stream, pa, G));
+            if (run.kind == RUN_BEAM && ctx->d_lgall && s_all < hp.n_text_ctx)  // WMI_LOGITS_ALL: this step's [K][V]
+                HIPCHK(ctx, hipMemcpyAsync(ctx->d_lgall + (size_t)s_all * ctx->lg_rows * hp.n_vocab, ctx->dlogits,
+                                           (size_t)run.K * hp.n_vocab * 4, hipMemcpyDeviceToDevice, ctx->stream));
+            int rc = enqueue_step_tail(ctx, run);
+            if (rc) return rc;
+        }
+        return WMI_OK;
+    }
+    // WMI_PTRACE: the phase clocks of the run's first launch
+    unsigned long long *ptrace = ctx->d_ptrace && pos0 == 0 && run.b0 == 0 ? ctx->d_ptrace : nullptr;
+    if (Gh > 0) {  // two half-grid launches, rows [b0, b0 + B1) and [b0 + B1, b0 + B)
+        const int B1 = run.B / 2;
+        DecRun r0 = run, r1 = run;
+        r0.B = B1;
+        r1.b0 = run.b0 + B1;
+        r1.B = run.B - B1;
+        PersistArgs p0 = persist_args(ctx, r0, Gh);
+        PersistArgs p1 = persist_args(ctx, r1, Gh);
+        // the second launch: its own exchange block and step state, the feed's
+        // and the self-attention cache's rows B1.., argmax carry and logits
+        // rows B1..; every workgroup owns twice the vocabulary rows of the full
+        // grid, so as many of them stay resident as the LDS holds
+        const size_t row = (size_t)hp.n_text_ctx * hp.n_text_state;
+        p1.xg = ctx->d_xg2;
+        p1.st = ctx->dstate2;
+        p1.feed += (size_t)B1 * run.feed_stride;
+        p1.kcache = ctx->kcache + B1 * row;
+        p1.vcache = ctx->vcache + B1 * row;
+        p1.cur_tok = ctx->d_curtok + B1;
+        if (ctx->persist_logits && !ctx->d_lgall) p1.logits_out += (size_t)B1 * hp.n_vocab;  // (dlogits rows B1..)
+        p0.nres = p1.nres = (hp.n_vocab + Gh - 1) / Gh;
+        p0.n_steps = p1.n_steps = steps;
+        p0.ptrace = ptrace;
+        HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+        HIPCHK(ctx, launch_dec_persist(ctx->stream, p0, Gh));
+        HIPCHK(ctx, launch_dec_persist(ctx->stream2, p1, Gh));
+        HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+    } else {  // the steps in one launch
+        PersistArgs pa = persist_args(ctx, run, G);
+        pa.n_steps = steps;
+        pa.ptrace = ptrace;
+        HIPCHK(ctx, launch_dec_persist(ctx->stream, pa, G));
+    }
+    return ptrace ? ptrace_dump(ctx, steps) : WMI_OK;
 }
 
 // device arrays of the language settings, allocated with the first setting
@@ -1770,24 +1914,11 @@ int upload_lang(wmi_context *ctx) {
 }
 
 // Language detection of every encoded clip: per block of up to 8 rows one
-// decoder step on [SOT] (the persistent decoder on its full grid, logits into
-// dlogits, no token recorded; or the kernel chain), then k_lang_detect.
-// Enqueues only; zeroes the error word, which the caller reads after its own
-// launches (a decode that follows must not zero it again).
-// The detection step is a plain greedy step: rows are consecutive clips and
-// nothing samples.  It must never be enqueued in beam or timestamp mode
-// (beam_k / ts_mode select the beam rows' shared cross K/V, their kv_src
-// history and the beam / timestamp kernels in enqueue_dec_step and
-// persist_args).  run_beam re-enters itself, and so this function, with
-// beam_k still set after a persistent fallback, so both are cleared here
-// for the duration of the call.
+// forced decoder step on [SOT] (rows are consecutive clips, logits into
+// dlogits, no token recorded), then k_lang_detect.  Enqueues only; zeroes the
+// error word, which the caller reads after its own launches (a decode that
+// follows must not zero it again).
 int run_lang_detect(wmi_context *ctx) {
-    struct Plain {
-        wmi_context *c; int beam_k; bool ts_mode;
-        ~Plain() { c->beam_k = beam_k; c->ts_mode = ts_mode; }
-    } plain{ctx, ctx->beam_k, ctx->ts_mode};
-    ctx->beam_k = 0;
-    ctx->ts_mode = false;
     const wmi_hparams &hp = ctx->hp;
     const int Bt = ctx->enc_clips;
     if (ctx->enc_T <= 0 || Bt < 1) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
@@ -1796,37 +1927,18 @@ int run_lang_detect(wmi_context *ctx) {
     if (rc) return rc;
     rc = ensure_decode_buffers(ctx, 8, 1);
     if (rc) return rc;
+    int32_t feed[8];
+    for (int b = 0; b < 8; ++b) feed[b] = ctx->sp.sot;
     for (int b0 = 0; b0 < Bt; b0 += 8) {
-        const int B = Bt - b0 < 8 ? Bt - b0 : 8;
-        const int G = persist_grid_for(ctx, B);
-        ResetArgs ra{};
-        auto zero = [&](void *p, size_t bytes) {
-            ra.ptr[ra.n] = p;
-            ra.bytes[ra.n++] = bytes;
-        };
-        ra.dfeed = ctx->dfeed;
-        ra.n_feed = 8;
-        for (int b = 0; b < 8; ++b) ra.feed[b] = ctx->sp.sot;
-        if (b0 == 0) zero(ctx->derr, 4);
-        zero(ctx->dstate, sizeof(DecState));
-        zero(ctx->damax, 8 * AMAX_SHARDS * 8);
-        zero(ctx->dsync, ctx->sync_bytes);
-        if (G > 0) zero(ctx->d_xg, ctx->xg_bytes);
-        HIPCHK(ctx, launch_dec_reset(ctx->stream, ra));
-        if (G > 0) {
-            PersistArgs pa = persist_args(ctx, b0, B, G, 1, 1, 0, 1);
-            pa.n_steps = 1;
-            pa.out_stride = 0;  // (record no token: dtokens holds decode results)
-            pa.logits_out = ctx->dlogits;
-            pa.lg_stride = 0;   // (not into the WMI_LOGITS_ALL capture)
-            HIPCHK(ctx, launch_dec_persist(ctx->stream, pa, G));
-        } else {
-            rc = run_dec_steps(ctx, b0, B, 1, 1, 0, 1, 0, 1);
-            if (rc) return rc;
-        }
+        const DecRun run{RUN_FORCED, b0, Bt - b0 < 8 ? Bt - b0 : 8};
+        const RunGrid gr = run_grid(ctx, run);
+        rc = reset_run(ctx, b0 == 0, gr.G, gr.Gh, false, feed, 8);
+        if (rc) return rc;
+        rc = advance_run(ctx, run, gr, 0, 1);
+        if (rc) return rc;
         LangArgs la{};
         la.logits = ctx->dlogits; la.V = hp.n_vocab; la.first = ctx->sp.sot + 1; la.n_lang = ctx->n_lang;
-        la.b0 = b0; la.B = B; la.is_auto = ctx->d_lang_auto; la.lang = ctx->d_lang; la.det = ctx->d_lang_det;
+        la.b0 = b0; la.B = run.B; la.is_auto = ctx->d_lang_auto; la.lang = ctx->d_lang; la.det = ctx->d_lang_det;
         la.p = ctx->d_lang_p; la.probs = ctx->d_lang_probs;
         HIPCHK(ctx, launch_lang_detect(ctx->stream, la));
     }
@@ -1835,14 +1947,13 @@ int run_lang_detect(wmi_context *ctx) {
 
 // run_lang_detect, waited for; a persistent exchange timeout re-runs it on the chain
 int run_lang_detect_sync(wmi_context *ctx) {
-    int rc = run_lang_detect(ctx);
-    if (rc) return rc;
-    uint32_t err = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&err, ctx->derr, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (persist_fallback(ctx, err)) return run_lang_detect_sync(ctx);
-    if (err) return dec_err(ctx, err);
-    return WMI_OK;
+    int rc;
+    do {
+        rc = run_lang_detect(ctx);
+        if (rc) return rc;
+        rc = finish_run(ctx);
+    } while (rc == RERUN_ON_CHAIN);
+    return rc;
 }
 
 // the prompt rows of a decoder block with each row's language token
@@ -1903,107 +2014,60 @@ int run_greedy(wmi_context *ctx, int n_gen, int suppress_eot, bool early_stop, s
     // languages first, then every block's prompt rows are written on the
     // device behind its reset (no host synchronisation in between)
     const bool lang_feed = !ctx->lang_default, detect = lang_feed && ctx->lang_any_auto;
-    if (detect) {
-        rc = run_lang_detect(ctx);
-        if (rc) return rc;
-    }
-    for (int b0 = 0; b0 < Bt; b0 += 8) {
-        const int B = Bt - b0 < 8 ? Bt - b0 : 8;
-        const int total_steps = np + n_gen - 1;
-        const int G = persist_grid_for(ctx, B);
-        const int B1 = B / 2, Gh = G > 0 && ctx->split_rows > 1 && B >= ctx->split_rows
-                                       ? persist_split_grid(ctx->hp.n_text_state, G) : 0;
-        // prompt feed (first block), error word, step state, argmax shards,
-        // chain sync words and exchange blocks: one reset launch
-        ResetArgs ra{};
-        auto zero = [&](void *p, size_t bytes) {
-            ra.ptr[ra.n] = p;
-            ra.bytes[ra.n++] = bytes;
-        };
-        if (b0 == 0 && !lang_feed) {
-            ra.dfeed = ctx->dfeed;
-            ra.n_feed = 8 * np;
-            for (int b = 0; b < 8; ++b)
-                for (int i = 0; i < np; ++i) ra.feed[b * np + i] = prompt[i];
-        }
-        if (b0 == 0 && !detect) zero(ctx->derr, 4);  // (run_lang_detect zeroed it)
-        zero(ctx->dstate, sizeof(DecState));
-        zero(ctx->damax, 8 * AMAX_SHARDS * 8);
-        zero(ctx->dsync, ctx->sync_bytes);
-        if (G > 0) zero(ctx->d_xg, ctx->xg_bytes);
-        if (Gh > 0) {
-            zero(ctx->d_xg2, ctx->xg_bytes);
-            zero(ctx->dstate2, sizeof(DecState));
-        }
-        HIPCHK(ctx, launch_dec_reset(ctx->stream, ra));
-        if (lang_feed) {
-            rc = enqueue_prompt_feed(ctx, prompt, np, b0, 1);
+    int32_t feed[64];  // the default prompt for all 8 rows: rides in the first block's reset
+    for (int b = 0; b < 8; ++b)
+        for (int i = 0; i < np; ++i) feed[b * np + i] = prompt[i];
+    do {
+        if (detect) {
+            rc = run_lang_detect(ctx);
             if (rc) return rc;
         }
-        int done_steps = 0;
-        while (done_steps < total_steps) {
-            int chunk = total_steps - done_steps;
-            if (early_stop && chunk > 32) chunk = 32;
-            if (Gh > 0) {  // two half-grid launches, rows [b0, b0 + B1) and [b0 + B1, b0 + B)
-                PersistArgs p0 = persist_args(ctx, b0, B1, Gh, np, np, suppress_eot, n_gen);
-                PersistArgs p1 = persist_args(ctx, b0 + B1, B - B1, Gh, np, np, suppress_eot, n_gen);
-                split_second(ctx, p1, B1, Gh);
-                if (lang_feed) p1.feed += (size_t)B1 * np;  // (its rows' own prompts; by default every row's is the same)
-                p0.nres = p1.nres;
-                p0.n_steps = p1.n_steps = chunk;
-                if (ctx->d_ptrace && done_steps == 0 && b0 == 0) p0.ptrace = ctx->d_ptrace;
-                HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-                HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-                HIPCHK(ctx, launch_dec_persist(ctx->stream, p0, Gh));
-                HIPCHK(ctx, launch_dec_persist(ctx->stream2, p1, Gh));
-                HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-                HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-                rc = p0.ptrace ? ptrace_dump(ctx, chunk) : 0;
-            } else if (G > 0) {  // persistent decoder: the chunk's steps in one launch
-                PersistArgs pa = persist_args(ctx, b0, B, G, np, np, suppress_eot, n_gen);
-                pa.n_steps = chunk;
-                if (ctx->d_ptrace && done_steps == 0 && b0 == 0) pa.ptrace = ctx->d_ptrace;
-                HIPCHK(ctx, launch_dec_persist(ctx->stream, pa, G));
-                if (pa.ptrace) rc = ptrace_dump(ctx, chunk);
-                else rc = 0;
-            } else {
-                rc = run_dec_steps(ctx, b0, B, np, np, suppress_eot, n_gen, done_steps, chunk);
+        for (int b0 = 0; b0 < Bt; b0 += 8) {
+            const DecRun run{RUN_GREEDY, b0, Bt - b0 < 8 ? Bt - b0 : 8, np, np, suppress_eot, n_gen};
+            const int B = run.B, total_steps = np + n_gen - 1;
+            const RunGrid gr = run_grid(ctx, run);
+            rc = reset_run(ctx, b0 == 0, gr.G, gr.Gh, detect, b0 == 0 && !lang_feed ? feed : nullptr, 8 * np);
+            if (rc) return rc;
+            if (lang_feed) {
+                rc = enqueue_prompt_feed(ctx, prompt, np, b0, 1);
+                if (rc) return rc;
             }
-            if (rc) return rc;
-            done_steps += chunk;
-            if (early_stop && done_steps < total_steps && done_steps >= np) {
-                // tokens generated so far: done_steps - np + 1 (last one still in amax)
-                const int have = done_steps - np;
-                std::vector<int32_t> tk((size_t)B * n_gen);
-                HIPCHK(ctx, hipMemcpyAsync(tk.data(), ctx->dtokens + (size_t)b0 * n_gen, tk.size() * 4,
-                                           hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                bool all = true;
-                for (int b = 0; b < B && all; ++b) {
-                    bool found = false;
-                    for (int i = 0; i < have; ++i)
-                        if (tk[(size_t)b * n_gen + i] == ctx->sp.eot) { found = true; break; }
-                    all = found;
+            int done_steps = 0;
+            while (done_steps < total_steps) {
+                int chunk = total_steps - done_steps;
+                if (early_stop && chunk > 32) chunk = 32;
+                rc = advance_run(ctx, run, gr, done_steps, chunk);
+                if (rc) return rc;
+                done_steps += chunk;
+                if (early_stop && done_steps < total_steps && done_steps >= np) {
+                    // tokens generated so far: done_steps - np + 1 (last one still in amax)
+                    const int have = done_steps - np;
+                    std::vector<int32_t> tk((size_t)B * n_gen);
+                    HIPCHK(ctx, hipMemcpyAsync(tk.data(), ctx->dtokens + (size_t)b0 * n_gen, tk.size() * 4,
+                                               hipMemcpyDeviceToHost, ctx->stream));
+                    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+                    bool all = true;
+                    for (int b = 0; b < B && all; ++b) {
+                        bool found = false;
+                        for (int i = 0; i < have; ++i)
+                            if (tk[(size_t)b * n_gen + i] == ctx->sp.eot) { found = true; break; }
+                        all = found;
+                    }
+                    if (all) break;
                 }
-                if (all) break;
             }
+            // record the last argmax (embed kernel in record-only mode; the
+            // persistent decoder records every token itself)
+            if (gr.G > 0) continue;
+            DecEmbedArgs em{};
+            em.te = ctx->te; em.pe = ctx->d_pe; em.x = ctx->dx; em.feed = ctx->dfeed; em.feed_len = np; em.feed_stride = np;
+            em.amax = ctx->damax; em.tokens_out = ctx->dtokens + (size_t)b0 * n_gen; em.out_stride = n_gen;
+            em.st = ctx->dstate; em.n = ctx->hp.n_text_state; em.B = B; em.record_only = 1;
+            HIPCHK(ctx, launch_dec_embed(ctx->stream, em));
         }
-        // record the last argmax (embed kernel in record-only mode; the
-        // persistent decoder records every token itself)
-        if (G > 0) continue;
-        DecEmbedArgs em{};
-        em.te = ctx->te; em.pe = ctx->d_pe; em.x = ctx->dx; em.feed = ctx->dfeed; em.feed_len = np; em.feed_stride = np;
-        em.amax = ctx->damax; em.tokens_out = ctx->dtokens + (size_t)b0 * n_gen; em.out_stride = n_gen;
-        em.st = ctx->dstate; em.n = ctx->hp.n_text_state; em.B = B; em.record_only = 1;
-        HIPCHK(ctx, launch_dec_embed(ctx->stream, em));
-    }
-    {
-        uint32_t err = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&err, ctx->derr, 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (persist_fallback(ctx, err)) return run_greedy(ctx, n_gen, suppress_eot, early_stop, host_tokens, host_counts);
-        if (err) return dec_err(ctx, err);
-    }
+        rc = finish_run(ctx);
+    } while (rc == RERUN_ON_CHAIN);
+    if (rc) return rc;
     if (host_tokens) {
         HIPCHK(ctx, hipMemcpyAsync(host_tokens->data(), ctx->dtokens, host_tokens->size() * 4, hipMemcpyDeviceToHost,
                                    ctx->stream));
@@ -2022,8 +2086,6 @@ int run_greedy(wmi_context *ctx, int n_gen, int suppress_eot, bool early_stop, s
 bool valid(const wmi_context *ctx) { return ctx != nullptr && ctx->d_model != nullptr; }
 
 
-// beam search (config C5) of every encoded clip, one clip (K decoder rows) at
-// a time; per-clip best hypothesis (tokens, score) on the host
 // Timestamp decoding of encoded clip `clip` after `prompt` (whisper.cpp-1.0.3
 // whisper_full inner loop): up to max_tokens sampled
 // with the device timestamp sampler (k_ts_sample), stopping after EOT.
@@ -2043,57 +2105,33 @@ int run_ts_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt
     int rc = ensure_decode_buffers(ctx, np, 1);
     if (rc) return rc;
     ctx->ts_prompt = prompt;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dfeed, prompt.data(), (size_t)np * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->dstate, 0, sizeof(DecState), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->damax, 0, 8 * AMAX_SHARDS * 8, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->dsync, 0, ctx->sync_bytes, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->derr, 0, 4, ctx->stream));
-    ctx->ts_mode = true;
-    struct Reset { wmi_context *c; ~Reset() { c->ts_mode = false; } } reset{ctx};
+    const DecRun run{RUN_TS, clip, 1, np, np};
     const int total = np + max_tokens - 1;
     std::vector<TsRec> rec((size_t)max_tokens);
-    int n_out = max_tokens;
-    const int G = persist_grid_for(ctx, 1);
-    if (G > 0) HIPCHK(ctx, hipMemsetAsync(ctx->d_xg, 0, ctx->xg_bytes, ctx->stream));
-    for (int done = 0; done < total;) {
-        const int chunk = std::min(16, total - done);
-        if (G > 0) {
-            // persistent decoder, one step per launch (logits stored, no token
-            // recorded), then the timestamp sampler picks the next token into
-            // dts_tok, which the next launch feeds (cur_tok)
-            for (int i = 0; i < chunk; ++i) {
-                PersistArgs pa = persist_args(ctx, clip, 1, G, np, np, 0, 1);
-                pa.n_steps = 1;
-                pa.out_stride = 0;
-                pa.logits_out = ctx->dlogits;
-                pa.lg_stride = 0;
-                pa.cur_tok = ctx->dts_tok;
-                HIPCHK(ctx, launch_dec_persist(ctx->stream, pa, G));
-                TsArgs ta{};
-                ta.logits = ctx->dlogits; ta.V = hp.n_vocab; ta.beg = ctx->sp.beg; ta.eot = ctx->sp.eot;
-                ta.sot = ctx->sp.sot; ta.solm = ctx->sp.solm; ta.not_ = ctx->sp.not_; ta.feed_len = np;
-                ta.max_rec = hp.n_text_ctx; ta.st = ctx->dstate; ta.tok_out = ctx->dts_tok; ta.rec = ctx->dts_rec;
-                HIPCHK(ctx, launch_ts_sample(ctx->stream, ta));
-            }
-        } else {
-            rc = run_dec_steps(ctx, clip, 1, np, np, 0, 1, done, chunk);
+    int n_out;
+    do {
+        n_out = max_tokens;
+        const RunGrid gr = run_grid(ctx, run);
+        rc = reset_run(ctx, true, gr.G, gr.Gh, false, prompt.data(), np);
+        if (rc) return rc;
+        for (int done = 0; done < total;) {
+            const int chunk = std::min(16, total - done);
+            rc = advance_run(ctx, run, gr, done, chunk);
             if (rc) return rc;
+            done += chunk;
+            const int have = done - np + 1;  // records written so far
+            if (have <= 0) continue;
+            HIPCHK(ctx, hipMemcpyAsync(rec.data(), ctx->dts_rec, (size_t)have * sizeof(TsRec), hipMemcpyDeviceToHost,
+                                       ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            bool eot = false;
+            for (int i = 0; i < have && !eot; ++i)
+                if (rec[i].id == ctx->sp.eot) { n_out = i + 1; eot = true; }
+            if (eot) break;
         }
-        done += chunk;
-        const int have = done - np + 1;  // records written so far
-        if (have <= 0) continue;
-        HIPCHK(ctx, hipMemcpyAsync(rec.data(), ctx->dts_rec, (size_t)have * sizeof(TsRec), hipMemcpyDeviceToHost,
-                                   ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        bool eot = false;
-        for (int i = 0; i < have && !eot; ++i)
-            if (rec[i].id == ctx->sp.eot) { n_out = i + 1; eot = true; }
-        if (eot) break;
-    }
-    uint32_t err = 0;
-    HIPCHK(ctx, hipMemcpy(&err, ctx->derr, 4, hipMemcpyDeviceToHost));
-    if (persist_fallback(ctx, err)) return run_ts_window(ctx, clip, prompt, max_tokens, out);
-    if (err) return dec_err(ctx, err);
+        rc = finish_run(ctx);
+    } while (rc == RERUN_ON_CHAIN);
+    if (rc) return rc;
     out->assign(rec.begin(), rec.begin() + n_out);
     return WMI_OK;
 }
@@ -2197,6 +2235,8 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
     return WMI_OK;
 }
 
+// beam search (config C5) of every encoded clip, one clip (K decoder rows) at
+// a time; per-clip best hypothesis (tokens, score) on the host
 int run_beam(wmi_context *ctx, int K, int n_gen, int suppress_eot, bool early_stop,
              std::vector<std::vector<int32_t>> *out_tokens, std::vector<double> *out_scores) {
     const int Bt = ctx->enc_clips;
@@ -2213,126 +2253,93 @@ int run_beam(wmi_context *ctx, int K, int n_gen, int suppress_eot, bool early_st
     // (a language or task other than the default: as in run_greedy, with the
     // K prompt rows written per clip)
     const bool lang_feed = !ctx->lang_default, detect = lang_feed && ctx->lang_any_auto;
-    if (!lang_feed) {
-        std::vector<int32_t> feed(8 * np);
-        for (int b = 0; b < 8; ++b)
-            for (int i = 0; i < np; ++i) feed[b * np + i] = prompt[i];
-        HIPCHK(ctx, hipMemcpy(ctx->dfeed, feed.data(), feed.size() * 4, hipMemcpyHostToDevice));
-    } else if (detect) {
-        rc = run_lang_detect(ctx);
-        if (rc) return rc;
-    }
+    int32_t feed[64];
+    for (int b = 0; b < 8; ++b)
+        for (int i = 0; i < np; ++i) feed[b * np + i] = prompt[i];
     BeamState init{};
     init.n_active = 1;
     if (out_tokens) out_tokens->assign(Bt, {});
     if (out_scores) out_scores->assign(Bt, 0.0);
-    ctx->beam_k = K;
-    ctx->beam_max_tokens = n_gen;
-    struct Reset { wmi_context *c; ~Reset() { c->beam_k = 0; } } reset{ctx};
-    if (!detect) HIPCHK(ctx, hipMemsetAsync(ctx->derr, 0, 4, ctx->stream));  // (run_lang_detect zeroed it)
-    for (int clip = 0; clip < Bt; ++clip) {
-        if (lang_feed) {
-            rc = enqueue_prompt_feed(ctx, prompt, np, clip, 0);
+    do {
+        if (detect) {
+            rc = run_lang_detect(ctx);
             if (rc) return rc;
         }
-        HIPCHK(ctx, hipMemsetAsync(ctx->dstate, 0, sizeof(DecState), ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(ctx->dsync, 0, ctx->sync_bytes, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->dbstate, &init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->dkvsrc, ctx->kvsrc_init.data(), ctx->kvsrc_init.size() * 4,
-                                   hipMemcpyHostToDevice, ctx->stream));
-        const int total_steps = np + n_gen - 1;
-        const int G = persist_grid_for(ctx, K);
-        if (G > 0) HIPCHK(ctx, hipMemsetAsync(ctx->d_xg, 0, ctx->xg_bytes, ctx->stream));
-        int done_steps = 0;
-        while (done_steps < total_steps) {
-            int chunk = total_steps - done_steps;
-            if (early_stop && chunk > 32) chunk = 32;
-            if (G > 0) {
-                // persistent decoder, one step per launch (K rows = the beam
-                // slots of this clip), then the beam kernels select
-                for (int i = 0; i < chunk; ++i) {
-                    PersistArgs pa = persist_args(ctx, clip, K, G, np, np, suppress_eot, 1);
-                    pa.n_steps = 1;
-                    pa.beam = 1;
-                    pa.cur_tok = ctx->dbstate->tok;
-                    pa.kv_src = ctx->dkvsrc;
-                    pa.kv_src_stride = hp.n_text_ctx;
-                    pa.logits_out = ctx->dlogits;  // (the beam kernels read this step's [K][V])
-                    pa.lg_stride = 0;
-                    pa.tokens_out = ctx->dtokens;  // (unused: no argmax in beam mode)
-                    // WMI_PTRACE: step s of clip 0 stamps slot s (its phase A
-                    // then includes the launch gap and the beam kernels)
-                    const int s_all = done_steps + i;
-                    if (ctx->d_ptrace && clip == 0 && s_all < hp.n_text_ctx)
-                        pa.ptrace = ctx->d_ptrace + (size_t)s_all * (hp.n_text_layer + 1) * 32 * 2;
-                    HIPCHK(ctx, launch_dec_persist(ctx->stream, pa, G));
-                    if (ctx->d_lgall && s_all < hp.n_text_ctx)  // WMI_LOGITS_ALL: this step's [K][V]
-                        HIPCHK(ctx, hipMemcpyAsync(ctx->d_lgall + (size_t)s_all * ctx->lg_rows * hp.n_vocab,
-                                                   ctx->dlogits, (size_t)K * hp.n_vocab * 4,
-                                                   hipMemcpyDeviceToDevice, ctx->stream));
-                    HIPCHK(ctx, launch_beam_step(ctx->stream, beam_args(ctx, np, suppress_eot)));
+        for (int clip = 0; clip < Bt; ++clip) {
+            const DecRun run{RUN_BEAM, clip, K, np, np, suppress_eot, 1, K, n_gen};
+            const RunGrid gr = run_grid(ctx, run);
+            rc = reset_run(ctx, clip == 0, gr.G, gr.Gh, detect, clip == 0 && !lang_feed ? feed : nullptr, 8 * np);
+            if (rc) return rc;
+            if (lang_feed) {
+                rc = enqueue_prompt_feed(ctx, prompt, np, clip, 0);
+                if (rc) return rc;
+            }
+            HIPCHK(ctx, hipMemcpyAsync(ctx->dbstate, &init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->dkvsrc, ctx->kvsrc_init.data(), ctx->kvsrc_init.size() * 4,
+                                       hipMemcpyHostToDevice, ctx->stream));
+            const int total_steps = np + n_gen - 1;
+            int done_steps = 0;
+            while (done_steps < total_steps) {
+                int chunk = total_steps - done_steps;
+                if (early_stop && chunk > 32) chunk = 32;
+                rc = advance_run(ctx, run, gr, done_steps, chunk);
+                if (rc) return rc;
+                done_steps += chunk;
+                if (gr.G > 0 && ctx->d_ptrace && clip == 0 && done_steps >= total_steps) {
+                    rc = ptrace_dump(ctx, std::min(total_steps, hp.n_text_ctx));
+                    if (rc) return rc;
                 }
+                if (early_stop && done_steps < total_steps) {
+                    int32_t done = 0;
+                    HIPCHK(ctx, hipMemcpyAsync(&done, &ctx->dbstate->done, 4, hipMemcpyDeviceToHost, ctx->stream));
+                    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+                    if (done) break;
+                }
+            }
+            BeamState bs{};
+            HIPCHK(ctx, hipMemcpyAsync(&bs, ctx->dbstate, sizeof bs, hipMemcpyDeviceToHost, ctx->stream));
+            rc = finish_run(ctx);
+            if (rc == RERUN_ON_CHAIN) break;  // (every clip again, on the kernel chain)
+            if (rc) return rc;
+            const int ns = bs.n_steps;
+            if (ns < 1) return set_err(ctx, WMI_E_HIP, "beam search produced no step");
+            std::vector<int32_t> hpar((size_t)ns * BEAM_MAX), htok((size_t)ns * BEAM_MAX);
+            HIPCHK(ctx, hipMemcpy(hpar.data(), ctx->dhist_par, hpar.size() * 4, hipMemcpyDeviceToHost));
+            HIPCHK(ctx, hipMemcpy(htok.data(), ctx->dhist_tok, htok.size() * 4, hipMemcpyDeviceToHost));
+            auto backtrack = [&](int tlast, int slot) {
+                std::vector<int32_t> seq(tlast + 1);
+                for (int t = tlast; t >= 0; --t) {
+                    seq[t] = htok[(size_t)t * BEAM_MAX + slot];
+                    slot = hpar[(size_t)t * BEAM_MAX + slot];
+                }
+                return seq;
+            };
+            // finished hypotheses in order, then active ones in slot order, first K
+            double best = -INFINITY;
+            int best_src = -1, best_i = 0, considered = 0;
+            for (int f = 0; f < bs.n_fin && considered < K; ++f, ++considered) {
+                const double sc = bs.fin_score[f] / (double)(bs.fin_t[f] > 0 ? bs.fin_t[f] : 1);
+                if (sc > best) { best = sc; best_src = 0; best_i = f; }
+            }
+            for (int a = 0; a < bs.n_active && considered < K; ++a, ++considered) {
+                const double sc = bs.score[a] / (double)ns;
+                if (sc > best) { best = sc; best_src = 1; best_i = a; }
+            }
+            std::vector<int32_t> seq;
+            double score;
+            if (best_src == 0) {
+                const int t = bs.fin_t[best_i];
+                if (t > 0) seq = backtrack(t - 1, bs.fin_beam[best_i]);
+                seq.push_back(ctx->sp.eot);
+                score = bs.fin_score[best_i];
             } else {
-                rc = run_dec_steps(ctx, clip, K, np, np, suppress_eot, 1, done_steps, chunk);
-                if (rc) return rc;
+                seq = backtrack(ns - 1, best_i);
+                score = bs.score[best_i];
             }
-            done_steps += chunk;
-            if (G > 0 && ctx->d_ptrace && clip == 0 && done_steps >= total_steps) {
-                rc = ptrace_dump(ctx, std::min(total_steps, hp.n_text_ctx));
-                if (rc) return rc;
-            }
-            if (early_stop && done_steps < total_steps) {
-                int32_t done = 0;
-                HIPCHK(ctx, hipMemcpyAsync(&done, &ctx->dbstate->done, 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                if (done) break;
-            }
+            if (out_tokens) (*out_tokens)[clip] = seq;
+            if (out_scores) (*out_scores)[clip] = score;
         }
-        BeamState bs{};
-        uint32_t err = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&bs, ctx->dbstate, sizeof bs, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(&err, ctx->derr, 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (persist_fallback(ctx, err)) return run_beam(ctx, K, n_gen, suppress_eot, early_stop, out_tokens, out_scores);
-        if (err) return dec_err(ctx, err);
-        const int ns = bs.n_steps;
-        if (ns < 1) return set_err(ctx, WMI_E_HIP, "beam search produced no step");
-        std::vector<int32_t> hpar((size_t)ns * BEAM_MAX), htok((size_t)ns * BEAM_MAX);
-        HIPCHK(ctx, hipMemcpy(hpar.data(), ctx->dhist_par, hpar.size() * 4, hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(htok.data(), ctx->dhist_tok, htok.size() * 4, hipMemcpyDeviceToHost));
-        auto backtrack = [&](int tlast, int slot) {
-            std::vector<int32_t> seq(tlast + 1);
-            for (int t = tlast; t >= 0; --t) {
-                seq[t] = htok[(size_t)t * BEAM_MAX + slot];
-                slot = hpar[(size_t)t * BEAM_MAX + slot];
-            }
-            return seq;
-        };
-        // finished hypotheses in order, then active ones in slot order, first K
-        double best = -INFINITY;
-        int best_src = -1, best_i = 0, considered = 0;
-        for (int f = 0; f < bs.n_fin && considered < K; ++f, ++considered) {
-            const double sc = bs.fin_score[f] / (double)(bs.fin_t[f] > 0 ? bs.fin_t[f] : 1);
-            if (sc > best) { best = sc; best_src = 0; best_i = f; }
-        }
-        for (int a = 0; a < bs.n_active && considered < K; ++a, ++considered) {
-            const double sc = bs.score[a] / (double)ns;
-            if (sc > best) { best = sc; best_src = 1; best_i = a; }
-        }
-        std::vector<int32_t> seq;
-        double score;
-        if (best_src == 0) {
-            const int t = bs.fin_t[best_i];
-            if (t > 0) seq = backtrack(t - 1, bs.fin_beam[best_i]);
-            seq.push_back(ctx->sp.eot);
-            score = bs.fin_score[best_i];
-        } else {
-            seq = backtrack(ns - 1, best_i);
-            score = bs.score[best_i];
-        }
-        if (out_tokens) (*out_tokens)[clip] = seq;
-        if (out_scores) (*out_scores)[clip] = score;
-    }
+    } while (rc == RERUN_ON_CHAIN);
     return record_lang_used(ctx);
 }
 
@@ -2793,34 +2800,20 @@ static int wmi_decode_logits_impl(wmi_context *ctx, int clip, const int32_t *tok
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc = ensure_decode_buffers(ctx, n_tokens, 1);
     if (rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dfeed, tokens, (size_t)n_tokens * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->dstate, 0, sizeof(DecState), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->damax, 0, 8 * AMAX_SHARDS * 8, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->dsync, 0, ctx->sync_bytes, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->derr, 0, 4, ctx->stream));
     const size_t V = ctx->hp.n_vocab;
-    const int G = persist_grid_for(ctx, 1);
-    if (G > 0) HIPCHK(ctx, hipMemsetAsync(ctx->d_xg, 0, ctx->xg_bytes, ctx->stream));
-    for (int i = 0; i < n_tokens; ++i) {
-        if (G > 0) {  // persistent decoder, one step per launch, logits stored
-            PersistArgs pa = persist_args(ctx, clip, 1, G, n_tokens, n_tokens, 0, 1);
-            pa.n_steps = 1;
-            pa.logits_out = ctx->dlogits;
-            pa.lg_stride = 0;
-            pa.out_stride = 0;  // teacher forcing: record no token (dtokens holds staged results)
-            HIPCHK(ctx, launch_dec_persist(ctx->stream, pa, G));
-        } else {
-            rc = run_dec_steps(ctx, clip, 1, n_tokens, n_tokens, 0, 1, i, 1);
+    const DecRun run{RUN_FORCED, clip, 1, n_tokens, n_tokens};
+    do {
+        const RunGrid gr = run_grid(ctx, run);
+        rc = reset_run(ctx, true, gr.G, gr.Gh, false, tokens, n_tokens);
+        if (rc) return rc;
+        for (int i = 0; i < n_tokens; ++i) {
+            rc = advance_run(ctx, run, gr, i, 1);
             if (rc) return rc;
+            HIPCHK(ctx, hipMemcpyAsync(logits + (size_t)i * V, ctx->dlogits, V * 4, hipMemcpyDeviceToHost, ctx->stream));
         }
-        HIPCHK(ctx, hipMemcpyAsync(logits + (size_t)i * V, ctx->dlogits, V * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    uint32_t err = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&err, ctx->derr, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (persist_fallback(ctx, err)) return wmi_decode_logits_impl(ctx, clip, tokens, n_tokens, logits);
-    if (err) return dec_err(ctx, err);
-    return WMI_OK;
+        rc = finish_run(ctx);
+    } while (rc == RERUN_ON_CHAIN);
+    return rc;
 }
 
 static int wmi_decode_beam_impl(wmi_context *ctx, int beam_size, int max_tokens, int suppress_eot, int32_t *tokens,
@@ -3093,9 +3086,9 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
         case 7: src = ctx->vcache; have = (size_t)ctx->hp.n_text_layer * R * ctx->hp.n_text_ctx * n * 2; break;
         case 8: src = ctx->dS; have = R * (size_t)ctx->hp.n_text_head * ctx->s_stride * 4; break;
         case 9: src = ctx->dopart; have = R * (size_t)ctx->n_chunks_max * n * 4; break;
-        case 10: {  // host: this context's tuning knobs (struct Tune, int32 fields in order)
+        case 10: {  // host: this context's tuning knobs (slots 1, 2: two knobs since fixed at these values)
             const Tune &t = ctx->tune;
-            const int32_t v[11] = {t.logits_cap, t.logits_g, t.gemv_nw, t.xattn_rows, t.graph_steps,
+            const int32_t v[11] = {t.logits_cap, 2, 4, t.xattn_rows, t.graph_steps,
                                    t.enc_attn_nw, t.gemm_g, t.mel_g, t.epi_staged, t.gemm_p, t.gelu_calc};
             memcpy(out, v, std::min(sizeof v, bytes));
             return WMI_OK;

@@ -72,8 +72,6 @@ enum GemmEpi {
 // context's copy; a null pointer means the defaults below.
 struct Tune {
     int logits_cap = 512;   // WMI_LOGITS_CAP: chain logits grid cap
-    int logits_g = 2;       // (fixed) chain logits rows per lane group
-    int gemv_nw = 4;        // (fixed) waves per chain decoder GEMV workgroup
     int xattn_rows = 1;     // WMI_XATTN_ROWS: beam rows share cross-attention phase A (1 auto, 2 always, 0 never)
     int graph_steps = 8;    // WMI_GRAPH_STEPS: chain decoder steps per captured graph
     int enc_attn_nw = 0;    // WMI_ENC_ATTN_NW: 32-query blocks (four key-part waves each) per k_attn_enc4 workgroup (0 auto, 1, 2, 4)

@@ -1915,14 +1915,13 @@ __global__ __launch_bounds__(64 * NW) void k_dec_gemv(DecGemvArgs a) {
     }
 }
 
-// waves per workgroup of the per-layer GEMVs (Tune::gemv_nw, fixed at 4: one
-// wave per workgroup measured mlp0 4.6 -> 10 us at base, B = 1, every
-// workgroup repeating the LayerNorm); row groups per register set of the
-// vocabulary GEMV at K <= 512 (Tune::logits_g, fixed at 2: base 13.9 us at
-// G = 1 -> 12.1 us at G = 2 over 1024 workgroups)
-
-template <int EPI, int IN, int WQ, int NW>
-static hipError_t dec_gemv_nw(hipStream_t s, const DecGemvArgs &a) {
+// four waves per workgroup (one wave per workgroup measured mlp0 4.6 -> 10 us
+// at base, B = 1, every workgroup repeating the LayerNorm); two row groups per
+// register set of the vocabulary GEMV at K <= 512 (base 13.9 us at G = 1 ->
+// 12.1 us at G = 2 over 1024 workgroups)
+template <int EPI, int IN, int WQ>
+static hipError_t dec_gemv_g(hipStream_t s, const DecGemvArgs &a) {
+    constexpr int NW = 4;
     const size_t lds = (size_t)a.B * a.K * 2;
     dim3 block(64 * NW);
     // the vocabulary GEMV runs persistent and pipelined (its K = n_state <=
@@ -1941,41 +1940,22 @@ static hipError_t dec_gemv_nw(hipStream_t s, const DecGemvArgs &a) {
         hipError_t e = allow_lds(k_dec_gemv<EPI, IN, 1, 16, 0, NW>, lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((k_dec_gemv<EPI, IN, 1, 16, 0, NW>), grid, block, lds, s, a);
-    } else if (EPI == DEC_LOGITS && a.K <= 512 && tn.logits_g > 1) {
-        // K <= 512: 4 chunks cover a row, so each register set can hold G = 2
-        // or 4 row groups (more bytes in flight per wave at the same VGPRs)
+    } else if (EPI == DEC_LOGITS && a.K <= 512) {
+        // K <= 512: 4 chunks cover a row, so each register set holds G = 2
+        // row groups (more bytes in flight per wave at the same VGPRs)
         // (128 VGPRs at G = 2: four workgroups per CU, hence the larger cap;
         // a balanced grid of equal row-group counts measured slower)
-        const int G = tn.logits_g == 2 ? 2 : 4, ng = cdiv(a.N, 4 * NW * G);
+        const int ng = cdiv(a.N, 4 * NW * 2);
         const dim3 grid2(ng < CHAIN_LOGITS_CAP2 ? ng : CHAIN_LOGITS_CAP2);
-        if (G == 2) {
-            hipError_t e = allow_lds(k_dec_gemv<EPI, IN, 2, 4, 0, NW>, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_dec_gemv<EPI, IN, 2, 4, 0, NW>), grid2, block, lds, s, a);
-        } else {
-            hipError_t e = allow_lds(k_dec_gemv<EPI, IN, 4, 4, 0, NW>, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_dec_gemv<EPI, IN, 4, 4, 0, NW>), grid2, block, lds, s, a);
-        }
+        hipError_t e = allow_lds(k_dec_gemv<EPI, IN, 2, 4, 0, NW>, lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((k_dec_gemv<EPI, IN, 2, 4, 0, NW>), grid2, block, lds, s, a);
     } else {
         hipError_t e = allow_lds(k_dec_gemv<EPI, IN, 1, 8, 0, NW>, lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((k_dec_gemv<EPI, IN, 1, 8, 0, NW>), grid, block, lds, s, a);
     }
     return hipGetLastError();
-}
-
-template <int EPI, int IN, int WQ>
-static hipError_t dec_gemv_g(hipStream_t s, const DecGemvArgs &a) {
-    // one wave per workgroup spreads a per-layer GEMV over 4x the CUs; with
-    // more rows each wave would normalise B / NW LayerNorm rows serially
-    if constexpr (EPI == DEC_LOGITS) {
-        return dec_gemv_nw<EPI, IN, WQ, 4>(s, a);
-    } else {
-        const Tune &tn = tune_of(a.tune);
-        const bool one = tn.gemv_nw == 1 || (tn.gemv_nw == 0 && a.B <= 2);
-        return one ? dec_gemv_nw<EPI, IN, WQ, 1>(s, a) : dec_gemv_nw<EPI, IN, WQ, 4>(s, a);
-    }
 }
 
 template <int EPI, int IN>
