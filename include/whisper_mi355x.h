@@ -89,7 +89,11 @@ typedef struct wmi_context wmi_context;
  * filters, vocab (+extra tokens), weights; then upload to `device`.
  * max_clips sizes the device workspace for batched calls (>= 1).  Weight
  * types: f16 and f32 files (hparams.f16 = 1 / 0, main.rs:817-821; f32
- * matrices are kept f32 on the device) and the ggml quantised types. */
+ * matrices are kept f32 on the device) and the ggml quantised types.
+ * Shapes: n_text_state == n_audio_state, a multiple of 128 up to 1280 with
+ * 64-wide heads, n_text_ctx <= 512, any depths and n_audio_ctx; anything
+ * else is WMI_E_UNSUPPORTED as soon as the header is parsed (before a tensor
+ * is read or the device touched). */
 int wmi_init_from_file(const char *path, int device, int max_clips, wmi_context **out);
 void wmi_free(wmi_context *ctx);
 const char *wmi_strerror(int status);
@@ -291,8 +295,9 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * WMI_* environment is read once per context at wmi_init_from_file),
  * 11 = decodes re-run on the kernel chain (int32, host), 12 = the encoder
  * residual stream, 13 = every position's logits [n_text_ctx][rows][n_vocab]
- * f32 of the last persistent greedy decode (clip b in row b) or beam search
- * (slot s in row s; contexts created with WMI_LOGITS_ALL=1), 14 / 15 = the
+ * f32 of the last greedy decode (clip b in row b) or beam search (slot s in
+ * row s), on the persistent decoder or the kernel chain (contexts created
+ * with WMI_LOGITS_ALL=1), 14 / 15 = the
  * last beam search's parent slots / tokens [n_text_ctx][8] int32 (its last
  * clip), 16 = the rows of 13 (int32, host: max(8, max_clips)), 17 = the
  * persistent decoder's grid per row count (int32 [9], host; -1 = not sized

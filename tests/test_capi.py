@@ -207,3 +207,45 @@ def test_decode_alg_bytes_counts_q5_blocks():
     assert g5 - b5 == pytest.approx(steps * 4 * L * T * n * 4, rel=1e-12)  # 4 more clips' cross K/V
     with pytest.raises(wmi.InvalidArgument):
         wmi.decode_alg_bytes(hp, 0, steps)
+
+
+HP_OFF = {k: 4 + 4 * i for i, k in enumerate(synth.HPARAM_ORDER)}  # byte offset of each header field
+
+REJECTED_SHAPES = {
+    "n_state_1408": dict(n_audio_state=1408, n_text_state=1408, n_audio_head=22, n_text_head=22),
+    "n_state_192_3_heads": dict(n_audio_state=192, n_text_state=192, n_audio_head=3, n_text_head=3),
+    "n_state_128_4_heads": dict(n_audio_head=4, n_text_head=4),
+    "n_text_state_256_vs_128": dict(n_text_state=256, n_text_head=4),
+    "n_text_ctx_576": dict(n_text_ctx=576),
+}
+
+
+@pytest.mark.parametrize("case", sorted(REJECTED_SHAPES))
+def test_unsupported_shapes_rejected_at_load(tmp_path, micro_model, case):
+    """The shapes the kernels do not implement (n_text_state != n_audio_state,
+    n_text_ctx > 512, a width that is no multiple of 128 or above 1280, a head
+    dim other than 64) are refused when the header is parsed — Unsupported
+    from WhisperContext.new, before a tensor is read or a device touched —
+    not at the first encode: a micro file with only its header fields
+    rewritten, and the same header with every tensor record cut off."""
+    data = bytearray(open(micro_model, "rb").read())
+    for k, v in REJECTED_SHAPES[case].items():
+        data[HP_OFF[k]:HP_OFF[k] + 4] = struct.pack("<i", v)
+    off = 48
+    n_mel, n_ff = struct.unpack("<ii", data[off:off + 8])
+    off += 8 + 4 * n_mel * n_ff
+    (n_tok,) = struct.unpack("<i", data[off:off + 4])
+    off += 4
+    for _ in range(n_tok):
+        off += 4 + struct.unpack("<I", data[off:off + 4])[0]
+    for name, blob in (("full.bin", data), ("header.bin", data[:off])):
+        path = os.path.join(str(tmp_path), name)
+        open(path, "wb").write(blob)
+        with pytest.raises(wmi.Unsupported) as ei:
+            wmi.WhisperContext.new(path)
+        assert ei.value.code == 13
+    # the unchanged header with the records cut off gets past the shape checks
+    ok = os.path.join(str(tmp_path), "ok-header.bin")
+    open(ok, "wb").write(open(micro_model, "rb").read()[:off])
+    with pytest.raises(wmi.UnexpectIO):
+        wmi.WhisperContext.new(ok)

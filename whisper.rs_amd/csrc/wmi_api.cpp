@@ -435,6 +435,23 @@ void dequant_f16(int t, const uint8_t *src, int64_t nel, uint16_t *dst) {
     }
 }
 
+// The model shapes the kernels implement; anything else is WMI_E_UNSUPPORTED.
+// Checked right after the header is parsed (before tensors are read and the
+// device is touched) and again by run_encode.
+int check_shape(const wmi_hparams &hp, std::string &err) {
+    char msg[128];
+    const int n = hp.n_audio_state, H = hp.n_audio_head;
+    msg[0] = 0;
+    if (hp.n_text_state != n) snprintf(msg, sizeof msg, "n_text_state != n_audio_state");
+    else if (hp.n_text_ctx > 512) snprintf(msg, sizeof msg, "n_text_ctx %d > 512", hp.n_text_ctx);
+    else if (n > 1280 || n % 128) snprintf(msg, sizeof msg, "n_state %d (need a multiple of 128, <= 1280)", n);
+    else if (n / H != 64 || hp.n_text_state / hp.n_text_head != 64)
+        snprintf(msg, sizeof msg, "head dim %d != 64", n / H != 64 ? n / H : hp.n_text_state / hp.n_text_head);
+    if (!msg[0]) return WMI_OK;
+    err = msg;
+    return WMI_E_UNSUPPORTED;
+}
+
 int parse_file(const char *path, ParsedModel &pm, std::string &err) {
     FILE *f = fopen(path, "rb");
     if (!f) { err = std::string("Unexpected IO: cannot open '") + path + "'"; return WMI_E_IO; }
@@ -465,6 +482,7 @@ int parse_file(const char *path, ParsedModel &pm, std::string &err) {
         err = "Unexpected: state not divisible by heads";
         return WMI_E_UNEXPECTED;
     }
+    if (int rc = check_shape(hp, err)) return rc;
     // filters (main.rs:513-535)
     if (!rd(&pm.n_filt_mel, 4) || !rd(&pm.n_filt_ff, 4)) { err = "Unexpected IO: short read (filters)"; return WMI_E_IO; }
     if (pm.n_filt_mel <= 0 || pm.n_filt_ff <= 0 || (int64_t)pm.n_filt_mel * pm.n_filt_ff > (1 << 24) ||
@@ -1224,10 +1242,10 @@ int run_encode(wmi_context *ctx, int mel_offset) {
     const int n = hp.n_audio_state, H = hp.n_audio_head, nt = hp.n_text_state;
     if (B < 1) return set_err(ctx, WMI_E_INVALID_ARG, "encode before pcm_to_mel");
     if (mel_offset < 0) return set_err(ctx, WMI_E_INVALID_ARG, "negative mel_offset");
-    if (nt != n) return set_err(ctx, WMI_E_UNSUPPORTED, "n_text_state != n_audio_state");
-    if (hp.n_text_ctx > 512) return set_err(ctx, WMI_E_UNSUPPORTED, "n_text_ctx %d > 512", hp.n_text_ctx);
-    if (n > 1280 || n % 128) return set_err(ctx, WMI_E_UNSUPPORTED, "n_state %d (need a multiple of 128, <= 1280)", n);
-    if (n / H != 64) return set_err(ctx, WMI_E_UNSUPPORTED, "head dim %d != 64", n / H);
+    {
+        std::string why;
+        if (int rc = check_shape(hp, why)) return set_err(ctx, rc, "%s", why.c_str());
+    }
     hipStream_t s = ctx->stream;
     if (ctx->layout_T != T) {
         const size_t qkv_bytes = (size_t)ctx->max_clips * H * up(hp.n_audio_ctx, 64) * 64 * 2;
@@ -1502,6 +1520,12 @@ int enqueue_dec_step(wmi_context *ctx, const DecRun &run) {
     g.st_advance = ctx->dstate;
     if (beam || ts) g.amax = nullptr;
     HIPCHK(ctx, launch_dec_gemv(s, DEC_LOGITS, g));
+    // WMI_LOGITS_ALL: what the persistent launches keep — a greedy run's rows
+    // b0.., a beam step's [K][V] — so a debug read 13 of a chain decode holds
+    // the decode's logits, not the buffer's zeros
+    if (ctx->d_lgall && (run.kind == RUN_GREEDY || beam) && (beam ? 0 : b0) + B <= ctx->lg_rows)
+        HIPCHK(ctx, launch_logits_capture(s, ctx->dlogits, ctx->d_lgall + (beam ? 0 : (size_t)b0 * hp.n_vocab), ctx->dstate,
+                                          B, hp.n_vocab, (int64_t)ctx->lg_rows * hp.n_vocab, hp.n_text_ctx));
     return enqueue_step_tail(ctx, run);
 }
 

@@ -282,6 +282,10 @@ struct TsArgs {
     TsRec *rec;              // [max_rec], record t = pos - feed_len
 };
 hipError_t launch_ts_sample(hipStream_t s, const TsArgs &a);
+// WMI_LOGITS_ALL on the kernel chain: logits [rows][V] -> all + (pos - 1) * slab
+// (after the step's logits GEMV; positions outside [0, tctx) are dropped)
+hipError_t launch_logits_capture(hipStream_t s, const float *logits, float *all, const DecState *st, int rows, int V,
+                                 int64_t slab, int tctx);
 
 // ---- language detection and per-clip prompts --------------------------------
 // (the language token of index i is sot + 1 + i; whisper.cpp's g_lang order)

@@ -2575,7 +2575,7 @@ hipError_t launch_dec_attn(hipStream_t s, const DecAttnArgs &a) {
         hipLaunchKernelGGL((k_dec_xattn_rows<KC>), g1, dim3(256), 0, s, a);      \
         break;
         switch (a.n / 128) {
-            XR(1) XR(2) XR(3) XR(4) XR(5) XR(6) XR(8) XR(10)
+            XR(1) XR(2) XR(3) XR(4) XR(5) XR(6) XR(7) XR(8) XR(9) XR(10)
             default: return hipErrorInvalidValue;
         }
 #undef XR
@@ -2590,13 +2590,33 @@ hipError_t launch_dec_attn(hipStream_t s, const DecAttnArgs &a) {
         else hipLaunchKernelGGL((k_dec_xattn<KC, 0>), grid, dim3(256), 0, s, a);               \
         break;
     switch (a.n / 128) {
-        XA(1) XA(2) XA(3) XA(4) XA(5) XA(6) XA(8) XA(10)
+        XA(1) XA(2) XA(3) XA(4) XA(5) XA(6) XA(7) XA(8) XA(9) XA(10)
         default: return hipErrorInvalidValue;
     }
 #undef XA
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || coop) return e;
     hipLaunchKernelGGL(k_dec_attn_pv, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// WMI_LOGITS_ALL on the kernel chain: the step's logits rows [rows][V] into
+// the slab of the position just processed (the logits GEMV advanced pos)
+__global__ __launch_bounds__(256) void k_logits_capture(const float *logits, float *all, const DecState *st, int rows,
+                                                        int V, int64_t slab, int tctx) {
+    const int p = st->pos - 1;
+    if (p < 0 || p >= tctx) return;
+    const int64_t n = (int64_t)rows * V;
+    float *dst = all + (int64_t)p * slab;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) dst[i] = logits[i];
+}
+
+hipError_t launch_logits_capture(hipStream_t s, const float *logits, float *all, const DecState *st, int rows, int V,
+                                 int64_t slab, int tctx) {
+    if (rows < 1 || V < 1 || slab < (int64_t)rows * V || tctx < 1) return hipErrorInvalidValue;
+    const int64_t nb = ((int64_t)rows * V + 255) / 256;
+    hipLaunchKernelGGL(k_logits_capture, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(256), 0, s, logits, all, st, rows, V,
+                       slab, tctx);
     return hipGetLastError();
 }
 
