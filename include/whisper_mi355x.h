@@ -235,6 +235,42 @@ int wmi_get_segment(const wmi_context *ctx, int i, int64_t *t0, int64_t *t1, cha
 /* Its tokens (text and timestamp tokens of the segment). */
 int wmi_get_segment_tokens(const wmi_context *ctx, int i, wmi_token_data *out, size_t cap, int32_t *n);
 
+/* no_context = 1: every window of wmi_transcribe decodes from the initial
+ * prompt [SOT (, language, task)] alone, without <|prev|> and the earlier
+ * text (whisper.cpp's no_context, OpenAI's condition_on_previous_text=False).
+ * Default 0.  Holds until changed. */
+int wmi_set_no_context(wmi_context *ctx, int no_context);
+
+/* ---- batched timestamped transcription -------------------------------- */
+
+/* wmi_decode_timestamps for every encoded clip at once: one window per clip
+ * after the one shared prompt, up to 8 clips per decoder step.  out is
+ * [n_clips][max_tokens]; n_out[c] counts clip c's tokens up to and including
+ * its EOT (nothing is written behind it).  A clip that has met EOT waits for
+ * the others of its block.  For one clip: what wmi_decode_timestamps returns. */
+int wmi_decode_timestamps_batch(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens,
+                                wmi_token_data *out, int32_t *n_out);
+/* wmi_transcribe over n_clips recordings (1 <= n_clips <= max_clips) of any,
+ * unequal lengths, up to 8 of them per decoder step: per round every active
+ * recording's next window is encoded at its own seek and the windows are
+ * decoded in lockstep; a recording that reached its end frees its row for a
+ * waiting one.  The rows of a step share the decoder position, so windows
+ * always decode without earlier text (as with wmi_set_no_context(1), whatever
+ * that setting is).  Recording c yields the segments wmi_transcribe gives for
+ * it alone with no-context on and the same language and task, whichever other
+ * recordings share the batch.  Language of clip c: wmi_set_language(c, ..);
+ * WMI_LANG_AUTO is detected on that recording's first window and kept
+ * (wmi_get_language(c)).  n_segments[n_clips]; read the segments with the
+ * _of getters below. */
+int wmi_transcribe_batch(wmi_context *ctx, int n_clips, const float *const *pcm, const size_t *n_samples, int max_tokens,
+                         int32_t *n_segments);
+/* wmi_get_segment / wmi_get_segment_tokens for recording `clip` of the last
+ * wmi_transcribe_batch (or clip 0 of the last wmi_transcribe); the getters
+ * without a clip read clip 0. */
+int wmi_get_segment_of(const wmi_context *ctx, int clip, int i, int64_t *t0, int64_t *t1, char *text, size_t cap,
+                       size_t *len);
+int wmi_get_segment_tokens_of(const wmi_context *ctx, int clip, int i, wmi_token_data *out, size_t cap, int32_t *n);
+
 /* ---- device-resident benchmark path --------------------------------- */
 
 /* Upload n_clips PCM clips to HBM once (untimed). */
@@ -305,7 +341,8 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * host: f16 inputs at or above it are computed, the rest read ggml's table;
  * +inf with WMI_GELU_CALC=0), 19 = the prompt of the last timestamp window
  * (wmi_transcribe / wmi_decode_timestamps; int32, host copy: the first
- * bytes / 4 tokens, entries past its length are -1). */
+ * bytes / 4 tokens, entries past its length are -1; a batched window's rows
+ * follow each other, [rows][n_prompt]). */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

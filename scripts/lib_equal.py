@@ -2,7 +2,8 @@
 on the encoder output and the persistent decoder: greedy ids and last-step
 logits of base (1 clip and 8 clips), micro and small; then micro's beam
 search, timestamp window, teacher-forced logits and language detection, so
-every kind of decode run is compared.  Usage: lib_equal.py LIB_A LIB_B (needs the GPU)."""
+every kind of decode run is compared; a 2-clip encode at a mel offset and
+wmi_transcribe over several windows.  Usage: lib_equal.py LIB_A LIB_B (needs the GPU)."""
 import os
 import subprocess
 import sys
@@ -53,6 +54,23 @@ def run_one(out):
     res["ts_ids"] = np.array([[t["id"], t["tid"]] for t in ts])
     res["ts_p"] = np.array([[t["p"], t["pt"], t["ptsum"]] for t in ts], np.float32)
     res["forced_lg"] = ctx.decode_logits((prompt + [sp["not"], 11, 23, 37, 41, 53])[:6], 1)
+    # the scalar-offset encode of a 2-clip batch away from frame 0, and
+    # wmi_transcribe with its default setting (earlier text as context) over
+    # several windows: on the segmenting fixture of tests/test_transcribe_batch.py
+    # if the model cache holds it (text segments), else on micro
+    ctx.encode(1, 37)
+    res["off_enc"] = np.stack([ctx.encoder_out(i) for i in range(2)])
+    for i in range(2):
+        res[f"off_ck{i}"], res[f"off_cv{i}"] = ctx.cross_kv(i)
+    ctx.close()
+    seg = os.path.join(os.environ["WMI_MODEL_CACHE"], "ggml-micro-tsbatch-A.bin")
+    ctx = wmi.WhisperContext.new(seg if os.path.exists(seg) else synth.model_path("micro"), 0, max_clips=1)
+    ctx.set_audio_ctx(64)
+    segs = ctx.transcribe(synth.synth_pcm_tones(4.0, 21), max_tokens=10)
+    res["tr_t"] = np.array([[s["t0"], s["t1"]] for s in segs], np.int64).reshape(-1, 2)
+    res["tr_ids"] = np.array([[t["id"], t["tid"]] for s in segs for t in s["tokens"]], np.int32).reshape(-1, 2)
+    res["tr_p"] = np.array([[t["p"], t["pt"], t["ptsum"]] for s in segs for t in s["tokens"]], np.float32).reshape(-1, 3)
+    res["tr_prompt"] = np.frombuffer(ctx.debug_read(19, 64 * 4), np.int32).copy()
     ctx.close()
     lang = os.path.join(os.environ["WMI_MODEL_CACHE"], "ggml-micro-lang-51865.bin")
     if os.path.exists(lang):

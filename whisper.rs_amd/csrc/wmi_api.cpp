@@ -222,12 +222,19 @@ struct wmi_context {
     int32_t *dkvsrc = nullptr, *dhist_par = nullptr, *dhist_tok = nullptr;
     std::vector<int32_t> kvsrc_init;
     // timestamp decoding (wmi_transcribe / wmi_decode_timestamps)
-    int32_t *dts_tok = nullptr; // [8] token the sampler chose for the next step
-    TsRec *dts_rec = nullptr;   // [n_text_ctx] per generated token
+    int32_t *dts_tok = nullptr; // [8] token the sampler chose for each row's next step
+    int32_t *dts_done = nullptr;// [8] row sampled EOT (same allocation, behind dts_tok)
+    TsRec *dts_rec = nullptr;   // [8][n_text_ctx] per row and generated token
+    int32_t *d_win = nullptr;   // batched transcription: source recording [8], then mel offset [8] of each encoder slot
+    bool no_context = false;    // wmi_set_no_context: windows of wmi_transcribe take no earlier text
     struct Segment { int64_t t0, t1; int first, count; std::string text; };
-    std::vector<Segment> segments;      // result_all (main.rs:353) of the last transcribe
-    std::vector<TsRec> seg_tokens;      // their tokens, in order
-    std::vector<int32_t> ts_prompt;     // prompt of the last timestamp window (debug read 19)
+    struct SegList {
+        std::vector<Segment> segments;  // result_all (main.rs:353)
+        std::vector<TsRec> tokens;      // their tokens, in order
+    };
+    // per recording of the last transcribe (one) / transcribe_batch
+    std::vector<SegList> results = std::vector<SegList>(1);
+    std::vector<int32_t> ts_prompt;     // prompt rows of the last timestamp window, [rows][np] (debug read 19)
     // language and task (wmi_set_language / wmi_set_task).  While every clip
     // is language 0 and the task transcribe (lang_default), the decode
     // entries enqueue what they always did; otherwise the block's prompt rows
@@ -1234,13 +1241,17 @@ int run_mel(wmi_context *ctx) {
     return WMI_OK;
 }
 
-int run_encode(wmi_context *ctx, int mel_offset) {
+// Encode B slots.  Without src / off: the loaded clips, each at mel_offset.
+// With them (device arrays [B]): slot b holds recording src[b]'s window at
+// off[b], B <= the loaded clips (a round of run_transcribe_batch).
+int run_encode(wmi_context *ctx, int mel_offset, int slots = 0, const int32_t *src = nullptr,
+               const int32_t *off = nullptr) {
     const wmi_hparams &hp = ctx->hp;
-    const int B = ctx->n_clips;
+    const int B = src ? slots : ctx->n_clips;
     const int T = ctx->cur_ctx > 0 ? ctx->cur_ctx : hp.n_audio_ctx, T2 = 2 * T;
     const int Tp = (int)up(T, 64);
     const int n = hp.n_audio_state, H = hp.n_audio_head, nt = hp.n_text_state;
-    if (B < 1) return set_err(ctx, WMI_E_INVALID_ARG, "encode before pcm_to_mel");
+    if (B < 1 || B > ctx->n_clips) return set_err(ctx, WMI_E_INVALID_ARG, "encode before pcm_to_mel");
     if (mel_offset < 0) return set_err(ctx, WMI_E_INVALID_ARG, "negative mel_offset");
     {
         std::string why;
@@ -1254,7 +1265,7 @@ int run_encode(wmi_context *ctx, int mel_offset) {
         HIPCHK(ctx, hipMemsetAsync(ctx->vt, 0, qkv_bytes, s));
         ctx->layout_T = T;
     }
-    if (ctx->checksums) {  // clip 0's mel window (main.rs:1819-1832)
+    if (ctx->checksums && !src) {  // clip 0's mel window (main.rs:1819-1832)
         const int64_t nl = ctx->n_len_host[0], nm = hp.n_mels;
         std::vector<float> m((size_t)nm * nl);
         if (!m.empty()) HIPCHK(ctx, hipMemcpy(m.data(), ctx->d_mel, m.size() * 4, hipMemcpyDeviceToHost));
@@ -1273,7 +1284,7 @@ int run_encode(wmi_context *ctx, int mel_offset) {
     auto W32 = [&](const uint16_t *w) { return f32 ? (const float *)w : nullptr; };
     // (f16 models: conv2's zero pad rows of g1 are written by the window kernel)
     HIPCHK(ctx, launch_mel_window(s, ctx->d_mel, ctx->mel_stride, hp.n_mels, ctx->d_nlen, mel_offset, T2, ctx->Cp1,
-                                  ctx->xconv, B, ctx->xconv32, f32 ? nullptr : ctx->g1, n));
+                                  ctx->xconv, B, ctx->xconv32, f32 ? nullptr : ctx->g1, n, src, off));
     if (f32) HIPCHK(ctx, hipMemsetAsync(ctx->g1, 0, (size_t)B * (T2 + 2) * n * 2, s));
     GemmArgs g{};
     // conv1 + bias + GELU (main.rs:1834-1855)
@@ -1355,7 +1366,8 @@ int run_encode(wmi_context *ctx, int mel_offset) {
 //   RUN_GREEDY  rows are consecutive clips; the argmax of a step feeds the next
 //               and is recorded in dtokens ([.][out_stride])
 //   RUN_BEAM    rows are the K hypotheses of clip b0; k_beam_step follows a step
-//   RUN_TS      one row; the timestamp sampler (k_ts_sample) follows a step
+//   RUN_TS      rows are consecutive clips, as greedy; the timestamp sampler
+//               (k_ts_sample) follows a step and picks each row's next token
 //   RUN_FORCED  the feed supplies every token (teacher forcing, the [SOT] step
 //               of language detection): each step's logits stay in dlogits and
 //               nothing is recorded
@@ -1385,6 +1397,7 @@ TsArgs ts_args(wmi_context *ctx, const DecRun &run) {
     ta.logits = ctx->dlogits; ta.V = ctx->hp.n_vocab; ta.beg = ctx->sp.beg; ta.eot = ctx->sp.eot; ta.sot = ctx->sp.sot;
     ta.solm = ctx->sp.solm; ta.not_ = ctx->sp.not_; ta.feed_len = run.feed_len; ta.max_rec = ctx->hp.n_text_ctx;
     ta.st = ctx->dstate; ta.tok_out = ctx->dts_tok; ta.rec = ctx->dts_rec;
+    ta.B = run.B; ta.done = ctx->dts_done;
     return ta;
 }
 
@@ -1793,10 +1806,12 @@ PersistArgs persist_args(wmi_context *ctx, const DecRun &run, int G) {
 // Zero the state a run (or its next 8-row block) starts from, in one launch:
 // the error word once per run (`first` block, unless language detection has
 // run in front and zeroed it: the caller reads the word after its own
-// launches), step state, argmax shards, chain sync words, and the exchange
+// launches), step state, argmax shards, chain sync words, a timestamp run's
+// done words, and the exchange
 // blocks of a persistent grid G (and of the split grids Gh).  A feed of up to
 // 64 words rides in the launch; a longer one is copied.
-int reset_run(wmi_context *ctx, bool first, int G, int Gh, bool err_cleared, const int32_t *feed, int n_feed) {
+int reset_run(wmi_context *ctx, bool first, int G, int Gh, bool err_cleared, const int32_t *feed, int n_feed,
+              bool ts = false) {
     ResetArgs ra{};
     auto zero = [&](void *p, size_t bytes) {
         ra.ptr[ra.n] = p;
@@ -1813,6 +1828,7 @@ int reset_run(wmi_context *ctx, bool first, int G, int Gh, bool err_cleared, con
     zero(ctx->dstate, sizeof(DecState));
     zero(ctx->damax, 8 * AMAX_SHARDS * 8);
     zero(ctx->dsync, ctx->sync_bytes);
+    if (ts) zero(ctx->dts_done, DEC_ROWS * 4);  // (a timestamp run: no row has met EOT)
     if (G > 0) zero(ctx->d_xg, ctx->xg_bytes);
     if (Gh > 0) {
         zero(ctx->d_xg2, ctx->xg_bytes);
@@ -2110,70 +2126,156 @@ int run_greedy(wmi_context *ctx, int n_gen, int suppress_eot, bool early_stop, s
 bool valid(const wmi_context *ctx) { return ctx != nullptr && ctx->d_model != nullptr; }
 
 
-// Timestamp decoding of encoded clip `clip` after `prompt` (whisper.cpp-1.0.3
-// whisper_full inner loop): up to max_tokens sampled
-// with the device timestamp sampler (k_ts_sample), stopping after EOT.
-int run_ts_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, int max_tokens,
-                  std::vector<TsRec> *out) {
+// Timestamp decoding of the encoded clips [b0, b0 + B) in lockstep (whisper.cpp-
+// 1.0.3 whisper_full inner loop): row b feeds the np
+// tokens feed[b * np ..), then up to max_tokens are sampled per row with the
+// device timestamp sampler (k_ts_sample).  A row stops at its EOT; the run
+// ends when every row has (polled through the rows' done words every 16
+// steps) or at max_tokens.  out[b] = row b's records up to and including EOT.
+int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &feed, int np, int max_tokens,
+                std::vector<std::vector<TsRec>> *out) {
     const wmi_hparams &hp = ctx->hp;
-    const int np = (int)prompt.size();
     if (ctx->enc_T <= 0) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
+    if (B < 1 || B > DEC_ROWS || b0 < 0 || b0 + B > ctx->enc_clips)
+        return set_err(ctx, WMI_E_INVALID_ARG, "rows [%d, %d) outside the %d encoded clips", b0, b0 + B, ctx->enc_clips);
     if (np < 1 || max_tokens < 1 || np + max_tokens > hp.n_text_ctx)
         return set_err(ctx, WMI_E_INVALID_ARG, "prompt %d + max_tokens %d exceed n_text_ctx %d", np, max_tokens,
                        hp.n_text_ctx);
     if (!ctx->dts_tok) {
-        HIPCHK(ctx, hipMalloc(&ctx->dts_tok, 64));
-        HIPCHK(ctx, hipMalloc(&ctx->dts_rec, (size_t)hp.n_text_ctx * sizeof(TsRec)));
+        HIPCHK(ctx, hipMalloc(&ctx->dts_tok, 2 * DEC_ROWS * 4));
+        HIPCHK(ctx, hipMemset(ctx->dts_tok, 0, 2 * DEC_ROWS * 4));
+        ctx->dts_done = ctx->dts_tok + DEC_ROWS;
+        HIPCHK(ctx, hipMalloc(&ctx->dts_rec, (size_t)DEC_ROWS * hp.n_text_ctx * sizeof(TsRec)));
         ctx->clear_graphs();
     }
-    int rc = ensure_decode_buffers(ctx, np, 1);
+    int rc = ensure_decode_buffers(ctx, DEC_ROWS * np, 1);
     if (rc) return rc;
-    ctx->ts_prompt = prompt;
-    const DecRun run{RUN_TS, clip, 1, np, np};
+    ctx->ts_prompt = feed;
+    const DecRun run{RUN_TS, b0, B, np, np};
     const int total = np + max_tokens - 1;
-    std::vector<TsRec> rec((size_t)max_tokens);
-    int n_out;
+    int have = 0;
     do {
-        n_out = max_tokens;
         const RunGrid gr = run_grid(ctx, run);
-        rc = reset_run(ctx, true, gr.G, gr.Gh, false, prompt.data(), np);
+        rc = reset_run(ctx, true, gr.G, gr.Gh, false, feed.data(), B * np, true);
         if (rc) return rc;
+        have = 0;
         for (int done = 0; done < total;) {
             const int chunk = std::min(16, total - done);
             rc = advance_run(ctx, run, gr, done, chunk);
             if (rc) return rc;
             done += chunk;
-            const int have = done - np + 1;  // records written so far
-            if (have <= 0) continue;
-            HIPCHK(ctx, hipMemcpyAsync(rec.data(), ctx->dts_rec, (size_t)have * sizeof(TsRec), hipMemcpyDeviceToHost,
-                                       ctx->stream));
+            have = done - np + 1;  // records written so far (per row that has not met EOT)
+            if (have <= 0 || done >= total) continue;
+            int32_t dn[DEC_ROWS];
+            HIPCHK(ctx, hipMemcpyAsync(dn, ctx->dts_done, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            bool eot = false;
-            for (int i = 0; i < have && !eot; ++i)
-                if (rec[i].id == ctx->sp.eot) { n_out = i + 1; eot = true; }
-            if (eot) break;
+            bool all = true;
+            for (int b = 0; b < B; ++b) all = all && dn[b] != 0;
+            if (all) break;
         }
+        have = std::max(have, 0);
+        out->assign(B, std::vector<TsRec>((size_t)have));
+        for (int b = 0; b < B && have > 0; ++b)
+            HIPCHK(ctx, hipMemcpyAsync((*out)[b].data(), ctx->dts_rec + (size_t)b * hp.n_text_ctx,
+                                       (size_t)have * sizeof(TsRec), hipMemcpyDeviceToHost, ctx->stream));
         rc = finish_run(ctx);
     } while (rc == RERUN_ON_CHAIN);
     if (rc) return rc;
-    out->assign(rec.begin(), rec.begin() + n_out);
+    // (a row that met EOT wrote nothing behind it: what lies there is stale)
+    for (auto &r : *out)
+        for (size_t i = 0; i < r.size(); ++i)
+            if (r[i].id == ctx->sp.eot) { r.resize(i + 1); break; }
     return WMI_OK;
+}
+
+// one row: encoded clip `clip` after `prompt`
+int run_ts_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, int max_tokens,
+                  std::vector<TsRec> *out) {
+    std::vector<std::vector<TsRec>> rows;
+    int rc = run_ts_rows(ctx, clip, 1, prompt, (int)prompt.size(), max_tokens, &rows);
+    if (rc) return rc;
+    *out = std::move(rows[0]);
+    return WMI_OK;
+}
+
+// The bookkeeping of one whisper_full window that started at frame `seek` of a
+// recording of n_len frames and sampled `toks`: the tokens up to the last
+// timestamp become segments [t0, t1) (10 ms units) appended to `res` (and,
+// with `past`, to the text context of later windows).  Returns the frames to
+// advance: to the last timestamp, or past the window; a window without a
+// usable timestamp is skipped by 100 frames.
+int64_t finish_ts_window(wmi_context *ctx, std::vector<TsRec> toks, int64_t seek, int64_t n_len, int window,
+                         wmi_context::SegList &res, std::vector<int32_t> *past) {
+    const int beg = ctx->sp.beg, eot = ctx->sp.eot;
+    int64_t seek_delta = window;
+    int result_len = 0;
+    bool failed = false, ended = false;
+    for (int i = 0; i < (int)toks.size(); ++i) {
+        if (toks[i].id > beg) { seek_delta = 2 * (int64_t)(toks[i].id - beg); result_len = i + 1; }
+        if (toks[i].id == eot) {
+            ended = true;
+            if (result_len == 0) {
+                if (seek + seek_delta + 100 >= n_len) result_len = i + 1;
+                else failed = true;
+            }
+            break;
+        }
+    }
+    if (!ended && (result_len == 0 || seek_delta < window / 2)) failed = true;  // stuck: no end in n_max tokens
+    if (failed) return 100;
+    toks.resize(result_len);
+    if (past)
+        for (const TsRec &t : toks) past->push_back(t.id);
+    if (!toks.empty()) {
+        int i0 = 0;
+        int64_t t0 = seek + 2 * (int64_t)(toks.front().tid - beg);
+        std::string text;
+        for (int i = 0; i < (int)toks.size(); ++i) {
+            if (toks[i].id < eot) text += ctx->vocab[toks[i].id];
+            if (toks[i].id > beg) {
+                const int64_t t1 = seek + 2 * (int64_t)(toks[i].tid - beg);
+                if (!text.empty()) {
+                    res.segments.push_back({t0, t1, (int)res.tokens.size(), i - i0 + 1, text});
+                    res.tokens.insert(res.tokens.end(), toks.begin() + i0, toks.begin() + i + 1);
+                }
+                text.clear();
+                while (i < (int)toks.size() && toks[i].id > beg) ++i;
+                --i;
+                t0 = t1;
+                i0 = i + 1;
+            }
+        }
+        if (!text.empty()) {
+            res.segments.push_back({t0, seek + seek_delta, (int)res.tokens.size(), (int)toks.size() - i0, text});
+            res.tokens.insert(res.tokens.end(), toks.begin() + i0, toks.end());
+        }
+    }
+    return seek_delta;
+}
+
+// the prompt every window starts from: [sot (, language, task)]
+std::vector<int32_t> ts_init_prompt(const wmi_context *ctx, int lang) {
+    std::vector<int32_t> init{ctx->sp.sot};
+    if (ctx->sp.is_multilingual) {
+        init.push_back(ctx->sp.sot + 1 + lang);
+        init.push_back(ctx->task == WMI_TASK_TRANSLATE ? ctx->sp.translate : ctx->sp.transcribe);
+    }
+    return init;
 }
 
 // whisper_full (whisper.cpp-1.0.3, the loop the reference's WhisperSegment /
 // WhisperTokenData / prompt_past fields belong to, main.rs:317-331, 353-362,
 // 599-604): windows of 2 * n_ctx mel frames from `seek`, prompt = [prev] +
 // the last min(n_text_ctx/2, past) tokens of earlier windows (whisper_full's
-// n_take) + [sot (, lang, transcribe)], at most n_text_ctx/2 - 4 sampled
-// tokens (1 + 224 + 3 + 220 = 448 positions at most), timestamp sampling; a window's tokens up to its last
-// timestamp form segments [t0, t1) in 10 ms units; seek advances to the
-// last timestamp, or past the window; a window without a usable timestamp is
-// skipped by 100 frames.  Restated op for op in oracle/pyoracle.py transcribe_ref.
+// n_take; none with wmi_set_no_context) + [sot (, lang, transcribe)], at most n_text_ctx/2 - 4 sampled
+// tokens (1 + 224 + 3 + 220 = 448 positions at most), timestamp sampling; the
+// window's bookkeeping is finish_ts_window.  Restated op for op in
+// oracle/pyoracle.py transcribe_ref.
 int run_transcribe(wmi_context *ctx, int max_tokens) {
     const wmi_hparams &hp = ctx->hp;
     const int64_t n_len = ctx->n_len_host[0];
     const int n_ctx = ctx->cur_ctx > 0 ? ctx->cur_ctx : hp.n_audio_ctx;
-    const int window = 2 * n_ctx, beg = ctx->sp.beg, eot = ctx->sp.eot;
+    const int window = 2 * n_ctx;
     const int n_max = std::min(max_tokens, hp.n_text_ctx / 2 - 4);
     // clip 0's language and the task; AUTO: detected once, on the first
     // window (as whisper.cpp does), and kept for every later window
@@ -2181,8 +2283,7 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
     float lang_p = -1.0f;
     std::vector<int32_t> init;
     std::vector<int32_t> past;
-    ctx->segments.clear();
-    ctx->seg_tokens.clear();
+    ctx->results.assign(1, {});
     for (int64_t seek = 0; seek < n_len;) {
         int rc = run_encode(ctx, (int)seek);
         if (rc) return rc;
@@ -2193,11 +2294,7 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
                 HIPCHK(ctx, hipMemcpy(&lang, ctx->d_lang_det, 4, hipMemcpyDeviceToHost));
                 HIPCHK(ctx, hipMemcpy(&lang_p, ctx->d_lang_p, 4, hipMemcpyDeviceToHost));
             }
-            init.push_back(ctx->sp.sot);
-            if (ctx->sp.is_multilingual) {
-                init.push_back(ctx->sp.sot + 1 + lang);
-                init.push_back(ctx->task == WMI_TASK_TRANSLATE ? ctx->sp.translate : ctx->sp.transcribe);
-            }
+            init = ts_init_prompt(ctx, lang);
             ctx->lang_used[0] = lang;
             ctx->lang_p[0] = lang_p;
         }
@@ -2211,50 +2308,87 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
         std::vector<TsRec> toks;
         rc = run_ts_window(ctx, 0, prompt, n_max, &toks);
         if (rc) return rc;
-        int64_t seek_delta = window;
-        int result_len = 0;
-        bool failed = false, ended = false;
-        for (int i = 0; i < (int)toks.size(); ++i) {
-            if (toks[i].id > beg) { seek_delta = 2 * (int64_t)(toks[i].id - beg); result_len = i + 1; }
-            if (toks[i].id == eot) {
-                ended = true;
-                if (result_len == 0) {
-                    if (seek + seek_delta + 100 >= n_len) result_len = i + 1;
-                    else failed = true;
-                }
-                break;
-            }
+        seek += finish_ts_window(ctx, std::move(toks), seek, n_len, window, ctx->results[0],
+                                 ctx->no_context ? nullptr : &past);
+    }
+    return WMI_OK;
+}
+
+// wmi_transcribe_batch: every loaded recording through whisper_full's loop
+// without text context, up to DEC_ROWS of them per decoder step.  All mels
+// stay resident; a recording holds host state (seek, language) and its own
+// segment list.  Per round the active recordings sit compacted in rows
+// 0..B-1: one encode of the B slots, each at its recording's seek
+// (k_mel_window's per-slot source and offset), one lockstep timestamp window
+// of B rows — every prompt is [sot (, language, task)], so the rows share the
+// decoder's one position — then each row's window bookkeeping.  A recording
+// that reached its end leaves its row; a waiting one takes a free row at the
+// next round.
+int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
+    const wmi_hparams &hp = ctx->hp;
+    const int R = ctx->n_clips;
+    const int n_ctx = ctx->cur_ctx > 0 ? ctx->cur_ctx : hp.n_audio_ctx;
+    const int window = 2 * n_ctx;
+    const int n_max = std::min(max_tokens, hp.n_text_ctx / 2 - 4);
+    if (!ctx->d_win) HIPCHK(ctx, hipMalloc(&ctx->d_win, 2 * DEC_ROWS * 4));
+    std::vector<int64_t> seek((size_t)R, 0);
+    std::vector<int> lang((size_t)R);
+    for (int r = 0; r < R; ++r) {
+        lang[r] = ctx->lang_set[r];
+        ctx->lang_used[r] = lang[r];  // (AUTO: until the recording's first window detects it)
+        ctx->lang_p[r] = -1.0f;
+    }
+    ctx->results.assign((size_t)R, {});
+    std::vector<int> rows;  // recording of each decoder row
+    int next = 0;
+    for (;;) {
+        size_t k = 0;
+        for (int r : rows)
+            if (seek[r] < ctx->n_len_host[r]) rows[k++] = r;
+        rows.resize(k);
+        for (; next < R && rows.size() < (size_t)DEC_ROWS; ++next)
+            if (ctx->n_len_host[next] > 0) rows.push_back(next);
+        if (rows.empty()) break;
+        const int B = (int)rows.size();
+        int32_t win[2 * DEC_ROWS] = {};
+        for (int b = 0; b < B; ++b) {
+            win[b] = rows[b];
+            win[DEC_ROWS + b] = (int32_t)seek[rows[b]];
         }
-        if (!ended && (result_len == 0 || seek_delta < window / 2)) failed = true;  // stuck: no end in n_max tokens
-        if (failed) { seek += 100; continue; }
-        toks.resize(result_len);
-        for (const TsRec &t : toks) past.push_back(t.id);
-        if (!toks.empty()) {
-            int i0 = 0;
-            int64_t t0 = seek + 2 * (int64_t)(toks.front().tid - beg);
-            std::string text;
-            for (int i = 0; i < (int)toks.size(); ++i) {
-                if (toks[i].id < eot) text += ctx->vocab[toks[i].id];
-                if (toks[i].id > beg) {
-                    const int64_t t1 = seek + 2 * (int64_t)(toks[i].tid - beg);
-                    if (!text.empty()) {
-                        ctx->segments.push_back({t0, t1, (int)ctx->seg_tokens.size(), i - i0 + 1, text});
-                        ctx->seg_tokens.insert(ctx->seg_tokens.end(), toks.begin() + i0, toks.begin() + i + 1);
-                    }
-                    text.clear();
-                    while (i < (int)toks.size() && toks[i].id > beg) ++i;
-                    --i;
-                    t0 = t1;
-                    i0 = i + 1;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_win, win, sizeof win, hipMemcpyHostToDevice, ctx->stream));
+        int rc = run_encode(ctx, 0, B, ctx->d_win, ctx->d_win + DEC_ROWS);
+        if (rc) return rc;
+        bool detect = false;
+        for (int b = 0; b < B; ++b) detect = detect || lang[rows[b]] == WMI_LANG_AUTO;
+        if (detect) {  // (only in a round that holds an AUTO recording's first window)
+            rc = run_lang_detect_sync(ctx);
+            if (rc) return rc;
+            int32_t det[DEC_ROWS];
+            float p[DEC_ROWS];
+            HIPCHK(ctx, hipMemcpy(det, ctx->d_lang_det, (size_t)B * 4, hipMemcpyDeviceToHost));
+            HIPCHK(ctx, hipMemcpy(p, ctx->d_lang_p, (size_t)B * 4, hipMemcpyDeviceToHost));
+            for (int b = 0; b < B; ++b)
+                if (lang[rows[b]] == WMI_LANG_AUTO) {
+                    lang[rows[b]] = det[b];
+                    ctx->lang_used[rows[b]] = det[b];
+                    ctx->lang_p[rows[b]] = p[b];
                 }
-            }
-            if (!text.empty()) {
-                ctx->segments.push_back({t0, seek + seek_delta, (int)ctx->seg_tokens.size(),
-                                         (int)toks.size() - i0, text});
-                ctx->seg_tokens.insert(ctx->seg_tokens.end(), toks.begin() + i0, toks.end());
-            }
         }
-        seek += seek_delta;
+        std::vector<int32_t> feed;
+        int np = 0;
+        for (int b = 0; b < B; ++b) {
+            const std::vector<int32_t> init = ts_init_prompt(ctx, lang[rows[b]]);
+            np = (int)init.size();
+            feed.insert(feed.end(), init.begin(), init.end());
+        }
+        std::vector<std::vector<TsRec>> toks;
+        rc = run_ts_rows(ctx, 0, B, feed, np, n_max, &toks);
+        if (rc) return rc;
+        for (int b = 0; b < B; ++b) {
+            const int r = rows[b];
+            seek[r] += finish_ts_window(ctx, std::move(toks[b]), seek[r], ctx->n_len_host[r], window, ctx->results[r],
+                                        nullptr);
+        }
     }
     return WMI_OK;
 }
@@ -2521,6 +2655,9 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->d_ptrace) (void)hipFree(ctx->d_ptrace);
     if (ctx->d_lgall) (void)hipFree(ctx->d_lgall);
     if (ctx->d_lang) (void)hipFree(ctx->d_lang);
+    if (ctx->dts_tok) (void)hipFree(ctx->dts_tok);
+    if (ctx->dts_rec) (void)hipFree(ctx->dts_rec);
+    if (ctx->d_win) (void)hipFree(ctx->d_win);
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -2726,13 +2863,101 @@ static int wmi_transcribe_impl(wmi_context *ctx, const float *pcm, size_t n_samp
     if (rc) return rc;
     rc = run_transcribe(ctx, max_tokens);
     if (rc) return rc;
-    *n_segments = (int32_t)ctx->segments.size();
+    *n_segments = (int32_t)ctx->results[0].segments.size();
+    return WMI_OK;
+}
+
+static int wmi_decode_timestamps_batch_impl(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens,
+                                            wmi_token_data *out, int32_t *n_out) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (!prompt || n_prompt < 1 || max_tokens < 1 || !out || !n_out)
+        return set_err(ctx, WMI_E_INVALID_ARG, "null prompt / out / n_out, or n_prompt %d / max_tokens %d below 1", n_prompt,
+                       max_tokens);
+    for (int i = 0; i < n_prompt; ++i)
+        if (prompt[i] < 0 || prompt[i] >= ctx->hp.n_vocab) return set_err(ctx, WMI_E_INVALID_ARG, "token id %d", prompt[i]);
+    if (ctx->enc_T <= 0 || ctx->enc_clips < 1) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int Bt = ctx->enc_clips;
+    for (int b0 = 0; b0 < Bt; b0 += DEC_ROWS) {
+        const int B = std::min(DEC_ROWS, Bt - b0);
+        std::vector<int32_t> feed;
+        for (int b = 0; b < B; ++b) feed.insert(feed.end(), prompt, prompt + n_prompt);
+        std::vector<std::vector<TsRec>> rec;
+        int rc = run_ts_rows(ctx, b0, B, feed, n_prompt, max_tokens, &rec);
+        if (rc) return rc;
+        for (int b = 0; b < B; ++b) {
+            for (size_t i = 0; i < rec[b].size(); ++i) to_token_data(rec[b][i], out + (size_t)(b0 + b) * max_tokens + i);
+            n_out[b0 + b] = (int32_t)rec[b].size();
+        }
+    }
+    return WMI_OK;
+}
+
+static int wmi_transcribe_batch_impl(wmi_context *ctx, int n_clips, const float *const *pcm, const size_t *n_samples,
+                                     int max_tokens, int32_t *n_segments) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (n_clips < 1 || n_clips > ctx->max_clips)
+        return set_err(ctx, WMI_E_INVALID_ARG, "n_clips %d outside [1, max_clips=%d]", n_clips, ctx->max_clips);
+    if (!pcm || !n_samples || !n_segments) return set_err(ctx, WMI_E_INVALID_ARG, "null pcm / n_samples / n_segments");
+    if (max_tokens < 1) return set_err(ctx, WMI_E_INVALID_ARG, "max_tokens %d below 1", max_tokens);
+    for (int c = 0; c < n_clips; ++c)  // (wmi_set_language / wmi_set_task refuse these; checked where they are used)
+        if (ctx->n_lang == 0 && (ctx->lang_set[c] != 0 || ctx->task != WMI_TASK_TRANSCRIBE))
+            return set_err(ctx, WMI_E_INVALID_ARG, "language %d / task %d on an English-only model (clip %d)",
+                           ctx->lang_set[c], ctx->task, c);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = wmi_pcm_to_mel_batch(ctx, n_clips, pcm, n_samples);
+    if (rc) return rc;
+    rc = run_transcribe_batch(ctx, max_tokens);
+    if (rc) return rc;
+    for (int c = 0; c < n_clips; ++c) n_segments[c] = (int32_t)ctx->results[c].segments.size();
+    return WMI_OK;
+}
+
+int wmi_set_no_context(wmi_context *ctx, int no_context) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    if (no_context != 0 && no_context != 1) return set_err(ctx, WMI_E_INVALID_ARG, "no_context %d is neither 0 nor 1", no_context);
+    ctx->no_context = no_context != 0;
+    return WMI_OK;
+}
+
+int wmi_get_segment_of(const wmi_context *ctx, int clip, int i, int64_t *t0, int64_t *t1, char *text, size_t cap,
+                       size_t *len) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    wmi_context *ec = const_cast<wmi_context *>(ctx);  // (last_error only)
+    if (clip < 0 || clip >= (int)ctx->results.size())
+        return set_err(ec, WMI_E_INVALID_ARG, "clip %d outside the %d recordings of the last transcribe", clip,
+                       (int)ctx->results.size());
+    if (i < 0 || i >= (int)ctx->results[clip].segments.size() || !len)
+        return set_err(ec, WMI_E_INVALID_ARG, "segment %d outside clip %d's %d segments, or null len", i, clip,
+                       (int)ctx->results[clip].segments.size());
+    const auto &sg = ctx->results[clip].segments[i];
+    if (t0) *t0 = sg.t0;
+    if (t1) *t1 = sg.t1;
+    *len = sg.text.size();
+    if (!text || cap < sg.text.size()) return WMI_E_NO_SPACE;
+    memcpy(text, sg.text.data(), sg.text.size());
+    return WMI_OK;
+}
+
+int wmi_get_segment_tokens_of(const wmi_context *ctx, int clip, int i, wmi_token_data *out, size_t cap, int32_t *n) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    wmi_context *ec = const_cast<wmi_context *>(ctx);
+    if (clip < 0 || clip >= (int)ctx->results.size())
+        return set_err(ec, WMI_E_INVALID_ARG, "clip %d outside the %d recordings of the last transcribe", clip,
+                       (int)ctx->results.size());
+    if (i < 0 || i >= (int)ctx->results[clip].segments.size() || !n)
+        return set_err(ec, WMI_E_INVALID_ARG, "segment %d outside clip %d's %d segments, or null n", i, clip,
+                       (int)ctx->results[clip].segments.size());
+    const auto &sg = ctx->results[clip].segments[i];
+    *n = sg.count;
+    if (!out || cap < (size_t)sg.count) return WMI_E_NO_SPACE;
+    for (int k = 0; k < sg.count; ++k) to_token_data(ctx->results[clip].tokens[sg.first + k], out + k);
     return WMI_OK;
 }
 
 int wmi_get_segment(const wmi_context *ctx, int i, int64_t *t0, int64_t *t1, char *text, size_t cap, size_t *len) {
-    if (!ctx || i < 0 || i >= (int)ctx->segments.size() || !len) return WMI_E_INVALID_ARG;
-    const auto &sg = ctx->segments[i];
+    if (!ctx || i < 0 || i >= (int)ctx->results[0].segments.size() || !len) return WMI_E_INVALID_ARG;
+    const auto &sg = ctx->results[0].segments[i];
     if (t0) *t0 = sg.t0;
     if (t1) *t1 = sg.t1;
     *len = sg.text.size();
@@ -2742,11 +2967,11 @@ int wmi_get_segment(const wmi_context *ctx, int i, int64_t *t0, int64_t *t1, cha
 }
 
 int wmi_get_segment_tokens(const wmi_context *ctx, int i, wmi_token_data *out, size_t cap, int32_t *n) {
-    if (!ctx || i < 0 || i >= (int)ctx->segments.size() || !n) return WMI_E_INVALID_ARG;
-    const auto &sg = ctx->segments[i];
+    if (!ctx || i < 0 || i >= (int)ctx->results[0].segments.size() || !n) return WMI_E_INVALID_ARG;
+    const auto &sg = ctx->results[0].segments[i];
     *n = sg.count;
     if (!out || cap < (size_t)sg.count) return WMI_E_NO_SPACE;
-    for (int k = 0; k < sg.count; ++k) to_token_data(ctx->seg_tokens[sg.first + k], out + k);
+    for (int k = 0; k < sg.count; ++k) to_token_data(ctx->results[0].tokens[sg.first + k], out + k);
     return WMI_OK;
 }
 
@@ -3297,6 +3522,16 @@ int wmi_decode_timestamps(wmi_context *ctx, const int32_t *prompt, int n_prompt,
 
 int wmi_transcribe(wmi_context *ctx, const float *pcm, size_t n_samples, int max_tokens, int32_t *n_segments) {
     return guarded(ctx, [&] { return wmi_transcribe_impl(ctx, pcm, n_samples, max_tokens, n_segments); });
+}
+
+int wmi_decode_timestamps_batch(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens, wmi_token_data *out,
+                                int32_t *n_out) {
+    return guarded(ctx, [&] { return wmi_decode_timestamps_batch_impl(ctx, prompt, n_prompt, max_tokens, out, n_out); });
+}
+
+int wmi_transcribe_batch(wmi_context *ctx, int n_clips, const float *const *pcm, const size_t *n_samples, int max_tokens,
+                         int32_t *n_segments) {
+    return guarded(ctx, [&] { return wmi_transcribe_batch_impl(ctx, n_clips, pcm, n_samples, max_tokens, n_segments); });
 }
 
 int wmi_pcm_to_mel_batch(wmi_context *ctx, int n_clips, const float *const *pcm, const size_t *n_samples) {

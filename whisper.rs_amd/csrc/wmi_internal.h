@@ -47,10 +47,14 @@ hipError_t launch_dec_reset(hipStream_t s, const ResetArgs &a);
 hipError_t launch_mel_norm(hipStream_t s, float *mel, int64_t mel_stride, int n_mel, const int64_t *n_len,
                            int64_t max_len, const uint32_t *mel_max, int n_clips);
 // mel window (main.rs:1816-1833) -> conv1 input, f16 time-major, zero-padded
-// by one frame at each end and to Cp channels: X[b][T2 + 2][Cp].
+// by one frame at each end and to Cp channels: X[b][T2 + 2][Cp].  With src /
+// off (device arrays [n_clips]) encoder slot b takes the window of recording
+// src[b] at frame off[b] (n_len[src[b]] frames) instead of clip b's at
+// mel_offset: the rows of a batched transcription sit at different seeks.
 hipError_t launch_mel_window(hipStream_t s, const float *mel, int64_t mel_stride, int n_mel, const int64_t *n_len,
                              int mel_offset, int T2, int Cp, uint16_t *xconv, int n_clips,
-                             float *xconv32 = nullptr, uint16_t *g1 = nullptr, int n = 0);
+                             float *xconv32 = nullptr, uint16_t *g1 = nullptr, int n = 0,
+                             const int32_t *src = nullptr, const int32_t *off = nullptr);
 
 // ---- LayerNorm (ggml norm + mul(repeat(w)) + add(repeat(b))) ----------------
 hipError_t launch_layernorm(hipStream_t s, const float *x, int rows, int n, const float *w, const float *b,
@@ -275,11 +279,13 @@ struct TsRec {               // WhisperTokenData (main.rs:317-331) as sampled
     int32_t pad;
 };
 struct TsArgs {
-    const float *logits;     // [V] (row 0)
+    const float *logits;     // [B][V]
     int V, beg, eot, sot, solm, not_, feed_len, max_rec;
+    int B;                   // decoder rows (<= DEC_ROWS): one workgroup each
     const DecState *st;      // pos already advanced by the logits launch
-    int32_t *tok_out;        // token fed at the next step
-    TsRec *rec;              // [max_rec], record t = pos - feed_len
+    int32_t *tok_out;        // [B] token row b feeds at the next step
+    TsRec *rec;              // [B][max_rec], record t = pos - feed_len
+    int32_t *done;           // [B] != 0 once row b sampled EOT: no more records, feeds EOT
 };
 hipError_t launch_ts_sample(hipStream_t s, const TsArgs &a);
 // WMI_LOGITS_ALL on the kernel chain: logits [rows][V] -> all + (pos - 1) * slab

@@ -215,20 +215,25 @@ __global__ void k_mel_norm(float *mel, int64_t mel_stride, int n_mel, const int6
     }
 }
 
+// Encoder slot b takes the window of recording src[b] at frame off[b] (src
+// null: slot b is clip b, every clip at mel_offset)
 __global__ void k_mel_window(const float *mel, int64_t mel_stride, int n_mel, const int64_t *n_len, int mel_offset,
-                             int T2, int Cp, uint16_t *xconv, float *xconv32, uint16_t *g1, int n) {
+                             const int32_t *src, const int32_t *off, int T2, int Cp, uint16_t *xconv, float *xconv32,
+                             uint16_t *g1, int n) {
     const int b = blockIdx.y;
+    const int clip = src ? src[b] : b;
+    if (src) mel_offset = off[b];
     // conv1's output rows 0 and T2 + 1 of this clip are conv2's zero padding
     // (its epilogue writes rows 1..T2): zeroed here instead of a memset of g1
     if (g1)
         for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < 2 * (int64_t)n;
              idx += (int64_t)gridDim.x * blockDim.x)
             g1[((int64_t)b * (T2 + 2) + (idx < n ? 0 : T2 + 1)) * n + (idx < n ? idx : idx - n)] = 0;
-    const int64_t nl = n_len[b];
+    const int64_t nl = n_len[clip];
     const int64_t tot = (int64_t)(T2 + 2) * Cp;
     const int64_t i0 = mel_offset < nl ? mel_offset : nl;
     const int64_t i1 = (int64_t)mel_offset + T2 < nl ? (int64_t)mel_offset + T2 : nl;
-    const float *p = mel + (int64_t)b * mel_stride;
+    const float *p = mel + (int64_t)clip * mel_stride;
     uint16_t *o = xconv + (int64_t)b * tot;
     float *o32 = xconv32 ? xconv32 + (int64_t)b * tot : nullptr;  // f32 models: conv1 input unrounded
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (int64_t)gridDim.x * blockDim.x) {
@@ -300,11 +305,12 @@ hipError_t launch_mel_norm(hipStream_t s, float *mel, int64_t mel_stride, int n_
 
 hipError_t launch_mel_window(hipStream_t s, const float *mel, int64_t mel_stride, int n_mel, const int64_t *n_len,
                              int mel_offset, int T2, int Cp, uint16_t *xconv, int n_clips,
-                             float *xconv32, uint16_t *g1, int n) {
+                             float *xconv32, uint16_t *g1, int n, const int32_t *src, const int32_t *off) {
+    if ((src == nullptr) != (off == nullptr)) return hipErrorInvalidValue;
     const int64_t tot = (int64_t)(T2 + 2) * Cp;
     dim3 grid(cdiv(tot, 1024) < 512 ? cdiv(tot, 1024) : 512, n_clips);
-    hipLaunchKernelGGL(k_mel_window, grid, dim3(256), 0, s, mel, mel_stride, n_mel, n_len, mel_offset, T2, Cp, xconv, xconv32,
-                       g1, n);
+    hipLaunchKernelGGL(k_mel_window, grid, dim3(256), 0, s, mel, mel_stride, n_mel, n_len, mel_offset, src, off, T2, Cp, xconv,
+                       xconv32, g1, n);
     return hipGetLastError();
 }
 
@@ -2632,11 +2638,21 @@ __device__ __forceinline__ unsigned long long ts_key(float v, int id) {
 }
 __device__ __forceinline__ int ts_key_id(unsigned long long k) { return (int)(0xffffffffu - (uint32_t)(k & 0xffffffffu)); }
 
+// One workgroup per decoder row b: logits row b, tok_out[b], records
+// rec[b * max_rec + t].  done[b] is set once row b has sampled EOT; from then
+// on the row records nothing and feeds EOT (the rows of a step share one
+// position, so a finished row keeps stepping until the host ends the round).
 __global__ __launch_bounds__(1024) void k_ts_sample(TsArgs a) {
     const int pos = a.st->pos;
     if (pos < a.feed_len) return;  // still feeding the prompt
     const int t = pos - a.feed_len;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int b = blockIdx.x;
+    if (a.done[b]) {  // (uniform over the workgroup; set by a previous launch)
+        if (tid == 0) a.tok_out[b] = a.eot;
+        return;
+    }
+    a.logits += (size_t)b * a.V;
     __shared__ float smax[16];
     __shared__ double ssum[16], sts[16];
     __shared__ unsigned long long sk[3][16];
@@ -2689,7 +2705,8 @@ __global__ __launch_bounds__(1024) void k_ts_sample(TsArgs a) {
     if (t == 0) id = ts_key_id(k_ts1);
     else if (sum_ts > p_maxtx) id = id_ts;
     else id = ts_key_id(k_all);
-    a.tok_out[0] = id;
+    a.tok_out[b] = id;
+    if (id == a.eot) a.done[b] = 1;
     if (t < a.max_rec) {
         TsRec r;
         r.id = id;
@@ -2698,13 +2715,13 @@ __global__ __launch_bounds__(1024) void k_ts_sample(TsArgs a) {
         r.pt = (float)(p_maxts / (sum_ts + 1e-10));
         r.ptsum = (float)sum_ts;
         r.pad = 0;
-        a.rec[t] = r;
+        a.rec[(size_t)b * a.max_rec + t] = r;
     }
 }
 
 hipError_t launch_ts_sample(hipStream_t s, const TsArgs &a) {
-    if (a.V < a.beg + 2) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_ts_sample, dim3(1), dim3(1024), 0, s, a);
+    if (a.V < a.beg + 2 || a.B < 1 || a.B > DEC_ROWS || !a.done) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ts_sample, dim3(a.B), dim3(1024), 0, s, a);
     return hipGetLastError();
 }
 

@@ -64,6 +64,8 @@ EXPORTS = (
     "wmi_lang_index", "wmi_lang_code", "wmi_lang_count", "wmi_set_language", "wmi_set_task", "wmi_detect_language",
     "wmi_get_language",
     "wmi_decode_timestamps", "wmi_transcribe", "wmi_get_segment", "wmi_get_segment_tokens",
+    "wmi_set_no_context", "wmi_decode_timestamps_batch", "wmi_transcribe_batch", "wmi_get_segment_of",
+    "wmi_get_segment_tokens_of",
     "wmi_pcm_to_mel", "wmi_pcm_to_mel_batch", "wmi_encode", "wmi_decode_greedy", "wmi_decode_logits",
     "wmi_decode_beam", "wmi_full", "wmi_stage_pcm", "wmi_run_staged", "wmi_run_staged_beam", "wmi_get_tokens", "wmi_get_timings", "wmi_sync",
     "wmi_get_mel", "wmi_get_checksums", "wmi_get_encoder_out", "wmi_get_cross_kv", "wmi_bench_kernel", "wmi_decode_alg_bytes",
@@ -142,6 +144,12 @@ def lib():
         L.wmi_get_segment.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, sz,
                                       C.POINTER(sz)]
         L.wmi_get_segment_tokens.argtypes = [vp, C.c_int, vp, sz, C.POINTER(i32)]
+        L.wmi_set_no_context.argtypes = [vp, C.c_int]
+        L.wmi_decode_timestamps_batch.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
+        L.wmi_transcribe_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_int, vp]
+        L.wmi_get_segment_of.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p,
+                                         sz, C.POINTER(sz)]
+        L.wmi_get_segment_tokens_of.argtypes = [vp, C.c_int, C.c_int, vp, sz, C.POINTER(i32)]
         L.wmi_pcm_to_mel.argtypes = [vp, vp, sz]
         L.wmi_pcm_to_mel_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]
         L.wmi_stage_pcm.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]
@@ -366,6 +374,50 @@ class WhisperContext:
             segs.append({"t0": t0.value, "t1": t1.value, "text": buf.raw[:ln.value],
                          "tokens": [toks[k].as_dict() for k in range(nt.value)]})
         return segs
+
+    def set_no_context(self, on: bool = True) -> None:
+        """Windows of transcribe() decode without the earlier windows' text
+        (whisper.cpp no_context); transcribe_batch() always does."""
+        _raise(lib().wmi_set_no_context(self._h, int(bool(on))), self._h)
+
+    def decode_timestamps_batch(self, prompt, max_tokens: int):
+        """One timestamp window of every encoded clip after the shared prompt,
+        up to 8 clips per decoder step: per clip [WhisperTokenData dict]."""
+        prompt = np.ascontiguousarray(prompt, dtype=np.int32)
+        out = (TokenData * (max(1, self.n_clips) * max_tokens))()
+        n = np.zeros(max(1, self.n_clips), np.int32)
+        _raise(lib().wmi_decode_timestamps_batch(self._h, _ptr(prompt), prompt.size, max_tokens, out, _ptr(n)),
+               self._h)
+        return [[out[c * max_tokens + i].as_dict() for i in range(n[c])] for c in range(self.n_clips)]
+
+    def segments_of(self, clip: int, n_segments: int):
+        """Segments of recording `clip` of the last transcribe_batch."""
+        segs = []
+        for i in range(n_segments):
+            t0, t1, ln = C.c_int64(), C.c_int64(), C.c_size_t()
+            lib().wmi_get_segment_of(self._h, clip, i, C.byref(t0), C.byref(t1), None, 0, C.byref(ln))
+            buf = C.create_string_buffer(max(1, ln.value))
+            _raise(lib().wmi_get_segment_of(self._h, clip, i, C.byref(t0), C.byref(t1), buf, ln.value, C.byref(ln)),
+                   self._h)
+            nt = C.c_int32()
+            lib().wmi_get_segment_tokens_of(self._h, clip, i, None, 0, C.byref(nt))
+            toks = (TokenData * max(1, nt.value))()
+            _raise(lib().wmi_get_segment_tokens_of(self._h, clip, i, toks, nt.value, C.byref(nt)), self._h)
+            segs.append({"t0": t0.value, "t1": t1.value, "text": buf.raw[:ln.value],
+                         "tokens": [toks[k].as_dict() for k in range(nt.value)]})
+        return segs
+
+    def transcribe_batch(self, clips, max_tokens: int = 220):
+        """transcribe() of several recordings (any lengths, at most max_clips)
+        with up to 8 of them per decoder step, every window without earlier
+        text: per recording the list transcribe() returns."""
+        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        ptrs = (C.c_void_p * max(1, len(clips)))(*[c.ctypes.data for c in clips])
+        ns = (C.c_size_t * max(1, len(clips)))(*[c.size for c in clips])
+        nseg = np.zeros(max(1, len(clips)), np.int32)
+        _raise(lib().wmi_transcribe_batch(self._h, len(clips), ptrs, ns, max_tokens, _ptr(nseg)), self._h)
+        self.n_clips = len(clips)
+        return [self.segments_of(c, int(nseg[c])) for c in range(len(clips))]
 
     # --- pipeline ---------------------------------------------------------
     def pcm_to_mel_batch(self, clips) -> None:
