@@ -241,6 +241,27 @@ int wmi_get_segment_tokens(const wmi_context *ctx, int i, wmi_token_data *out, s
  * Default 0.  Holds until changed. */
 int wmi_set_no_context(wmi_context *ctx, int no_context);
 
+/* ---- beam search in timestamped decoding ------------------------------- */
+
+/* wmi_decode_timestamps with beam search: K = beam_size (1..8) hypotheses of
+ * encoded clip 0; out = the chosen hypothesis' tokens, *score (optional) its
+ * summed log-probability under the masked distributions.  Every hypothesis
+ * row takes the timestamp rule of wmi_decode_timestamps on its own logits
+ * (first token: ids > beg; then the timestamp ids when their probabilities
+ * sum above the most probable text token, else every id but sot / solm /
+ * not), contributes its K + 1 most probable allowed ids renormalised over
+ * that set, and the candidates are ranked, finished and chosen as by
+ * wmi_decode_beam (best score / length).  At beam_size 1 the ids and tids
+ * are those of wmi_decode_timestamps.  out[max_tokens]. */
+int wmi_decode_timestamps_beam(wmi_context *ctx, int beam_size, const int32_t *prompt, int n_prompt,
+                               int max_tokens, wmi_token_data *out, int32_t *n_out, double *score);
+/* Beam size of wmi_transcribe's windows; default 1 = the greedy sampler,
+ * exactly as before.  Holds until changed.  Outside [1, 8]:
+ * WMI_E_INVALID_ARG.  wmi_transcribe_batch with a beam size above 1 set is
+ * WMI_E_UNSUPPORTED (8 recordings x K hypotheses do not fit the 8 decoder
+ * rows); wmi_decode_timestamps and wmi_decode_timestamps_batch ignore it. */
+int wmi_set_beam_size(wmi_context *ctx, int beam_size);
+
 /* ---- batched timestamped transcription -------------------------------- */
 
 /* wmi_decode_timestamps for every encoded clip at once: one window per clip
@@ -342,7 +363,10 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * +inf with WMI_GELU_CALC=0), 19 = the prompt of the last timestamp window
  * (wmi_transcribe / wmi_decode_timestamps; int32, host copy: the first
  * bytes / 4 tokens, entries past its length are -1; a batched window's rows
- * follow each other, [rows][n_prompt]). */
+ * follow each other, [rows][n_prompt], as do the K hypothesis rows of a beam
+ * window), 20 = the windows and the decoder steps of the last wmi_transcribe
+ * (int64 [2], host).  13 to 15 also hold the last wmi_decode_timestamps_beam
+ * window. */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

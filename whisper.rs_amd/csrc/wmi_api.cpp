@@ -225,6 +225,12 @@ struct wmi_context {
     int32_t *dts_tok = nullptr; // [8] token the sampler chose for each row's next step
     int32_t *dts_done = nullptr;// [8] row sampled EOT (same allocation, behind dts_tok)
     TsRec *dts_rec = nullptr;   // [8][n_text_ctx] per row and generated token
+    // beam search under the timestamp rule (wmi_decode_timestamps_beam, wmi_set_beam_size)
+    TsBeamPart *d_tsb_parts = nullptr;  // [BEAM_MAX][BEAM_NS]
+    TsRec *d_tsb_rec = nullptr; // [n_text_ctx + 1][BEAM_MAX]: per (step, slot), then per finished hypothesis
+    int beam_size = 1;          // wmi_set_beam_size: hypotheses of a wmi_transcribe window (1: the greedy sampler)
+    int last_run_steps = 0;     // decoder steps the last timestamp window enqueued (early stop included)
+    int64_t tr_count[2] = {0, 0};  // windows and decoder steps of the last wmi_transcribe (debug read 20)
     int32_t *d_win = nullptr;   // batched transcription: source recording [8], then mel offset [8] of each encoder slot
     bool no_context = false;    // wmi_set_no_context: windows of wmi_transcribe take no earlier text
     struct Segment { int64_t t0, t1; int first, count; std::string text; };
@@ -1365,7 +1371,8 @@ int run_encode(wmi_context *ctx, int mel_offset, int slots = 0, const int32_t *s
 // enqueues steps takes the run's descriptor; the context holds no decode mode.
 //   RUN_GREEDY  rows are consecutive clips; the argmax of a step feeds the next
 //               and is recorded in dtokens ([.][out_stride])
-//   RUN_BEAM    rows are the K hypotheses of clip b0; k_beam_step follows a step
+//   RUN_BEAM    rows are the K hypotheses of clip b0; k_beam_step follows a step,
+//               or with ts_beam the step under the timestamp rule (k_tsbeam_*)
 //   RUN_TS      rows are consecutive clips, as greedy; the timestamp sampler
 //               (k_ts_sample) follows a step and picks each row's next token
 //   RUN_FORCED  the feed supplies every token (teacher forcing, the [SOT] step
@@ -1378,6 +1385,7 @@ struct DecRun {
     int feed_len = 1, feed_stride = 1, suppress_eot = 0, out_stride = 1;
     int K = 0, max_tokens = 0;    // beam width and token limit (RUN_BEAM)
     int mk = 512;                 // key capacity of the self-attention launch being enqueued (run_dec_steps)
+    int ts_beam = 0;              // RUN_BEAM: the hypotheses follow the timestamp rule and keep token records
 };
 
 // beam-step kernel arguments of a beam run
@@ -1389,6 +1397,17 @@ BeamArgs beam_args(wmi_context *ctx, const DecRun &run) {
     ba.st = ctx->dstate; ba.parts = ctx->dbparts; ba.bs = ctx->dbstate; ba.kv_src = ctx->dkvsrc;
     ba.hist_parent = ctx->dhist_par; ba.hist_tok = ctx->dhist_tok;
     return ba;
+}
+
+// ... and of one under the timestamp rule
+TsBeamArgs tsbeam_args(wmi_context *ctx, const DecRun &run) {
+    TsBeamArgs ta{};
+    ta.b = beam_args(ctx, run);
+    ta.b.parts = nullptr;
+    ta.beg = ctx->sp.beg; ta.sot = ctx->sp.sot; ta.solm = ctx->sp.solm; ta.not_ = ctx->sp.not_;
+    ta.tparts = ctx->d_tsb_parts; ta.hist_rec = ctx->d_tsb_rec;
+    ta.fin_rec = ctx->d_tsb_rec + (size_t)ctx->hp.n_text_ctx * BEAM_MAX;
+    return ta;
 }
 
 // timestamp-sampler arguments of a timestamp run
@@ -1405,7 +1424,8 @@ TsArgs ts_args(wmi_context *ctx, const DecRun &run) {
 // (after the last kernel of a chain step, after a one-step persistent launch)
 int enqueue_step_tail(wmi_context *ctx, const DecRun &run) {
     if (run.kind == RUN_TS) HIPCHK(ctx, launch_ts_sample(ctx->stream, ts_args(ctx, run)));
-    if (run.kind == RUN_BEAM) HIPCHK(ctx, launch_beam_step(ctx->stream, beam_args(ctx, run)));
+    if (run.kind == RUN_BEAM && run.ts_beam) HIPCHK(ctx, launch_tsbeam_step(ctx->stream, tsbeam_args(ctx, run)));
+    else if (run.kind == RUN_BEAM) HIPCHK(ctx, launch_beam_step(ctx->stream, beam_args(ctx, run)));
     return WMI_OK;
 }
 
@@ -1622,7 +1642,7 @@ int run_dec_steps(wmi_context *ctx, const DecRun &run0, int pos0, int steps) {
             // (a forced step enqueues what a greedy step does: they share graphs)
             snprintf(key, sizeof key, "%d/%d/%d/%d/%d/%d/%d/%d/%p/%p/%d/%d/%d/%d/%d", run.b0, run.B, run.feed_len,
                      run.feed_stride, run.suppress_eot, run.out_stride, ctx->enc_T, ctx->enc_clips, (void *)ctx->dfeed,
-                     (void *)ctx->dtokens, run.K, run.max_tokens, mk, (int)(run.kind == RUN_TS), reps);
+                     (void *)ctx->dtokens, run.K, run.max_tokens, mk, run.kind == RUN_TS ? 1 : run.ts_beam ? 2 : 0, reps);
             auto it = ctx->graphs.find(key);
             if (it == ctx->graphs.end()) {
                 if (ctx->graphs.size() >= 32) ctx->clear_graphs();
@@ -2164,6 +2184,7 @@ int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &fee
             rc = advance_run(ctx, run, gr, done, chunk);
             if (rc) return rc;
             done += chunk;
+            ctx->last_run_steps = done;
             have = done - np + 1;  // records written so far (per row that has not met EOT)
             if (have <= 0 || done >= total) continue;
             int32_t dn[DEC_ROWS];
@@ -2263,6 +2284,9 @@ std::vector<int32_t> ts_init_prompt(const wmi_context *ctx, int lang) {
     return init;
 }
 
+int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, int K, int max_tokens,
+                       std::vector<TsRec> *out, double *score);
+
 // whisper_full (whisper.cpp-1.0.3, the loop the reference's WhisperSegment /
 // WhisperTokenData / prompt_past fields belong to, main.rs:317-331, 353-362,
 // 599-604): windows of 2 * n_ctx mel frames from `seek`, prompt = [prev] +
@@ -2284,6 +2308,7 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
     std::vector<int32_t> init;
     std::vector<int32_t> past;
     ctx->results.assign(1, {});
+    ctx->tr_count[0] = ctx->tr_count[1] = 0;
     for (int64_t seek = 0; seek < n_len;) {
         int rc = run_encode(ctx, (int)seek);
         if (rc) return rc;
@@ -2306,8 +2331,11 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
         }
         prompt.insert(prompt.end(), init.begin(), init.end());
         std::vector<TsRec> toks;
-        rc = run_ts_window(ctx, 0, prompt, n_max, &toks);
+        rc = ctx->beam_size > 1 ? run_ts_beam_window(ctx, 0, prompt, ctx->beam_size, n_max, &toks, nullptr)
+                                : run_ts_window(ctx, 0, prompt, n_max, &toks);
         if (rc) return rc;
+        ++ctx->tr_count[0];
+        ctx->tr_count[1] += ctx->last_run_steps;
         seek += finish_ts_window(ctx, std::move(toks), seek, n_len, window, ctx->results[0],
                                  ctx->no_context ? nullptr : &past);
     }
@@ -2501,6 +2529,106 @@ int run_beam(wmi_context *ctx, int K, int n_gen, int suppress_eot, bool early_st
     return record_lang_used(ctx);
 }
 
+// One timestamped window with beam search: K hypotheses of encoded clip `clip`
+// after `prompt` (every row is fed the same prompt), each step followed by the
+// beam step under the timestamp rule (k_tsbeam_part / k_tsbeam_select).  The
+// hypothesis is chosen as run_beam chooses it; out = its tokens' records, the
+// EOT of a finished one included, *score its summed log-probability.
+int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, int K, int max_tokens,
+                       std::vector<TsRec> *out, double *score) {
+    const wmi_hparams &hp = ctx->hp;
+    const int np = (int)prompt.size();
+    if (ctx->enc_T <= 0 || ctx->enc_clips < 1) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
+    if (K < 1 || K > BEAM_MAX) return set_err(ctx, WMI_E_INVALID_ARG, "beam size %d outside [1, %d]", K, BEAM_MAX);
+    if (clip < 0 || clip >= ctx->enc_clips)
+        return set_err(ctx, WMI_E_INVALID_ARG, "clip %d outside the %d encoded clips", clip, ctx->enc_clips);
+    if (np < 1 || max_tokens < 1 || np + max_tokens > hp.n_text_ctx)
+        return set_err(ctx, WMI_E_INVALID_ARG, "prompt %d + max_tokens %d exceed n_text_ctx %d", np, max_tokens,
+                       hp.n_text_ctx);
+    const size_t n_rec = ((size_t)hp.n_text_ctx + 1) * BEAM_MAX;
+    if (!ctx->d_tsb_parts) {
+        HIPCHK(ctx, hipMalloc(&ctx->d_tsb_parts, (size_t)BEAM_MAX * BEAM_NS * sizeof(TsBeamPart)));
+        HIPCHK(ctx, hipMalloc(&ctx->d_tsb_rec, n_rec * sizeof(TsRec)));
+    }
+    // (a window's prompt holds up to n_text_ctx / 2 earlier tokens: K rows of
+    // it are more than the 64 words of the reset launch, so reset_run copies them)
+    int rc = ensure_decode_buffers(ctx, K * np, 1);
+    if (rc) return rc;
+    std::vector<int32_t> feed;
+    feed.reserve((size_t)K * np);
+    for (int b = 0; b < K; ++b) feed.insert(feed.end(), prompt.begin(), prompt.end());
+    ctx->ts_prompt = feed;
+    BeamState init{};
+    init.n_active = 1;
+    DecRun run{RUN_BEAM, clip, K, np, np, 0, 1, K, max_tokens};
+    run.ts_beam = 1;
+    const int total = np + max_tokens - 1;
+    BeamState bs{};
+    do {
+        const RunGrid gr = run_grid(ctx, run);
+        rc = reset_run(ctx, true, gr.G, gr.Gh, false, feed.data(), K * np);
+        if (rc) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->dbstate, &init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->dkvsrc, ctx->kvsrc_init.data(), ctx->kvsrc_init.size() * 4, hipMemcpyHostToDevice,
+                                   ctx->stream));
+        for (int done = 0; done < total;) {
+            // (the prompt in one chunk, then 16 steps between looks at BeamState::done)
+            const int chunk = std::min(done < np - 1 ? np - 1 - done + 16 : 16, total - done);
+            rc = advance_run(ctx, run, gr, done, chunk);
+            if (rc) return rc;
+            done += chunk;
+            ctx->last_run_steps = done;
+            if (done >= total) break;
+            int32_t fin = 0;
+            HIPCHK(ctx, hipMemcpyAsync(&fin, &ctx->dbstate->done, 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            if (fin) break;
+        }
+        HIPCHK(ctx, hipMemcpyAsync(&bs, ctx->dbstate, sizeof bs, hipMemcpyDeviceToHost, ctx->stream));
+        rc = finish_run(ctx);
+    } while (rc == RERUN_ON_CHAIN);
+    if (rc) return rc;
+    const int ns = bs.n_steps;
+    if (ns < 1 || ns > max_tokens) return set_err(ctx, WMI_E_HIP, "beam search produced %d steps", ns);
+    std::vector<int32_t> hpar((size_t)ns * BEAM_MAX);
+    std::vector<TsRec> hrec((size_t)ns * BEAM_MAX), frec(BEAM_MAX);
+    HIPCHK(ctx, hipMemcpy(hpar.data(), ctx->dhist_par, hpar.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(hrec.data(), ctx->d_tsb_rec, hrec.size() * sizeof(TsRec), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(frec.data(), ctx->d_tsb_rec + (size_t)hp.n_text_ctx * BEAM_MAX, frec.size() * sizeof(TsRec),
+                          hipMemcpyDeviceToHost));
+    auto backtrack = [&](int tlast, int slot) {
+        std::vector<TsRec> seq((size_t)tlast + 1);
+        for (int t = tlast; t >= 0; --t) {
+            seq[t] = hrec[(size_t)t * BEAM_MAX + slot];
+            slot = hpar[(size_t)t * BEAM_MAX + slot];
+        }
+        return seq;
+    };
+    // finished hypotheses in order, then active ones in slot order, first K
+    double best = -INFINITY;
+    int best_src = -1, best_i = 0, considered = 0;
+    for (int f = 0; f < bs.n_fin && considered < K; ++f, ++considered) {
+        const double sc = bs.fin_score[f] / (double)(bs.fin_t[f] > 0 ? bs.fin_t[f] : 1);
+        if (sc > best) { best = sc; best_src = 0; best_i = f; }
+    }
+    for (int a = 0; a < bs.n_active && considered < K; ++a, ++considered) {
+        const double sc = bs.score[a] / (double)ns;
+        if (sc > best) { best = sc; best_src = 1; best_i = a; }
+    }
+    if (best_src < 0) return set_err(ctx, WMI_E_HIP, "beam search left no hypothesis");
+    if (best_src == 0) {
+        const int t = bs.fin_t[best_i];
+        out->clear();
+        if (t > 0) *out = backtrack(t - 1, bs.fin_beam[best_i]);
+        out->push_back(frec[best_i]);
+        if (score) *score = bs.fin_score[best_i];
+    } else {
+        *out = backtrack(ns - 1, best_i);
+        if (score) *score = bs.score[best_i];
+    }
+    return WMI_OK;
+}
+
 }  // namespace
 
 // An exception (host allocation failure on a hostile file, an internal
@@ -2657,6 +2785,8 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->d_lang) (void)hipFree(ctx->d_lang);
     if (ctx->dts_tok) (void)hipFree(ctx->dts_tok);
     if (ctx->dts_rec) (void)hipFree(ctx->dts_rec);
+    if (ctx->d_tsb_parts) (void)hipFree(ctx->d_tsb_parts);
+    if (ctx->d_tsb_rec) (void)hipFree(ctx->d_tsb_rec);
     if (ctx->d_win) (void)hipFree(ctx->d_win);
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -2854,6 +2984,23 @@ static int wmi_decode_timestamps_impl(wmi_context *ctx, const int32_t *prompt, i
     return WMI_OK;
 }
 
+static int wmi_decode_timestamps_beam_impl(wmi_context *ctx, int beam_size, const int32_t *prompt, int n_prompt,
+                                           int max_tokens, wmi_token_data *out, int32_t *n_out, double *score) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (!prompt || n_prompt < 1 || max_tokens < 1 || !out || !n_out)
+        return set_err(ctx, WMI_E_INVALID_ARG, "null prompt / out / n_out, or n_prompt %d / max_tokens %d below 1", n_prompt,
+                       max_tokens);
+    for (int i = 0; i < n_prompt; ++i)
+        if (prompt[i] < 0 || prompt[i] >= ctx->hp.n_vocab) return set_err(ctx, WMI_E_INVALID_ARG, "token id %d", prompt[i]);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<TsRec> rec;
+    int rc = run_ts_beam_window(ctx, 0, std::vector<int32_t>(prompt, prompt + n_prompt), beam_size, max_tokens, &rec, score);
+    if (rc) return rc;
+    for (size_t i = 0; i < rec.size(); ++i) to_token_data(rec[i], out + i);
+    *n_out = (int32_t)rec.size();
+    return WMI_OK;
+}
+
 static int wmi_transcribe_impl(wmi_context *ctx, const float *pcm, size_t n_samples, int max_tokens, int32_t *n_segments) {
     if (!valid(ctx) || (!pcm && n_samples) || max_tokens < 1 || !n_segments) return WMI_E_INVALID_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2900,6 +3047,9 @@ static int wmi_transcribe_batch_impl(wmi_context *ctx, int n_clips, const float 
         return set_err(ctx, WMI_E_INVALID_ARG, "n_clips %d outside [1, max_clips=%d]", n_clips, ctx->max_clips);
     if (!pcm || !n_samples || !n_segments) return set_err(ctx, WMI_E_INVALID_ARG, "null pcm / n_samples / n_segments");
     if (max_tokens < 1) return set_err(ctx, WMI_E_INVALID_ARG, "max_tokens %d below 1", max_tokens);
+    if (ctx->beam_size > 1)  // (8 recordings x K hypotheses do not fit the 8 decoder rows; no silent greedy)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "wmi_transcribe_batch decodes greedily only: beam size %d is set "
+                       "(wmi_set_beam_size(ctx, 1), or wmi_transcribe per recording)", ctx->beam_size);
     for (int c = 0; c < n_clips; ++c)  // (wmi_set_language / wmi_set_task refuse these; checked where they are used)
         if (ctx->n_lang == 0 && (ctx->lang_set[c] != 0 || ctx->task != WMI_TASK_TRANSCRIBE))
             return set_err(ctx, WMI_E_INVALID_ARG, "language %d / task %d on an English-only model (clip %d)",
@@ -2917,6 +3067,14 @@ int wmi_set_no_context(wmi_context *ctx, int no_context) {
     if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
     if (no_context != 0 && no_context != 1) return set_err(ctx, WMI_E_INVALID_ARG, "no_context %d is neither 0 nor 1", no_context);
     ctx->no_context = no_context != 0;
+    return WMI_OK;
+}
+
+int wmi_set_beam_size(wmi_context *ctx, int beam_size) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    if (beam_size < 1 || beam_size > BEAM_MAX)
+        return set_err(ctx, WMI_E_INVALID_ARG, "beam size %d outside [1, %d]", beam_size, BEAM_MAX);
+    ctx->beam_size = beam_size;
     return WMI_OK;
 }
 
@@ -3372,6 +3530,10 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
             memcpy(out, ctx->ts_prompt.data(), std::min(have19, bytes));
             return WMI_OK;
         }
+        case 20: {  // host: windows and decoder steps of the last wmi_transcribe, int64 [2]
+            memcpy(out, ctx->tr_count, std::min(sizeof ctx->tr_count, bytes));
+            return WMI_OK;
+        }
         case 11: {  // host: decodes re-run on the kernel chain after a persistent exchange timeout
             const int32_t v = ctx->n_fallbacks;
             memcpy(out, &v, std::min(sizeof v, bytes));
@@ -3518,6 +3680,13 @@ int wmi_tokens_to_text(const wmi_context *ctx, const int32_t *ids, int n, char *
 int wmi_decode_timestamps(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens, wmi_token_data *out,
                           int32_t *n_out) {
     return guarded(ctx, [&] { return wmi_decode_timestamps_impl(ctx, prompt, n_prompt, max_tokens, out, n_out); });
+}
+
+int wmi_decode_timestamps_beam(wmi_context *ctx, int beam_size, const int32_t *prompt, int n_prompt, int max_tokens,
+                               wmi_token_data *out, int32_t *n_out, double *score) {
+    return guarded(ctx, [&] {
+        return wmi_decode_timestamps_beam_impl(ctx, beam_size, prompt, n_prompt, max_tokens, out, n_out, score);
+    });
 }
 
 int wmi_transcribe(wmi_context *ctx, const float *pcm, size_t n_samples, int max_tokens, int32_t *n_segments) {

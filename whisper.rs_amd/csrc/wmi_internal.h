@@ -288,6 +288,32 @@ struct TsArgs {
     int32_t *done;           // [B] != 0 once row b sampled EOT: no more records, feeds EOT
 };
 hipError_t launch_ts_sample(hipStream_t s, const TsArgs &a);
+
+// ---- beam search under the timestamp rule (DESIGN.md "Beam search in
+// timestamped decoding"): the rule of k_ts_sample decides each hypothesis
+// row's allowed set, the beam step of k_beam_topk / k_beam_select ranks the
+// rows' top-(K+1) of their sets ------------------------------------------------
+struct TsBeamPart {          // one vocabulary split of one row
+    float m_all, m_tx;       // max over the split's ids; over its ids < beg (-inf: none)
+    float m_ts, m_tl;        // max over its ids >= beg; over the set of the timestamp list
+    int32_t id_ts, pad;      // argmax over its ids >= beg, ties to the lowest id (-1: none)
+    double sum_all;          // sum exp(l - m_all) over the split
+    double sum_ts;           // sum exp(l - m_ts) over ids >= beg
+    double sum_tl;           // sum exp(l - m_tl) over the set of the timestamp list
+    double sum_a;            // sum exp(l - a_val[0]) over ids other than sot / solm / not
+    float ts_val[BEAM_TK];   // top-(K+1) of ids >= beg (first generated token: ids > beg)
+    int32_t ts_id[BEAM_TK];
+    float a_val[BEAM_TK];    // top-(K+1) of ids other than sot / solm / not (not at the first token)
+    int32_t a_id[BEAM_TK];
+};
+struct TsBeamArgs {
+    BeamArgs b;              // (parts unused; suppress_id -1)
+    int beg, sot, solm, not_;
+    TsBeamPart *tparts;      // [K][BEAM_NS]
+    TsRec *hist_rec;         // [tctx][BEAM_MAX] record of the token slot s took at step t
+    TsRec *fin_rec;          // [BEAM_MAX] record of finished hypothesis f's EOT
+};
+hipError_t launch_tsbeam_step(hipStream_t s, const TsBeamArgs &a);
 // WMI_LOGITS_ALL on the kernel chain: logits [rows][V] -> all + (pos - 1) * slab
 // (after the step's logits GEMV; positions outside [0, tctx) are dropped)
 hipError_t launch_logits_capture(hipStream_t s, const float *logits, float *all, const DecState *st, int rows, int V,

@@ -65,7 +65,7 @@ EXPORTS = (
     "wmi_get_language",
     "wmi_decode_timestamps", "wmi_transcribe", "wmi_get_segment", "wmi_get_segment_tokens",
     "wmi_set_no_context", "wmi_decode_timestamps_batch", "wmi_transcribe_batch", "wmi_get_segment_of",
-    "wmi_get_segment_tokens_of",
+    "wmi_get_segment_tokens_of", "wmi_decode_timestamps_beam", "wmi_set_beam_size",
     "wmi_pcm_to_mel", "wmi_pcm_to_mel_batch", "wmi_encode", "wmi_decode_greedy", "wmi_decode_logits",
     "wmi_decode_beam", "wmi_full", "wmi_stage_pcm", "wmi_run_staged", "wmi_run_staged_beam", "wmi_get_tokens", "wmi_get_timings", "wmi_sync",
     "wmi_get_mel", "wmi_get_checksums", "wmi_get_encoder_out", "wmi_get_cross_kv", "wmi_bench_kernel", "wmi_decode_alg_bytes",
@@ -145,7 +145,10 @@ def lib():
                                       C.POINTER(sz)]
         L.wmi_get_segment_tokens.argtypes = [vp, C.c_int, vp, sz, C.POINTER(i32)]
         L.wmi_set_no_context.argtypes = [vp, C.c_int]
-        L.wmi_decode_timestamps_batch.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
+        L.wmi_decode_timestamps_beam.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.POINTER(i32),
+                                                 C.POINTER(C.c_double)]
+        L.wmi_set_beam_size.argtypes = [vp, C.c_int]
+        L.wmi_decode_timestamps_batch.argtypes =[vp, vp, C.c_int, C.c_int, vp, vp]
         L.wmi_transcribe_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_int, vp]
         L.wmi_get_segment_of.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p,
                                          sz, C.POINTER(sz)]
@@ -379,6 +382,23 @@ class WhisperContext:
         """Windows of transcribe() decode without the earlier windows' text
         (whisper.cpp no_context); transcribe_batch() always does."""
         _raise(lib().wmi_set_no_context(self._h, int(bool(on))), self._h)
+
+    def decode_timestamps_beam(self, beam_size: int, prompt, max_tokens: int):
+        """decode_timestamps() with beam search over beam_size (1..8)
+        hypotheses under the timestamp rule: ([WhisperTokenData dict] of the
+        chosen hypothesis, its summed log-probability)."""
+        prompt = np.ascontiguousarray(prompt, dtype=np.int32)
+        out = (TokenData * max(1, max_tokens))()
+        n = C.c_int32()
+        sc = C.c_double()
+        _raise(lib().wmi_decode_timestamps_beam(self._h, beam_size, _ptr(prompt), prompt.size, max_tokens, out,
+                                                C.byref(n), C.byref(sc)), self._h)
+        return [out[i].as_dict() for i in range(n.value)], sc.value
+
+    def set_beam_size(self, k: int) -> None:
+        """Hypotheses of every transcribe() window (1..8; 1, the default, is
+        the greedy sampler).  transcribe_batch() refuses a size above 1."""
+        _raise(lib().wmi_set_beam_size(self._h, int(k)), self._h)
 
     def decode_timestamps_batch(self, prompt, max_tokens: int):
         """One timestamp window of every encoded clip after the shared prompt,
