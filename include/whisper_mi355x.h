@@ -292,6 +292,63 @@ int wmi_get_segment_of(const wmi_context *ctx, int clip, int i, int64_t *t0, int
                        size_t *len);
 int wmi_get_segment_tokens_of(const wmi_context *ctx, int clip, int i, wmi_token_data *out, size_t cap, int32_t *n);
 
+/* ---- temperature fallback, quality thresholds, no-speech ---------------- */
+
+/* The per-window decode loop of OpenAI's decode_with_fallback / whisper.cpp
+ * 1.2 for wmi_transcribe and wmi_transcribe_batch.  A window is decoded at
+ * T_j = temperature + j * temperature_inc for j = 0, 1, .. while T_j <= 1
+ * (one attempt with temperature_inc 0).  At T = 0 the token is the most
+ * probable allowed one (wmi_decode_timestamps' pick, or the beam window with
+ * wmi_set_beam_size above 1); at T > 0 it is drawn from the allowed set's
+ * distribution softmax(l / T) with u_t = (sm64(key + t) >> 11) * 2^-53, sm64 =
+ * splitmix64 and key = sm64(seed + n), n = the T > 0 attempts the recording
+ * has made before in the call.  Over the window's tokens (EOT included):
+ * avg_logprob = the mean log-probability under the masked distribution at
+ * temperature 1; entropy = that of the id counts over its last 32 tokens.  An
+ * attempt is rejected if the window failed (would skip 100 frames), avg_logprob
+ * < logprob_thold or entropy < entropy_thold; the first accepted attempt, or
+ * the last one, is the window's result.  After attempt 0, no_speech_prob
+ * (P(<|nospeech|>) of the first generated step) > no_speech_thold together
+ * with avg_logprob < logprob_thold skips the window without segments.  A
+ * result of T > 0.5 clears the text context of later windows.
+ * Defaults (also params = NULL): temperature 0, temperature_inc 0,
+ * logprob_thold = entropy_thold = -inf, no_speech_thold = +inf, seed 0 — with
+ * them every call decodes exactly as without this interface (the same
+ * kernels, no window infos).  NaN, temperature outside [0, 1], a negative
+ * increment or one in (0, 0.01) (more than 101 attempts a window):
+ * WMI_E_INVALID_ARG.  A vocabulary above 65536 ids, or one whose sot / solm /
+ * not ids are not below beg (no Whisper vocabulary): WMI_E_UNSUPPORTED.
+ * Holds until changed. */
+typedef struct wmi_fallback_params {
+    float temperature, temperature_inc, logprob_thold, entropy_thold, no_speech_thold;
+    uint64_t seed;
+} wmi_fallback_params;
+int wmi_set_fallback(wmi_context *ctx, const wmi_fallback_params *params);
+/* One window of the encoded clip 0 at one temperature, as attempt ordinal n of
+ * `seed` (the key of the draws; unused at temperature 0, where ids, tids and
+ * records are those of wmi_decode_timestamps).  out[max_tokens];
+ * plog[max_tokens] (optional) each token's log-probability as in avg_logprob;
+ * *p_nosp (optional) the no-speech probability. */
+int wmi_decode_timestamps_sampled(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens,
+                                  float temperature, uint64_t seed, int n, wmi_token_data *out, int32_t *n_out,
+                                  float *plog, float *p_nosp);
+/* Window i of recording `clip` in the last wmi_transcribe /
+ * wmi_transcribe_batch made with fallback parameters other than the defaults
+ * (the count is 0 otherwise): the window's start frame, the attempts made, and
+ * of the attempt that became the result its temperature, avg_logprob and
+ * entropy; the no-speech probability of attempt 0; its segments
+ * [first_segment, first_segment + n_segments) of the recording.
+ * flags: 1 = skipped as silence, 2 = failed (100-frame skip), 4 = every
+ * attempt was rejected, 8 = the text context was reset after it. */
+typedef struct wmi_window_info {
+    int64_t seek;
+    int32_t n_attempts;
+    float temperature, avg_logprob, entropy, no_speech_prob;
+    int32_t flags, first_segment, n_segments;
+} wmi_window_info;
+int wmi_get_window_count(const wmi_context *ctx, int clip, int32_t *n);
+int wmi_get_window_info(const wmi_context *ctx, int clip, int i, wmi_window_info *out);
+
 /* ---- device-resident benchmark path --------------------------------- */
 
 /* Upload n_clips PCM clips to HBM once (untimed). */
@@ -365,8 +422,10 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * bytes / 4 tokens, entries past its length are -1; a batched window's rows
  * follow each other, [rows][n_prompt], as do the K hypothesis rows of a beam
  * window), 20 = the windows and the decoder steps of the last wmi_transcribe
- * (int64 [2], host).  13 to 15 also hold the last wmi_decode_timestamps_beam
- * window. */
+ * (int64 [2], host; every attempt's steps under wmi_set_fallback, and a third
+ * int64: the attempts).  13 to 15 also hold the last wmi_decode_timestamps_beam
+ * window; 13 also the last sampled window (wmi_decode_timestamps_sampled, a
+ * window of wmi_transcribe under wmi_set_fallback; row b in row b). */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

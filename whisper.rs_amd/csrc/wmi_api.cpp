@@ -230,7 +230,13 @@ struct wmi_context {
     TsRec *d_tsb_rec = nullptr; // [n_text_ctx + 1][BEAM_MAX]: per (step, slot), then per finished hypothesis
     int beam_size = 1;          // wmi_set_beam_size: hypotheses of a wmi_transcribe window (1: the greedy sampler)
     int last_run_steps = 0;     // decoder steps the last timestamp window enqueued (early stop included)
-    int64_t tr_count[2] = {0, 0};  // windows and decoder steps of the last wmi_transcribe (debug read 20)
+    int64_t tr_count[3] = {0, 0, 0};  // windows, decoder steps and attempts of the last wmi_transcribe (debug read 20)
+    // temperature fallback (wmi_set_fallback); fb_on: the parameters are not the defaults
+    wmi_fallback_params fb{0.0f, 0.0f, -INFINITY, -INFINITY, INFINITY, 0};
+    bool fb_on = false;
+    SampRow *d_samp_rows = nullptr;  // one allocation: rows [8], p_nosp [8], plog [8][n_text_ctx]
+    float *d_samp_nosp = nullptr, *d_samp_plog = nullptr;
+    std::vector<std::vector<wmi_window_info>> windows;  // per recording of the last transcribe under fb_on
     int32_t *d_win = nullptr;   // batched transcription: source recording [8], then mel offset [8] of each encoder slot
     bool no_context = false;    // wmi_set_no_context: windows of wmi_transcribe take no earlier text
     struct Segment { int64_t t0, t1; int first, count; std::string text; };
@@ -1374,7 +1380,8 @@ int run_encode(wmi_context *ctx, int mel_offset, int slots = 0, const int32_t *s
 //   RUN_BEAM    rows are the K hypotheses of clip b0; k_beam_step follows a step,
 //               or with ts_beam the step under the timestamp rule (k_tsbeam_*)
 //   RUN_TS      rows are consecutive clips, as greedy; the timestamp sampler
-//               (k_ts_sample) follows a step and picks each row's next token
+//               (k_ts_sample) follows a step and picks each row's next token,
+//               or with `sampled` the temperature sampler (k_ts_sample_t)
 //   RUN_FORCED  the feed supplies every token (teacher forcing, the [SOT] step
 //               of language detection): each step's logits stay in dlogits and
 //               nothing is recorded
@@ -1386,6 +1393,8 @@ struct DecRun {
     int K = 0, max_tokens = 0;    // beam width and token limit (RUN_BEAM)
     int mk = 512;                 // key capacity of the self-attention launch being enqueued (run_dec_steps)
     int ts_beam = 0;              // RUN_BEAM: the hypotheses follow the timestamp rule and keep token records
+    int sampled = 0;              // RUN_TS: the temperature sampler (k_ts_sample_t) with the rows' T and keys in d_samp_rows
+    int nosp = 0;                 // RUN_BEAM with ts_beam: the first generated step also yields the no-speech probability
 };
 
 // beam-step kernel arguments of a beam run
@@ -1423,6 +1432,19 @@ TsArgs ts_args(wmi_context *ctx, const DecRun &run) {
 // the kernel that follows a step's logits: the run kind's sampler, if any
 // (after the last kernel of a chain step, after a one-step persistent launch)
 int enqueue_step_tail(wmi_context *ctx, const DecRun &run) {
+    if (run.kind == RUN_TS && run.sampled) {
+        TsSampArgs sa{};
+        sa.t = ts_args(ctx, run);
+        sa.rows = ctx->d_samp_rows; sa.plog = ctx->d_samp_plog; sa.p_nosp = ctx->d_samp_nosp;
+        HIPCHK(ctx, launch_ts_sample_t(ctx->stream, sa));
+        return WMI_OK;
+    }
+    if (run.kind == RUN_BEAM && run.ts_beam && run.nosp) {
+        NoSpeechArgs na{};
+        na.logits = ctx->dlogits; na.V = ctx->hp.n_vocab; na.solm = ctx->sp.solm; na.feed_len = run.feed_len;
+        na.st = ctx->dstate; na.p_nosp = ctx->d_samp_nosp;
+        HIPCHK(ctx, launch_no_speech(ctx->stream, na));
+    }
     if (run.kind == RUN_TS) HIPCHK(ctx, launch_ts_sample(ctx->stream, ts_args(ctx, run)));
     if (run.kind == RUN_BEAM && run.ts_beam) HIPCHK(ctx, launch_tsbeam_step(ctx->stream, tsbeam_args(ctx, run)));
     else if (run.kind == RUN_BEAM) HIPCHK(ctx, launch_beam_step(ctx->stream, beam_args(ctx, run)));
@@ -1556,7 +1578,7 @@ int enqueue_dec_step(wmi_context *ctx, const DecRun &run) {
     // WMI_LOGITS_ALL: what the persistent launches keep — a greedy run's rows
     // b0.., a beam step's [K][V] — so a debug read 13 of a chain decode holds
     // the decode's logits, not the buffer's zeros
-    if (ctx->d_lgall && (run.kind == RUN_GREEDY || beam) && (beam ? 0 : b0) + B <= ctx->lg_rows)
+    if (ctx->d_lgall && (run.kind == RUN_GREEDY || beam || (ts && run.sampled)) && (beam ? 0 : b0) + B <= ctx->lg_rows)
         HIPCHK(ctx, launch_logits_capture(s, ctx->dlogits, ctx->d_lgall + (beam ? 0 : (size_t)b0 * hp.n_vocab), ctx->dstate,
                                           B, hp.n_vocab, (int64_t)ctx->lg_rows * hp.n_vocab, hp.n_text_ctx));
     return enqueue_step_tail(ctx, run);
@@ -1642,7 +1664,8 @@ int run_dec_steps(wmi_context *ctx, const DecRun &run0, int pos0, int steps) {
             // (a forced step enqueues what a greedy step does: they share graphs)
             snprintf(key, sizeof key, "%d/%d/%d/%d/%d/%d/%d/%d/%p/%p/%d/%d/%d/%d/%d", run.b0, run.B, run.feed_len,
                      run.feed_stride, run.suppress_eot, run.out_stride, ctx->enc_T, ctx->enc_clips, (void *)ctx->dfeed,
-                     (void *)ctx->dtokens, run.K, run.max_tokens, mk, run.kind == RUN_TS ? 1 : run.ts_beam ? 2 : 0, reps);
+                     (void *)ctx->dtokens, run.K, run.max_tokens, mk,
+                     run.kind == RUN_TS ? (run.sampled ? 3 : 1) : run.ts_beam ? (run.nosp ? 4 : 2) : 0, reps);
             auto it = ctx->graphs.find(key);
             if (it == ctx->graphs.end()) {
                 if (ctx->graphs.size() >= 32) ctx->clear_graphs();
@@ -1887,6 +1910,9 @@ int advance_run(wmi_context *ctx, const DecRun &run, RunGrid gr, int pos0, int s
             if (run.kind == RUN_BEAM && ctx->d_lgall && s_all < hp.n_text_ctx)  // WMI_LOGITS_ALL: this step's [K][V]
                 HIPCHK(ctx, hipMemcpyAsync(ctx->d_lgall + (size_t)s_all * ctx->lg_rows * hp.n_vocab, ctx->dlogits,
                                            (size_t)run.K * hp.n_vocab * 4, hipMemcpyDeviceToDevice, ctx->stream));
+            if (run.kind == RUN_TS && run.sampled && ctx->d_lgall && s_all < hp.n_text_ctx && run.b0 + run.B <= ctx->lg_rows)
+                HIPCHK(ctx, hipMemcpyAsync(ctx->d_lgall + ((size_t)s_all * ctx->lg_rows + run.b0) * hp.n_vocab, ctx->dlogits,
+                                           (size_t)run.B * hp.n_vocab * 4, hipMemcpyDeviceToDevice, ctx->stream));
             int rc = enqueue_step_tail(ctx, run);
             if (rc) return rc;
         }
@@ -2152,8 +2178,48 @@ bool valid(const wmi_context *ctx) { return ctx != nullptr && ctx->d_model != nu
 // device timestamp sampler (k_ts_sample).  A row stops at its EOT; the run
 // ends when every row has (polled through the rows' done words every 16
 // steps) or at max_tokens.  out[b] = row b's records up to and including EOT.
+//
+// With `samp` the run is a sampled one (k_ts_sample_t): row b decodes at
+// temperature samp->T[b] with the draws of stream key samp->key[b], and the
+// run also yields each record's log-probability and each row's no-speech
+// probability.
+struct TsSampled {
+    float T[DEC_ROWS] = {};
+    uint64_t key[DEC_ROWS] = {};
+    std::vector<std::vector<float>> plog;  // [B][records of row b]
+    float p_nosp[DEC_ROWS] = {};
+};
+// splitmix64 (wmi_sample.hip's sm64)
+uint64_t sm64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    uint64_t z = x;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// what k_ts_sample_t asks of the vocabulary beyond k_ts_sample (launch_ts_sample_t refuses the rest):
+// 1024 tiles of 64 ids, and sot / solm / not below beg (every Whisper vocabulary)
+int samp_supported(wmi_context *ctx) {
+    const wmi_special_tokens &sp = ctx->sp;
+    if (ctx->hp.n_vocab > 65536 || sp.sot >= sp.beg || sp.solm >= sp.beg || sp.not_ >= sp.beg || sp.solm < 0)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "the temperature sampler needs n_vocab <= 65536 (%d) and sot / solm / not "
+                       "below beg (%d / %d / %d, %d)", ctx->hp.n_vocab, sp.sot, sp.solm, sp.not_, sp.beg);
+    return WMI_OK;
+}
+int ensure_samp_buffers(wmi_context *ctx) {
+    if (ctx->d_samp_rows) return WMI_OK;
+    const size_t nb = DEC_ROWS * sizeof(SampRow) + DEC_ROWS * 4 + (size_t)DEC_ROWS * ctx->hp.n_text_ctx * 4;
+    void *p = nullptr;
+    HIPCHK(ctx, hipMalloc(&p, nb));
+    HIPCHK(ctx, hipMemset(p, 0, nb));
+    ctx->d_samp_rows = (SampRow *)p;
+    ctx->d_samp_nosp = (float *)(ctx->d_samp_rows + DEC_ROWS);
+    ctx->d_samp_plog = ctx->d_samp_nosp + DEC_ROWS;
+    return WMI_OK;
+}
+
 int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &feed, int np, int max_tokens,
-                std::vector<std::vector<TsRec>> *out) {
+                std::vector<std::vector<TsRec>> *out, TsSampled *samp = nullptr) {
     const wmi_hparams &hp = ctx->hp;
     if (ctx->enc_T <= 0) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
     if (B < 1 || B > DEC_ROWS || b0 < 0 || b0 + B > ctx->enc_clips)
@@ -2171,13 +2237,21 @@ int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &fee
     int rc = ensure_decode_buffers(ctx, DEC_ROWS * np, 1);
     if (rc) return rc;
     ctx->ts_prompt = feed;
-    const DecRun run{RUN_TS, b0, B, np, np};
+    DecRun run{RUN_TS, b0, B, np, np};
+    SampRow srows[DEC_ROWS] = {};
+    if (samp) {
+        rc = ensure_samp_buffers(ctx);
+        if (rc) return rc;
+        run.sampled = 1;
+        for (int b = 0; b < B; ++b) { srows[b].T = samp->T[b]; srows[b].key = samp->key[b]; }
+    }
     const int total = np + max_tokens - 1;
     int have = 0;
     do {
         const RunGrid gr = run_grid(ctx, run);
         rc = reset_run(ctx, true, gr.G, gr.Gh, false, feed.data(), B * np, true);
         if (rc) return rc;
+        if (samp) HIPCHK(ctx, hipMemcpyAsync(ctx->d_samp_rows, srows, sizeof srows, hipMemcpyHostToDevice, ctx->stream));
         have = 0;
         for (int done = 0; done < total;) {
             const int chunk = std::min(16, total - done);
@@ -2199,13 +2273,23 @@ int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &fee
         for (int b = 0; b < B && have > 0; ++b)
             HIPCHK(ctx, hipMemcpyAsync((*out)[b].data(), ctx->dts_rec + (size_t)b * hp.n_text_ctx,
                                        (size_t)have * sizeof(TsRec), hipMemcpyDeviceToHost, ctx->stream));
+        if (samp) {
+            samp->plog.assign(B, std::vector<float>((size_t)have));
+            for (int b = 0; b < B && have > 0; ++b)
+                HIPCHK(ctx, hipMemcpyAsync(samp->plog[b].data(), ctx->d_samp_plog + (size_t)b * hp.n_text_ctx,
+                                           (size_t)have * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(samp->p_nosp, ctx->d_samp_nosp, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
+        }
         rc = finish_run(ctx);
     } while (rc == RERUN_ON_CHAIN);
     if (rc) return rc;
     // (a row that met EOT wrote nothing behind it: what lies there is stale)
-    for (auto &r : *out)
+    for (size_t b = 0; b < out->size(); ++b) {
+        auto &r = (*out)[b];
         for (size_t i = 0; i < r.size(); ++i)
             if (r[i].id == ctx->sp.eot) { r.resize(i + 1); break; }
+        if (samp) samp->plog[b].resize(r.size());
+    }
     return WMI_OK;
 }
 
@@ -2225,8 +2309,17 @@ int run_ts_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt
 // with `past`, to the text context of later windows).  Returns the frames to
 // advance: to the last timestamp, or past the window; a window without a
 // usable timestamp is skipped by 100 frames.
-int64_t finish_ts_window(wmi_context *ctx, std::vector<TsRec> toks, int64_t seek, int64_t n_len, int window,
-                         wmi_context::SegList &res, std::vector<int32_t> *past) {
+// Two halves: classify_ts_window judges the sampled tokens (the frames to
+// advance, the tokens kept, whether the window failed) and
+// commit_ts_window appends a window that did not fail; an attempt of the
+// temperature fallback is judged before anything is appended.
+struct TsWindowClass {
+    int64_t seek_delta;
+    int result_len;
+    bool failed;
+};
+TsWindowClass classify_ts_window(const wmi_context *ctx, const std::vector<TsRec> &toks, int64_t seek, int64_t n_len,
+                                 int window) {
     const int beg = ctx->sp.beg, eot = ctx->sp.eot;
     int64_t seek_delta = window;
     int result_len = 0;
@@ -2243,8 +2336,15 @@ int64_t finish_ts_window(wmi_context *ctx, std::vector<TsRec> toks, int64_t seek
         }
     }
     if (!ended && (result_len == 0 || seek_delta < window / 2)) failed = true;  // stuck: no end in n_max tokens
-    if (failed) return 100;
-    toks.resize(result_len);
+    return {seek_delta, result_len, failed};
+}
+
+int64_t commit_ts_window(wmi_context *ctx, std::vector<TsRec> toks, const TsWindowClass &wc, int64_t seek,
+                         wmi_context::SegList &res, std::vector<int32_t> *past) {
+    const int beg = ctx->sp.beg, eot = ctx->sp.eot;
+    const int64_t seek_delta = wc.seek_delta;
+    if (wc.failed) return 100;
+    toks.resize(wc.result_len);
     if (past)
         for (const TsRec &t : toks) past->push_back(t.id);
     if (!toks.empty()) {
@@ -2274,6 +2374,54 @@ int64_t finish_ts_window(wmi_context *ctx, std::vector<TsRec> toks, int64_t seek
     return seek_delta;
 }
 
+int64_t finish_ts_window(wmi_context *ctx, std::vector<TsRec> toks, int64_t seek, int64_t n_len, int window,
+                         wmi_context::SegList &res, std::vector<int32_t> *past) {
+    const TsWindowClass wc = classify_ts_window(ctx, toks, seek, n_len, window);
+    return commit_ts_window(ctx, std::move(toks), wc, seek, res, past);
+}
+
+// ---- temperature fallback (wmi_set_fallback) ---------------------------------
+// the temperatures of a window's attempts: T_j = temperature + j * inc while <= 1 + 1e-6
+std::vector<float> fb_temperatures(const wmi_fallback_params &fb) {
+    std::vector<float> ts;
+    for (int j = 0;; ++j) {
+        const double t = (double)fb.temperature + (double)j * (double)fb.temperature_inc;
+        if (t > 1.0 + 1e-6) break;
+        ts.push_back((float)t);
+        if (!(fb.temperature_inc > 0.0f)) break;
+    }
+    return ts;
+}
+
+// one attempt's verdict: the window's class, its quality figures, rejected or not
+struct FbAttempt {
+    TsWindowClass wc;
+    double avg_logprob, entropy;
+    bool rejected;
+};
+FbAttempt fb_judge(const wmi_context *ctx, const std::vector<TsRec> &toks, double logprob_sum, int64_t seek, int64_t n_len,
+                   int window) {
+    FbAttempt a{};
+    a.wc = classify_ts_window(ctx, toks, seek, n_len, window);
+    const size_t cnt = toks.size();
+    a.avg_logprob = cnt ? logprob_sum / (double)cnt : 0.0;
+    // entropy of the id counts over the last n = min(32, count) tokens
+    const size_t n = std::min<size_t>(32, cnt);
+    std::map<int32_t, int> counts;
+    for (size_t i = cnt - n; i < cnt; ++i) ++counts[toks[i].id];
+    double ent = 0.0;
+    for (const auto &c : counts) {
+        const double p = (double)c.second / (double)n;
+        ent -= p * log(p);
+    }
+    a.entropy = ent;
+    a.rejected = a.wc.failed || a.avg_logprob < (double)ctx->fb.logprob_thold || a.entropy < (double)ctx->fb.entropy_thold;
+    return a;
+}
+
+// wmi_window_info::flags
+constexpr int WIN_SILENCE = 1, WIN_FAILED = 2, WIN_ALL_REJECTED = 4, WIN_RESET = 8;
+
 // the prompt every window starts from: [sot (, language, task)]
 std::vector<int32_t> ts_init_prompt(const wmi_context *ctx, int lang) {
     std::vector<int32_t> init{ctx->sp.sot};
@@ -2285,7 +2433,78 @@ std::vector<int32_t> ts_init_prompt(const wmi_context *ctx, int lang) {
 }
 
 int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, int K, int max_tokens,
-                       std::vector<TsRec> *out, double *score);
+                       std::vector<TsRec> *out, double *score, float *p_nosp = nullptr);
+
+// The end of a window under the fallback: its info record, and unless it was
+// skipped as silence its segments (commit_ts_window); a result of T > 0.5
+// clears the text context.  Returns the frames to advance.
+int64_t fb_finish_window(wmi_context *ctx, int clip, std::vector<TsRec> toks, const FbAttempt &att, bool silence, float T,
+                         int n_attempts, float p_nosp, int64_t seek, int window, std::vector<int32_t> *past) {
+    wmi_context::SegList &res = ctx->results[clip];
+    wmi_window_info wi{};
+    wi.seek = seek; wi.n_attempts = n_attempts; wi.temperature = T; wi.avg_logprob = (float)att.avg_logprob;
+    wi.entropy = (float)att.entropy; wi.no_speech_prob = p_nosp; wi.first_segment = (int32_t)res.segments.size();
+    int64_t delta = window;
+    if (silence) {
+        wi.flags = WIN_SILENCE;
+    } else {
+        delta = commit_ts_window(ctx, std::move(toks), att.wc, seek, res, past);
+        if (att.wc.failed) wi.flags |= WIN_FAILED;
+        if (att.rejected) wi.flags |= WIN_ALL_REJECTED;
+        if (T > 0.5f) {
+            wi.flags |= WIN_RESET;
+            if (past) past->clear();
+        }
+    }
+    wi.n_segments = (int32_t)res.segments.size() - wi.first_segment;
+    ctx->windows[clip].push_back(wi);
+    return delta;
+}
+
+// after attempt 0: probably silence (OpenAI's no_speech_threshold rule)
+bool fb_silence(const wmi_context *ctx, float p_nosp, const FbAttempt &att) {
+    return p_nosp > ctx->fb.no_speech_thold && att.avg_logprob < (double)ctx->fb.logprob_thold;
+}
+
+// One window of wmi_transcribe under the fallback: the attempts at rising
+// temperature on the encoded clip 0 until one is accepted.  *n_samp counts the
+// recording's T > 0 attempts (the ordinal behind each attempt's stream key).
+int run_fb_window(wmi_context *ctx, const std::vector<int32_t> &prompt, int n_max, int64_t seek, int64_t n_len, int window,
+                  const std::vector<float> &temps, uint64_t *n_samp, std::vector<int32_t> *past, int64_t *delta) {
+    std::vector<TsRec> toks;
+    FbAttempt att{};
+    float p_nosp = 0.0f, T = 0.0f;
+    bool silence = false;
+    int j = 0;
+    for (;; ++j) {
+        T = temps[j];
+        double sum = 0.0;
+        if (T == 0.0f && ctx->beam_size > 1) {
+            float pn = 0.0f;
+            int rc = run_ts_beam_window(ctx, 0, prompt, ctx->beam_size, n_max, &toks, &sum, &pn);
+            if (rc) return rc;
+            if (j == 0) p_nosp = pn;
+        } else {
+            TsSampled sp;
+            sp.T[0] = T;
+            if (T > 0.0f) sp.key[0] = sm64(ctx->fb.seed + (*n_samp)++);
+            std::vector<std::vector<TsRec>> rows;
+            int rc = run_ts_rows(ctx, 0, 1, prompt, (int)prompt.size(), n_max, &rows, &sp);
+            if (rc) return rc;
+            toks = std::move(rows[0]);
+            for (float v : sp.plog[0]) sum += (double)v;
+            if (j == 0) p_nosp = sp.p_nosp[0];
+        }
+        ctx->tr_count[1] += ctx->last_run_steps;
+        ++ctx->tr_count[2];
+        att = fb_judge(ctx, toks, sum, seek, n_len, window);
+        silence = j == 0 && fb_silence(ctx, p_nosp, att);
+        if (silence || !att.rejected || j + 1 >= (int)temps.size()) break;
+    }
+    ++ctx->tr_count[0];
+    *delta = fb_finish_window(ctx, 0, std::move(toks), att, silence, T, j + 1, p_nosp, seek, window, past);
+    return WMI_OK;
+}
 
 // whisper_full (whisper.cpp-1.0.3, the loop the reference's WhisperSegment /
 // WhisperTokenData / prompt_past fields belong to, main.rs:317-331, 353-362,
@@ -2308,7 +2527,11 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
     std::vector<int32_t> init;
     std::vector<int32_t> past;
     ctx->results.assign(1, {});
-    ctx->tr_count[0] = ctx->tr_count[1] = 0;
+    ctx->tr_count[0] = ctx->tr_count[1] = ctx->tr_count[2] = 0;
+    ctx->windows.clear();
+    const std::vector<float> temps = ctx->fb_on ? fb_temperatures(ctx->fb) : std::vector<float>();
+    if (ctx->fb_on) ctx->windows.assign(1, {});
+    uint64_t n_samp = 0;
     for (int64_t seek = 0; seek < n_len;) {
         int rc = run_encode(ctx, (int)seek);
         if (rc) return rc;
@@ -2330,6 +2553,14 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
             prompt.insert(prompt.end(), past.end() - keep, past.end());
         }
         prompt.insert(prompt.end(), init.begin(), init.end());
+        if (ctx->fb_on) {  // the attempts of the temperature fallback
+            int64_t delta = 0;
+            rc = run_fb_window(ctx, prompt, n_max, seek, n_len, window, temps, &n_samp, ctx->no_context ? nullptr : &past,
+                               &delta);
+            if (rc) return rc;
+            seek += delta;
+            continue;
+        }
         std::vector<TsRec> toks;
         rc = ctx->beam_size > 1 ? run_ts_beam_window(ctx, 0, prompt, ctx->beam_size, n_max, &toks, nullptr)
                                 : run_ts_window(ctx, 0, prompt, n_max, &toks);
@@ -2367,6 +2598,16 @@ int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
         ctx->lang_p[r] = -1.0f;
     }
     ctx->results.assign((size_t)R, {});
+    // the temperature fallback: each recording's attempt at its current window
+    // (a rejected recording stays at its seek and takes its next temperature
+    // in the next round), its T > 0 attempts so far, attempt 0's no-speech
+    // probability
+    ctx->windows.clear();
+    const std::vector<float> temps = ctx->fb_on ? fb_temperatures(ctx->fb) : std::vector<float>();
+    if (ctx->fb_on) ctx->windows.assign((size_t)R, {});
+    std::vector<int> att_j((size_t)R, 0);
+    std::vector<uint64_t> n_samp((size_t)R, 0);
+    std::vector<float> p_nosp0((size_t)R, 0.0f);
     std::vector<int> rows;  // recording of each decoder row
     int next = 0;
     for (;;) {
@@ -2410,6 +2651,32 @@ int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
             feed.insert(feed.end(), init.begin(), init.end());
         }
         std::vector<std::vector<TsRec>> toks;
+        if (ctx->fb_on) {  // every row at its recording's temperature, with its own stream key
+            TsSampled sp;
+            for (int b = 0; b < B; ++b) {
+                const int r = rows[b];
+                sp.T[b] = temps[att_j[r]];
+                if (sp.T[b] > 0.0f) sp.key[b] = sm64(ctx->fb.seed + n_samp[r]++);
+            }
+            rc = run_ts_rows(ctx, 0, B, feed, np, n_max, &toks, &sp);
+            if (rc) return rc;
+            for (int b = 0; b < B; ++b) {
+                const int r = rows[b], j = att_j[r];
+                double sum = 0.0;
+                for (float v : sp.plog[b]) sum += (double)v;
+                const FbAttempt att = fb_judge(ctx, toks[b], sum, seek[r], ctx->n_len_host[r], window);
+                if (j == 0) p_nosp0[r] = sp.p_nosp[b];
+                const bool silence = j == 0 && fb_silence(ctx, p_nosp0[r], att);
+                if (!silence && att.rejected && j + 1 < (int)temps.size()) {
+                    ++att_j[r];
+                    continue;
+                }
+                seek[r] += fb_finish_window(ctx, r, std::move(toks[b]), att, silence, sp.T[b], j + 1, p_nosp0[r], seek[r],
+                                            window, nullptr);
+                att_j[r] = 0;
+            }
+            continue;
+        }
         rc = run_ts_rows(ctx, 0, B, feed, np, n_max, &toks);
         if (rc) return rc;
         for (int b = 0; b < B; ++b) {
@@ -2535,7 +2802,7 @@ int run_beam(wmi_context *ctx, int K, int n_gen, int suppress_eot, bool early_st
 // hypothesis is chosen as run_beam chooses it; out = its tokens' records, the
 // EOT of a finished one included, *score its summed log-probability.
 int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, int K, int max_tokens,
-                       std::vector<TsRec> *out, double *score) {
+                       std::vector<TsRec> *out, double *score, float *p_nosp) {
     const wmi_hparams &hp = ctx->hp;
     const int np = (int)prompt.size();
     if (ctx->enc_T <= 0 || ctx->enc_clips < 1) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
@@ -2562,6 +2829,11 @@ int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &p
     init.n_active = 1;
     DecRun run{RUN_BEAM, clip, K, np, np, 0, 1, K, max_tokens};
     run.ts_beam = 1;
+    if (p_nosp) {  // (the fallback's attempt 0: k_no_speech behind the first generated step)
+        rc = ensure_samp_buffers(ctx);
+        if (rc) return rc;
+        run.nosp = 1;
+    }
     const int total = np + max_tokens - 1;
     BeamState bs{};
     do {
@@ -2585,6 +2857,7 @@ int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &p
             if (fin) break;
         }
         HIPCHK(ctx, hipMemcpyAsync(&bs, ctx->dbstate, sizeof bs, hipMemcpyDeviceToHost, ctx->stream));
+        if (p_nosp) HIPCHK(ctx, hipMemcpyAsync(p_nosp, ctx->d_samp_nosp, 4, hipMemcpyDeviceToHost, ctx->stream));
         rc = finish_run(ctx);
     } while (rc == RERUN_ON_CHAIN);
     if (rc) return rc;
@@ -2788,6 +3061,7 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->d_tsb_parts) (void)hipFree(ctx->d_tsb_parts);
     if (ctx->d_tsb_rec) (void)hipFree(ctx->d_tsb_rec);
     if (ctx->d_win) (void)hipFree(ctx->d_win);
+    if (ctx->d_samp_rows) (void)hipFree(ctx->d_samp_rows);
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -2984,6 +3258,37 @@ static int wmi_decode_timestamps_impl(wmi_context *ctx, const int32_t *prompt, i
     return WMI_OK;
 }
 
+static int wmi_decode_timestamps_sampled_impl(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens,
+                                              float temperature, uint64_t seed, int n, wmi_token_data *out, int32_t *n_out,
+                                              float *plog, float *p_nosp) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (!prompt || n_prompt < 1 || max_tokens < 1 || !out || !n_out)
+        return set_err(ctx, WMI_E_INVALID_ARG, "null prompt / out / n_out, or n_prompt %d / max_tokens %d below 1", n_prompt,
+                       max_tokens);
+    if (!(temperature >= 0.0f && temperature <= 1.0f) || n < 0)
+        return set_err(ctx, WMI_E_INVALID_ARG, "temperature %g outside [0, 1], or attempt ordinal %d below 0",
+                       (double)temperature, n);
+    for (int i = 0; i < n_prompt; ++i)
+        if (prompt[i] < 0 || prompt[i] >= ctx->hp.n_vocab) return set_err(ctx, WMI_E_INVALID_ARG, "token id %d", prompt[i]);
+    int rc0 = samp_supported(ctx);
+    if (rc0) return rc0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    TsSampled sp;
+    sp.T[0] = temperature;
+    if (temperature > 0.0f) sp.key[0] = sm64(seed + (uint64_t)n);
+    std::vector<std::vector<TsRec>> rows;
+    int rc = run_ts_rows(ctx, 0, 1, std::vector<int32_t>(prompt, prompt + n_prompt), n_prompt, max_tokens, &rows, &sp);
+    if (rc) return rc;
+    const std::vector<TsRec> &rec = rows[0];
+    for (size_t i = 0; i < rec.size(); ++i) {
+        to_token_data(rec[i], out + i);
+        if (plog) plog[i] = sp.plog[0][i];
+    }
+    *n_out = (int32_t)rec.size();
+    if (p_nosp) *p_nosp = sp.p_nosp[0];
+    return WMI_OK;
+}
+
 static int wmi_decode_timestamps_beam_impl(wmi_context *ctx, int beam_size, const int32_t *prompt, int n_prompt,
                                            int max_tokens, wmi_token_data *out, int32_t *n_out, double *score) {
     if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
@@ -3067,6 +3372,50 @@ int wmi_set_no_context(wmi_context *ctx, int no_context) {
     if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
     if (no_context != 0 && no_context != 1) return set_err(ctx, WMI_E_INVALID_ARG, "no_context %d is neither 0 nor 1", no_context);
     ctx->no_context = no_context != 0;
+    return WMI_OK;
+}
+
+int wmi_set_fallback(wmi_context *ctx, const wmi_fallback_params *params) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    const wmi_fallback_params def{0.0f, 0.0f, -INFINITY, -INFINITY, INFINITY, 0};
+    const wmi_fallback_params p = params ? *params : def;
+    if (std::isnan(p.temperature) || std::isnan(p.temperature_inc) || std::isnan(p.logprob_thold) ||
+        std::isnan(p.entropy_thold) || std::isnan(p.no_speech_thold))
+        return set_err(ctx, WMI_E_INVALID_ARG, "NaN fallback parameter");
+    if (p.temperature < 0.0f || p.temperature > 1.0f)
+        return set_err(ctx, WMI_E_INVALID_ARG, "temperature %g outside [0, 1]", (double)p.temperature);
+    // (every attempt is a whole window decode: an increment is 0 or at least 0.01, at most 101 attempts)
+    if (p.temperature_inc < 0.0f || (p.temperature_inc > 0.0f && p.temperature_inc < 0.01f))
+        return set_err(ctx, WMI_E_INVALID_ARG, "temperature_inc %g is neither 0 nor in [0.01, inf)", (double)p.temperature_inc);
+    // (the defaults: every transcribe takes the path it took before this interface existed)
+    const bool on = p.temperature > 0.0f || p.temperature_inc > 0.0f || p.logprob_thold > -INFINITY ||
+                    p.entropy_thold > -INFINITY || p.no_speech_thold < INFINITY;
+    if (on) {
+        int rc = samp_supported(ctx);
+        if (rc) return rc;
+    }
+    ctx->fb = p;
+    ctx->fb_on = on;
+    return WMI_OK;
+}
+
+int wmi_get_window_count(const wmi_context *ctx, int clip, int32_t *n) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    wmi_context *ec = const_cast<wmi_context *>(ctx);  // (last_error only)
+    if (!n || clip < 0 || clip >= (int)ctx->results.size())
+        return set_err(ec, WMI_E_INVALID_ARG, "null n, or clip %d outside the %d recordings of the last transcribe", clip,
+                       (int)ctx->results.size());
+    *n = clip < (int)ctx->windows.size() ? (int32_t)ctx->windows[clip].size() : 0;
+    return WMI_OK;
+}
+
+int wmi_get_window_info(const wmi_context *ctx, int clip, int i, wmi_window_info *out) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    wmi_context *ec = const_cast<wmi_context *>(ctx);
+    if (!out || clip < 0 || clip >= (int)ctx->windows.size() || i < 0 || i >= (int)ctx->windows[clip].size())
+        return set_err(ec, WMI_E_INVALID_ARG, "null out, or window %d of clip %d outside the last transcribe's window infos", i,
+                       clip);
+    *out = ctx->windows[clip][i];
     return WMI_OK;
 }
 
@@ -3530,7 +3879,7 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
             memcpy(out, ctx->ts_prompt.data(), std::min(have19, bytes));
             return WMI_OK;
         }
-        case 20: {  // host: windows and decoder steps of the last wmi_transcribe, int64 [2]
+        case 20: {  // host: windows, decoder steps (every attempt's) and fallback attempts of the last wmi_transcribe, int64 [3]
             memcpy(out, ctx->tr_count, std::min(sizeof ctx->tr_count, bytes));
             return WMI_OK;
         }
@@ -3680,6 +4029,14 @@ int wmi_tokens_to_text(const wmi_context *ctx, const int32_t *ids, int n, char *
 int wmi_decode_timestamps(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens, wmi_token_data *out,
                           int32_t *n_out) {
     return guarded(ctx, [&] { return wmi_decode_timestamps_impl(ctx, prompt, n_prompt, max_tokens, out, n_out); });
+}
+
+int wmi_decode_timestamps_sampled(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens, float temperature,
+                                  uint64_t seed, int n, wmi_token_data *out, int32_t *n_out, float *plog, float *p_nosp) {
+    return guarded(ctx, [&] {
+        return wmi_decode_timestamps_sampled_impl(ctx, prompt, n_prompt, max_tokens, temperature, seed, n, out, n_out, plog,
+                                                  p_nosp);
+    });
 }
 
 int wmi_decode_timestamps_beam(wmi_context *ctx, int beam_size, const int32_t *prompt, int n_prompt, int max_tokens,

@@ -314,6 +314,29 @@ struct TsBeamArgs {
     TsRec *fin_rec;          // [BEAM_MAX] record of finished hypothesis f's EOT
 };
 hipError_t launch_tsbeam_step(hipStream_t s, const TsBeamArgs &a);
+
+// ---- temperature sampling under the timestamp rule (wmi_sample.hip; DESIGN.md
+// "Temperature fallback"): k_ts_sample's records and rule, the id drawn from
+// the allowed set's distribution at the row's temperature -------------------
+struct SampRow {             // per decoder row, in device memory (cached graphs replay the launch)
+    float T;                 // 0: the argmax of the allowed set (k_ts_sample's pick)
+    int32_t pad;
+    unsigned long long key;  // stream key: u_t = (sm64(key + t) >> 11) * 2^-53
+};
+struct TsSampArgs {
+    TsArgs t;
+    const SampRow *rows;     // [B]
+    float *plog;             // [B][max_rec] log-probability of the id under the unscaled masked distribution
+    float *p_nosp;           // [B] P(solm) under the unmasked softmax of the first generated step
+};
+hipError_t launch_ts_sample_t(hipStream_t s, const TsSampArgs &a);
+struct NoSpeechArgs {        // a beam window's no-speech probability (row 0 of its first generated step)
+    const float *logits;     // [V]
+    int V, solm, feed_len;
+    const DecState *st;      // pos already advanced by the logits launch
+    float *p_nosp;
+};
+hipError_t launch_no_speech(hipStream_t s, const NoSpeechArgs &a);
 // WMI_LOGITS_ALL on the kernel chain: logits [rows][V] -> all + (pos - 1) * slab
 // (after the step's logits GEMV; positions outside [0, tctx) are dropped)
 hipError_t launch_logits_capture(hipStream_t s, const float *logits, float *all, const DecState *st, int rows, int V,

@@ -66,6 +66,7 @@ EXPORTS = (
     "wmi_decode_timestamps", "wmi_transcribe", "wmi_get_segment", "wmi_get_segment_tokens",
     "wmi_set_no_context", "wmi_decode_timestamps_batch", "wmi_transcribe_batch", "wmi_get_segment_of",
     "wmi_get_segment_tokens_of", "wmi_decode_timestamps_beam", "wmi_set_beam_size",
+    "wmi_set_fallback", "wmi_decode_timestamps_sampled", "wmi_get_window_count", "wmi_get_window_info",
     "wmi_pcm_to_mel", "wmi_pcm_to_mel_batch", "wmi_encode", "wmi_decode_greedy", "wmi_decode_logits",
     "wmi_decode_beam", "wmi_full", "wmi_stage_pcm", "wmi_run_staged", "wmi_run_staged_beam", "wmi_get_tokens", "wmi_get_timings", "wmi_sync",
     "wmi_get_mel", "wmi_get_checksums", "wmi_get_encoder_out", "wmi_get_cross_kv", "wmi_bench_kernel", "wmi_decode_alg_bytes",
@@ -99,6 +100,19 @@ class TokenData(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class FallbackParams(C.Structure):
+    """wmi_fallback_params."""
+    _fields_ = [("temperature", C.c_float), ("temperature_inc", C.c_float), ("logprob_thold", C.c_float),
+                ("entropy_thold", C.c_float), ("no_speech_thold", C.c_float), ("seed", C.c_uint64)]
+
+
+class WindowInfo(C.Structure):
+    """wmi_window_info; flags: 1 silence, 2 failed, 4 every attempt rejected, 8 context reset."""
+    _fields_ = [("seek", C.c_int64), ("n_attempts", C.c_int32), ("temperature", C.c_float),
+                ("avg_logprob", C.c_float), ("entropy", C.c_float), ("no_speech_prob", C.c_float),
+                ("flags", C.c_int32), ("first_segment", C.c_int32), ("n_segments", C.c_int32)]
 
 
 class Timings(C.Structure):
@@ -148,6 +162,11 @@ def lib():
         L.wmi_decode_timestamps_beam.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.POINTER(i32),
                                                  C.POINTER(C.c_double)]
         L.wmi_set_beam_size.argtypes = [vp, C.c_int]
+        L.wmi_set_fallback.argtypes = [vp, C.POINTER(FallbackParams)]
+        L.wmi_decode_timestamps_sampled.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, vp,
+                                                    C.POINTER(i32), vp, C.POINTER(C.c_float)]
+        L.wmi_get_window_count.argtypes = [vp, C.c_int, C.POINTER(i32)]
+        L.wmi_get_window_info.argtypes = [vp, C.c_int, C.c_int, C.POINTER(WindowInfo)]
         L.wmi_decode_timestamps_batch.argtypes =[vp, vp, C.c_int, C.c_int, vp, vp]
         L.wmi_transcribe_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_int, vp]
         L.wmi_get_segment_of.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p,
@@ -438,6 +457,45 @@ class WhisperContext:
         _raise(lib().wmi_transcribe_batch(self._h, len(clips), ptrs, ns, max_tokens, _ptr(nseg)), self._h)
         self.n_clips = len(clips)
         return [self.segments_of(c, int(nseg[c])) for c in range(len(clips))]
+
+    # --- temperature fallback ---------------------------------------------
+    def set_fallback(self, temperature: float = 0.0, temperature_inc: float = 0.0, logprob_thold: float = -np.inf,
+                     entropy_thold: float = -np.inf, no_speech_thold: float = np.inf, seed: int = 0,
+                     default: bool = False) -> None:
+        """Temperature fallback, quality thresholds and the no-speech skip of
+        transcribe() / transcribe_batch() (wmi_set_fallback); the defaults
+        (or default=True: a NULL parameter block) switch it off."""
+        if default:
+            _raise(lib().wmi_set_fallback(self._h, None), self._h)
+            return
+        p = FallbackParams(temperature, temperature_inc, logprob_thold, entropy_thold, no_speech_thold,
+                           int(seed) & 0xFFFFFFFFFFFFFFFF)
+        _raise(lib().wmi_set_fallback(self._h, C.byref(p)), self._h)
+
+    def decode_timestamps_sampled(self, prompt, max_tokens: int, temperature: float, seed: int = 0, n: int = 0):
+        """One window of encoded clip 0 at one temperature, as attempt ordinal
+        n of `seed`: ([WhisperTokenData dict], plog float32 [tokens], p_nosp)."""
+        prompt = np.ascontiguousarray(prompt, dtype=np.int32)
+        out = (TokenData * max(1, max_tokens))()
+        cnt = C.c_int32()
+        plog = np.zeros(max(1, max_tokens), np.float32)
+        pn = C.c_float()
+        _raise(lib().wmi_decode_timestamps_sampled(self._h, _ptr(prompt), prompt.size, max_tokens, temperature,
+                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, n, out, C.byref(cnt), _ptr(plog),
+                                                   C.byref(pn)), self._h)
+        return [out[i].as_dict() for i in range(cnt.value)], plog[:cnt.value].copy(), pn.value
+
+    def windows_of(self, clip: int = 0):
+        """Window infos of recording `clip` of the last transcribe() /
+        transcribe_batch() under set_fallback ([] when it is off)."""
+        n = C.c_int32()
+        _raise(lib().wmi_get_window_count(self._h, clip, C.byref(n)), self._h)
+        out = []
+        for i in range(n.value):
+            wi = WindowInfo()
+            _raise(lib().wmi_get_window_info(self._h, clip, i, C.byref(wi)), self._h)
+            out.append({k: getattr(wi, k) for k, _ in WindowInfo._fields_})
+        return out
 
     # --- pipeline ---------------------------------------------------------
     def pcm_to_mel_batch(self, clips) -> None:
