@@ -250,57 +250,88 @@ def ts_window_ref(om, ck, cv, prompt, max_tokens, n_threads=8):
     return recs, margin
 
 
-def transcribe_ref(om, pcm, n_ctx, max_tokens, token_text, n_threads=8):
-    """whisper_full restated (wmi_api.cpp run_transcribe): segments
-    [{t0, t1, text, ids}] and the smallest sampling margin met."""
+def init_prompt(special, lang=0, task="transcribe"):
+    """The prompt every window starts from: [sot (, language, task)]."""
+    sp = special
+    return [sp["sot"]] + ([sp["sot"] + 1 + lang, sp[task]] if sp["multilingual"] else [])
+
+
+def classify_window(ids, seek, n_len, window, special):
+    """whisper_full's judgement of a window's sampled ids (wmi_api.cpp
+    classify_ts_window): (seek_delta, result_len, failed)."""
+    beg, eot = special["beg"], special["eot"]
+    seek_delta, result_len, failed, ended = window, 0, False, False
+    for i, t in enumerate(ids):
+        if t > beg:
+            seek_delta, result_len = 2 * (t - beg), i + 1
+        if t == eot:
+            ended = True
+            if result_len == 0:
+                if seek + seek_delta + 100 >= n_len:
+                    result_len = i + 1
+                else:
+                    failed = True
+            break
+    if not ended and (result_len == 0 or seek_delta < window // 2):
+        failed = True
+    return seek_delta, result_len, failed
+
+
+def commit_window(toks, seek, seek_delta, special, token_text, segs):
+    """The segments of a window's kept records (wmi_api.cpp commit_ts_window),
+    appended to segs: {t0, t1, text, ids, tokens (the records)}."""
+    beg, eot = special["beg"], special["eot"]
+
+    def seg(t0, t1, text, part):
+        segs.append({"t0": t0, "t1": t1, "text": text, "ids": [t["id"] for t in part], "tokens": part})
+    if not toks:
+        return
+    i0, t0, text, i = 0, seek + 2 * (toks[0]["tid"] - beg), b"", 0
+    while i < len(toks):
+        if toks[i]["id"] < eot:
+            text += token_text(toks[i]["id"])
+        if toks[i]["id"] > beg:
+            t1 = seek + 2 * (toks[i]["tid"] - beg)
+            if text:
+                seg(t0, t1, text, toks[i0:i + 1])
+            text = b""
+            while i < len(toks) and toks[i]["id"] > beg:
+                i += 1
+            i -= 1
+            t0, i0 = t1, i + 1
+        i += 1
+    if text:
+        seg(t0, seek + seek_delta, text, toks[i0:])
+
+
+def transcribe_ref(om, pcm, n_ctx, max_tokens, token_text, n_threads=8, *, window_fn=ts_window_ref, no_context=False,
+                   init=None, windows=False):
+    """whisper_full restated (wmi_api.cpp run_transcribe): segments (see
+    commit_window) and the smallest sampling margin met; with `windows` also
+    per window (seek, tokens sampled, ended in EOT).  window_fn decodes one
+    window (ts_window_ref's signature), no_context leaves earlier text out of
+    the prompt (whisper.cpp no_context), init replaces init_prompt."""
     sp, hp = om.special, om.hp
     mel = om.mel(pcm, n_threads=4)
     n_len = mel.shape[1]
-    window, beg, eot = 2 * n_ctx, sp["beg"], sp["eot"]
+    window = 2 * n_ctx
     n_max = min(max_tokens, hp["n_text_ctx"] // 2 - 4)
-    init = [sp["sot"]] + ([sp["sot"] + 1, sp["transcribe"]] if sp["multilingual"] else [])
-    past, segs, margin, seek = [], [], np.inf, 0
+    init = init or init_prompt(sp)
+    past, segs, wins, margin, seek = [], [], [], np.inf, 0
     while seek < n_len:
         _, ck, cv = om.encode(mel, n_ctx=n_ctx, mel_offset=seek, n_threads=n_threads)
         # whisper_full: n_take = min(n_text_ctx / 2, past size) tokens after <|prev|>
         prompt = ([sp["prev"]] + past[-(hp["n_text_ctx"] // 2):] if past else []) + init
-        toks, m = ts_window_ref(om, ck, cv, prompt, n_max, n_threads)
+        toks, m = window_fn(om, ck, cv, prompt, n_max, n_threads)
         margin = min(margin, m)
-        seek_delta, result_len, failed, ended = window, 0, False, False
-        for i, t in enumerate(toks):
-            if t["id"] > beg:
-                seek_delta, result_len = 2 * (t["id"] - beg), i + 1
-            if t["id"] == eot:
-                ended = True
-                if result_len == 0:
-                    if seek + seek_delta + 100 >= n_len:
-                        result_len = i + 1
-                    else:
-                        failed = True
-                break
-        if not ended and (result_len == 0 or seek_delta < window // 2):
-            failed = True
+        wins.append((seek, len(toks), toks[-1]["id"] == sp["eot"]))
+        seek_delta, result_len, failed = classify_window([t["id"] for t in toks], seek, n_len, window, sp)
         if failed:
             seek += 100
             continue
         toks = toks[:result_len]
-        past += [t["id"] for t in toks]
-        if toks:
-            i0, t0, text, i = 0, seek + 2 * (toks[0]["tid"] - beg), b"", 0
-            while i < len(toks):
-                if toks[i]["id"] < eot:
-                    text += token_text(toks[i]["id"])
-                if toks[i]["id"] > beg:
-                    t1 = seek + 2 * (toks[i]["tid"] - beg)
-                    if text:
-                        segs.append({"t0": t0, "t1": t1, "text": text, "ids": [t["id"] for t in toks[i0:i + 1]]})
-                    text = b""
-                    while i < len(toks) and toks[i]["id"] > beg:
-                        i += 1
-                    i -= 1
-                    t0, i0 = t1, i + 1
-                i += 1
-            if text:
-                segs.append({"t0": t0, "t1": seek + seek_delta, "text": text, "ids": [t["id"] for t in toks[i0:]]})
+        if not no_context:
+            past += [t["id"] for t in toks]
+        commit_window(toks, seek, seek_delta, sp, token_text, segs)
         seek += seek_delta
-    return segs, margin
+    return (segs, margin, wins) if windows else (segs, margin)

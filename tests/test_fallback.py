@@ -27,7 +27,7 @@ Per-row sampler (temperature T, stream key k, generated-token index t):
 
 Per window, over all its records (EOT included): avg_logprob = mean plog;
 entropy = -sum (c / n) ln(c / n) over the id counts of the last n = min(32,
-count) ids; failed = the window would skip 100 frames (pyoracle.transcribe_ref).
+count) ids; failed = the window would skip 100 frames (pyoracle.classify_window).
 
 Attempts: T_j = temperature + j * temperature_inc (float64, cast to f32), j =
 0, 1, .. while T_j <= 1 + 1e-6 (one attempt with a zero increment).  Rejected:
@@ -172,49 +172,6 @@ def quality(ids, plogs):
     return avg, float(-(p * np.log(p)).sum())
 
 
-def classify(ids, seek, n_len, window, sp):
-    """pyoracle.transcribe_ref's judgement of a window: (seek_delta, result_len, failed)."""
-    beg, eot = sp["beg"], sp["eot"]
-    seek_delta, result_len, failed, ended = window, 0, False, False
-    for i, t in enumerate(ids):
-        if t > beg:
-            seek_delta, result_len = 2 * (t - beg), i + 1
-        if t == eot:
-            ended = True
-            if result_len == 0:
-                if seek + seek_delta + 100 >= n_len:
-                    result_len = i + 1
-                else:
-                    failed = True
-            break
-    if not ended and (result_len == 0 or seek_delta < window // 2):
-        failed = True
-    return seek_delta, result_len, failed
-
-
-def commit(toks, seek, seek_delta, sp, token_text, segs):
-    """pyoracle.transcribe_ref's segments of the kept tokens, appended to segs."""
-    beg, eot = sp["beg"], sp["eot"]
-    if not toks:
-        return
-    i0, t0, text, i = 0, seek + 2 * (toks[0]["tid"] - beg), b"", 0
-    while i < len(toks):
-        if toks[i]["id"] < eot:
-            text += token_text(toks[i]["id"])
-        if toks[i]["id"] > beg:
-            t1 = seek + 2 * (toks[i]["tid"] - beg)
-            if text:
-                segs.append({"t0": t0, "t1": t1, "text": text, "ids": [t["id"] for t in toks[i0:i + 1]]})
-            text = b""
-            while i < len(toks) and toks[i]["id"] > beg:
-                i += 1
-            i -= 1
-            t0, i0 = t1, i + 1
-        i += 1
-    if text:
-        segs.append({"t0": t0, "t1": seek + seek_delta, "text": text, "ids": [t["id"] for t in toks[i0:]]})
-
-
 def temperatures(fb):
     out, j = [], 0
     while True:
@@ -253,7 +210,7 @@ def transcribe_fb_ref(om, pcm, params, token_text, K=1, no_context=False, n_tok=
     n_len = mel.shape[1]
     window = 2 * n_ctx
     n_max = min(n_tok, hp["n_text_ctx"] // 2 - 4)
-    init = [sp["sot"]] + ([sp["sot"] + 1 + params.get("lang", 0), sp["transcribe"]] if sp["multilingual"] else [])
+    init = pyoracle.init_prompt(sp, params.get("lang", 0))
     temps = temperatures(params)
     out = {"segs": [], "infos": [], "margin": np.inf, "prompts": [], "attempts": [], "windows": []}
     past, seek, n_samp = [], 0, 0
@@ -280,7 +237,7 @@ def transcribe_fb_ref(om, pcm, params, token_text, K=1, no_context=False, n_tok=
             if j == 0:
                 p_nosp = pn
             ids = [r["id"] for r in recs]
-            seek_delta, result_len, failed = classify(ids, seek, n_len, window, sp)
+            seek_delta, result_len, failed = pyoracle.classify_window(ids, seek, n_len, window, sp)
             m = min(m, thold_margin(avg, params["logprob_thold"]))
             if ent == params["entropy_thold"]:
                 m = 0.0
@@ -304,7 +261,7 @@ def transcribe_fb_ref(om, pcm, params, token_text, K=1, no_context=False, n_tok=
             toks = recs[:result_len]
             if not no_context:
                 past += [t["id"] for t in toks]
-            commit(toks, seek, seek_delta, sp, token_text, out["segs"])
+            pyoracle.commit_window(toks, seek, seek_delta, sp, token_text, out["segs"])
             seek += seek_delta
         if not silence:
             info["flags"] |= (FAILED if failed else 0) | (ALL_REJECTED if rejected else 0)
@@ -318,26 +275,9 @@ def transcribe_fb_ref(om, pcm, params, token_text, K=1, no_context=False, n_tok=
 
 # --- fixtures ----------------------------------------------------------------------------
 
-def sharp_hook(scale=30.0, amp=60.0):
-    """test_timestamps.write_segmenting_model's shaping with the token embedding scaled by `scale`."""
-    hp = synth.MODEL_DIMS["micro"]
-    beg = hp["n_vocab"] - 1501
-    u = np.random.default_rng(5).standard_normal(hp["n_text_state"]).astype(np.float32)
-    u /= np.linalg.norm(u)
-
-    def hook(name, arr):
-        dt = arr.dtype
-        if name == "decoder.token_embedding.weight":
-            e = arr.astype(np.float32) * scale
-            j = np.arange(e.shape[0] - beg)
-            good = ((j >= 32) & (j < 64)).astype(np.float32)
-            e[beg:] = e[(j * 37) % 50000] * 0.5 + 10.0 * good[:, None] * u[None, :]
-            return e.astype(dt)
-        if name == "decoder.positional_embedding":
-            sgn = np.where(np.arange(arr.shape[0]) % 2 == 0, amp, -amp).astype(np.float32)
-            return (arr.astype(np.float32) + sgn[:, None] * u[None, :]).astype(dt)
-        return arr
-    return hook
+def sharp_hook():
+    """synth.segmenting_hook with the token embedding scaled by 30."""
+    return synth.segmenting_hook(synth.MODEL_DIMS["micro"], scale=30.0)
 
 
 def sharp_model_path(model_cache):
@@ -376,11 +316,10 @@ def nospeech_model_path(model_cache):
 def audio_model_path(model_cache):
     """MODEL SA: S with test_transcribe_batch.py's audio shaping (conv1 x 20, cross-attention
     output x 100), so that the recordings of a batch decode differently."""
-    import test_transcribe_batch as TB
     path = os.path.join(model_cache, "ggml-micro-fallback-s30-a60-audio.bin")
     if not os.path.exists(path):
         os.makedirs(model_cache, exist_ok=True)
-        synth.write_ggml(path, "micro", tensor_hook=TB._audio_hook(sharp_hook()))
+        synth.write_ggml(path, "micro", tensor_hook=synth.audio_hook(sharp_hook()))
     return path
 
 
@@ -533,7 +472,8 @@ def test_t0_is_the_greedy_sampler(models):
     pcm = synth.synth_pcm_f32(*SEG_PCM)
     segs, m = pyoracle.transcribe_ref(om, pcm, N_CTX, N_TOK, token_text, n_threads=threads())
     off = transcribe_fb_ref(om, pcm, fb(), token_text)
-    assert off["segs"] == segs and off["margin"] == m >= TIE and len(segs) >= 8
+    same = [dict(s, tokens=[{k: v for k, v in t.items() if k != "plog"} for t in s["tokens"]]) for s in off["segs"]]
+    assert same == segs and off["margin"] == m >= TIE and len(segs) >= 8          # (the sampler's records carry plog too)
     assert all(i["n_attempts"] == 1 and i["flags"] == 0 and i["temperature"] == 0.0 for i in off["infos"])
 
 
@@ -623,7 +563,7 @@ def test_margins_multilingual(models):
     ref = _lang_ref(models)
     assert [i["n_attempts"] for i in ref["infos"]] == [3] and ref["infos"][0]["flags"] == ALL_REJECTED | RESET
     sp = models("lang")[1].special
-    assert ref["prompts"][0] == [sp["sot"], sp["sot"] + 1 + LANG, sp["transcribe"]]
+    assert ref["prompts"][0] == pyoracle.init_prompt(sp, LANG)
 
 
 # --- GPU -------------------------------------------------------------------------------------
@@ -847,7 +787,7 @@ def test_multilingual(wmi, models, chain):
             _check_segments(got, _with_library_text(ctx, om, ref["segs"]))
             _check_infos(ctx.windows_of(0), ref["infos"])
             fed = np.frombuffer(ctx.debug_read(19, 4 * 4), np.int32)
-            assert fed.tolist() == [sp["sot"], sp["sot"] + 1 + LANG, sp["transcribe"], -1]
+            assert fed.tolist() == pyoracle.init_prompt(sp, LANG) + [-1]
             used, p = ctx.language(0)
             assert used == LANG and ((p == -1.0) if lang == LANG else (0.0 < p <= 1.0))
         B._ran_on(ctx, 1, chain)

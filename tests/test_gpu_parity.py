@@ -981,9 +981,7 @@ def test_no_state_leaks_between_decode_kinds(wmi, micro_model, persist):
         return ctx
 
     def ts(ctx):
-        sp = ctx.special
-        prompt = [sp["sot"]] + ([sp["sot"] + 1, sp["transcribe"]] if sp["multilingual"] else [])
-        got = ctx.decode_timestamps(prompt, 6)
+        got = ctx.decode_timestamps(pyoracle.init_prompt(ctx.special), 6)
         return [np.array([[g["id"], g["tid"]] for g in got]),
                 np.array([[g["p"], g["pt"], g["ptsum"]] for g in got], np.float32)]
 

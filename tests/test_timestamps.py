@@ -7,15 +7,12 @@ Ids must match exactly up to the first near-tie the oracle meets (a sampling
 decision whose margin is below TIE, which f32 reordering may flip).
 
 Random weights make the decoder settle on one token forever (all timestamps, so
-no segment has text).  `segmenting_model` therefore shapes the micro model's
-decoder embeddings so that windows alternate <|ts|> text <|ts|> text ...: a
-unit direction u is added to the token embeddings of timestamps 32..63 and,
-with alternating sign, to the decoder positional embedding, so even steps pick
-a timestamp (seek_delta 64..126 frames, several windows over 4 s) and odd steps
-a text token.  test_segmenting_model_has_segments pins that on the CPU."""
+no segment has text).  `segmenting_model` is therefore the micro model under
+synth.segmenting_hook: windows alternate <|ts|> text <|ts|> text ... with a
+seek_delta of 64..126 frames, several windows over 4 s.
+test_segmenting_model_has_segments pins that on the CPU."""
 import os
 
-import numpy as np
 import pytest
 
 import pyoracle
@@ -25,33 +22,12 @@ from conftest import threads
 TIE = 1e-3
 
 
-def write_segmenting_model(path):
-    hp = synth.MODEL_DIMS["micro"]
-    beg = hp["n_vocab"] - 1501           # <|0.00|> of an English-only vocab
-    u = np.random.default_rng(5).standard_normal(hp["n_text_state"]).astype(np.float32)
-    u /= np.linalg.norm(u)
-
-    def hook(name, arr):
-        dt = arr.dtype
-        if name == "decoder.token_embedding.weight":
-            e = arr.astype(np.float32) * 10.0
-            j = np.arange(e.shape[0] - beg)
-            good = ((j >= 32) & (j < 64)).astype(np.float32)
-            e[beg:] = e[(j * 37) % 50000] * 0.5 + 10.0 * good[:, None] * u[None, :]
-            return e.astype(dt)
-        if name == "decoder.positional_embedding":
-            sgn = np.where(np.arange(arr.shape[0]) % 2 == 0, 60.0, -60.0).astype(np.float32)
-            return (arr.astype(np.float32) + sgn[:, None] * u[None, :]).astype(dt)
-        return arr
-    synth.write_ggml(path, "micro", tensor_hook=hook)
-
-
 @pytest.fixture(scope="module")
 def segmenting_model(model_cache):
     path = os.path.join(model_cache, "ggml-micro-segmenting.bin")
     if not os.path.exists(path):
         os.makedirs(model_cache, exist_ok=True)
-        write_segmenting_model(path)          # synth writes a temp file, then renames
+        synth.write_ggml(path, "micro", tensor_hook=synth.segmenting_hook(synth.MODEL_DIMS["micro"]))  # temp file, then rename
     return path
 
 
@@ -93,8 +69,7 @@ def test_timestamp_window_matches_oracle(ctx, oracle_micro):
         pcm = synth.synth_pcm_f32(2.0, seed)
         mel = om.mel(pcm, n_threads=threads())
         _, ck, cv = om.encode(mel, n_ctx=64, n_threads=threads())
-        prompt = [om.special["sot"]] + ([om.special["sot"] + 1, om.special["transcribe"]]
-                                        if om.special["multilingual"] else [])
+        prompt = pyoracle.init_prompt(om.special)
         ref, margin = pyoracle.ts_window_ref(om, ck, cv, prompt, 12, n_threads=threads())
         if margin < TIE:
             continue

@@ -10,8 +10,8 @@ pyoracle.transcribe_ref with prompt = init at every window.
 
 The fixtures shape the micro model so that the tokens follow the audio (the
 plain segmenting model of test_timestamps.py ignores it: every recording then
-decodes the same ids and a row mix-up would pass): its hook, plus
-encoder.conv1.weight x 20 and every decoder cross_attn.out.weight x 100.
+decodes the same ids and a row mix-up would pass): synth.segmenting_hook
+inside synth.audio_hook.
   A: windows per recording 5 / 3 / 2 / 4, no window reaches EOT.
   B: A with token_embedding[eot] = 1.05 * token_embedding[5581]: most windows
      end in EOT at the second token, the last windows run all 10 tokens, so
@@ -43,44 +43,6 @@ def _pcm(rec):
     return synth.synth_pcm_tones(secs, seed)
 
 
-def _audio_hook(inner):
-    def hook(name, arr):
-        arr = inner(name, arr) if inner else arr
-        if name == "encoder.conv1.weight":
-            return (arr.astype(np.float32) * 20.0).astype(arr.dtype)
-        if name.startswith("decoder.blocks.") and name.endswith(".cross_attn.out.weight"):
-            return (arr.astype(np.float32) * 100.0).astype(arr.dtype)
-        return arr
-    return hook
-
-
-def _segmenting_hook(hp, eot_like=None):
-    """test_timestamps.py's shaping for a vocabulary whose <|0.00|> is `beg`:
-    text rows x 10, timestamp rows from text rows with a unit direction u on
-    timestamps 32..63, u with alternating sign on the positions."""
-    mult = hp["n_vocab"] >= 51865
-    beg = hp["n_vocab"] - 1501           # <|0.00|>
-    eot = 50256 + (1 if mult else 0)
-    u = np.random.default_rng(5).standard_normal(hp["n_text_state"]).astype(np.float32)
-    u /= np.linalg.norm(u)
-
-    def hook(name, arr):
-        dt = arr.dtype
-        if name == "decoder.token_embedding.weight":
-            e = arr.astype(np.float32) * 10.0
-            j = np.arange(e.shape[0] - beg)
-            good = ((j >= 32) & (j < 64)).astype(np.float32)
-            e[beg:] = e[(j * 37) % 50000] * 0.5 + 10.0 * good[:, None] * u[None, :]
-            if eot_like is not None:
-                e[eot] = 1.05 * e[eot_like]
-            return e.astype(dt)
-        if name == "decoder.positional_embedding":
-            sgn = np.where(np.arange(arr.shape[0]) % 2 == 0, 60.0, -60.0).astype(np.float32)
-            return (arr.astype(np.float32) + sgn[:, None] * u[None, :]).astype(dt)
-        return arr
-    return hook
-
-
 def _write(path, model, hook, hp_override=None):
     if not os.path.exists(path):
         synth.write_ggml(path, model, hp_override=hp_override, tensor_hook=hook)  # temp file, then rename
@@ -96,13 +58,13 @@ def fixtures(model_cache):
         if tag not in made:
             hp = dict(synth.MODEL_DIMS["micro"])
             if tag in ("A", "B"):
-                hook = _audio_hook(_segmenting_hook(hp, EOT_LIKE if tag == "B" else None))
+                hook = synth.audio_hook(synth.segmenting_hook(hp, eot_like=EOT_LIKE if tag == "B" else None))
                 path = _write(os.path.join(model_cache, f"ggml-micro-tsbatch-{tag}.bin"), "micro", hook)
             elif tag == "W":  # a micro-depth n = 1024 model
                 hpw = dict(n_vocab=51865, n_audio_state=1024, n_text_state=1024, n_audio_head=16, n_text_head=16,
                            n_audio_layer=2, n_text_layer=2)
                 hp.update(hpw)
-                hook = _audio_hook(_segmenting_hook(hp))
+                hook = synth.audio_hook(synth.segmenting_hook(hp))
                 path = _write(os.path.join(model_cache, "ggml-micro-tsbatch-n1024.bin"), "micro", hook, hpw)
             elif tag == "L":  # test_language.py's 51865-vocabulary micro model, written the same way
                 path = _write(os.path.join(model_cache, "ggml-micro-lang-51865.bin"), "micro", synth.xsharp_lv3_hook,
@@ -110,7 +72,7 @@ def fixtures(model_cache):
             else:  # "LS": the segmenting, audio-following shaping on that vocabulary
                 hpl = dict(n_vocab=51865)
                 hp.update(hpl)
-                hook = _audio_hook(_segmenting_hook(hp))
+                hook = synth.audio_hook(synth.segmenting_hook(hp))
                 path = _write(os.path.join(model_cache, "ggml-micro-tsbatch-lang.bin"), "micro", hook, hpl)
             made[tag] = (path, pyoracle.OracleModel(path))
         return made[tag]
@@ -125,57 +87,10 @@ def token_text(i):
 
 def nocontext_ref(om, pcm, n_ctx, max_tokens, init=None):
     """pyoracle.transcribe_ref with prompt = init at every window (whisper.cpp
-    no_context): (segments with ids and their token records, smallest margin,
-    per window (seek, tokens sampled, ended in EOT))."""
-    sp, hp = om.special, om.hp
-    mel = om.mel(pcm, n_threads=4)
-    n_len = mel.shape[1]
-    window, beg, eot = 2 * n_ctx, sp["beg"], sp["eot"]
-    n_max = min(max_tokens, hp["n_text_ctx"] // 2 - 4)
-    init = init or [sp["sot"]] + ([sp["sot"] + 1, sp["transcribe"]] if sp["multilingual"] else [])
-    segs, wins, margin, seek = [], [], np.inf, 0
-    while seek < n_len:
-        _, ck, cv = om.encode(mel, n_ctx=n_ctx, mel_offset=seek, n_threads=threads())
-        toks, m = pyoracle.ts_window_ref(om, ck, cv, init, n_max, threads())
-        margin = min(margin, m)
-        wins.append((seek, len(toks), toks[-1]["id"] == eot))
-        seek_delta, result_len, failed, ended = window, 0, False, False
-        for i, t in enumerate(toks):
-            if t["id"] > beg:
-                seek_delta, result_len = 2 * (t["id"] - beg), i + 1
-            if t["id"] == eot:
-                ended = True
-                if result_len == 0:
-                    if seek + seek_delta + 100 >= n_len:
-                        result_len = i + 1
-                    else:
-                        failed = True
-                break
-        if not ended and (result_len == 0 or seek_delta < window // 2):
-            failed = True
-        if failed:
-            seek += 100
-            continue
-        toks = toks[:result_len]
-        if toks:
-            i0, t0, text, i = 0, seek + 2 * (toks[0]["tid"] - beg), b"", 0
-            while i < len(toks):
-                if toks[i]["id"] < eot:
-                    text += token_text(toks[i]["id"])
-                if toks[i]["id"] > beg:
-                    t1 = seek + 2 * (toks[i]["tid"] - beg)
-                    if text:
-                        segs.append({"t0": t0, "t1": t1, "text": text, "tokens": toks[i0:i + 1]})
-                    text = b""
-                    while i < len(toks) and toks[i]["id"] > beg:
-                        i += 1
-                    i -= 1
-                    t0, i0 = t1, i + 1
-                i += 1
-            if text:
-                segs.append({"t0": t0, "t1": seek + seek_delta, "text": text, "tokens": toks[i0:]})
-        seek += seek_delta
-    return segs, margin, wins
+    no_context): (segments, smallest margin, per window (seek, tokens sampled,
+    ended in EOT))."""
+    return pyoracle.transcribe_ref(om, pcm, n_ctx, max_tokens, token_text, n_threads=threads(), no_context=True,
+                                   init=init, windows=True)
 
 
 _REF = {}
@@ -196,8 +111,7 @@ def first_window_ref(om, rec, prompt, max_tokens):
 
 
 def init_prompt(om):
-    sp = om.special
-    return [sp["sot"]] + ([sp["sot"] + 1, sp["transcribe"]] if sp["multilingual"] else [])
+    return pyoracle.init_prompt(om.special)
 
 
 def assert_tokens(got, ref):
@@ -439,8 +353,7 @@ LANG_SET = ("de", "ja", None)
 
 
 def _lang_init(om, lang):
-    sp = om.special
-    return [sp["sot"], sp["sot"] + 1 + lang, sp["transcribe"]]
+    return pyoracle.init_prompt(om.special, lang)
 
 
 def _lang_refs(om, recs):

@@ -174,21 +174,14 @@ def oracle_window(om, ck, cv, prompt, K, max_tokens, key=None):
 
 
 def transcribe_beam_ref(om, pcm, K, token_text, key):
-    """pyoracle.transcribe_ref's bookkeeping over beam windows."""
-    if (om.path, "tr", key, K) in _REF:
-        return _REF[om.path, "tr", key, K]
-
-    def window(om_, ck, cv, prompt, n_max, n_threads=8):
-        recs, _, m, _ = oracle_window(om_, ck, cv, prompt, K, n_max)
-        return recs, m
-    old = pyoracle.ts_window_ref
-    pyoracle.ts_window_ref = window
-    try:
-        out = pyoracle.transcribe_ref(om, pcm, N_CTX, N_TOK, token_text, n_threads=threads())
-    finally:
-        pyoracle.ts_window_ref = old
-    _REF[om.path, "tr", key, K] = out
-    return out
+    """pyoracle.transcribe_ref over beam windows."""
+    if (om.path, "tr", key, K) not in _REF:
+        def window(om_, ck, cv, prompt, n_max, n_threads=8):
+            recs, _, m, _ = oracle_window(om_, ck, cv, prompt, K, n_max)
+            return recs, m
+        _REF[om.path, "tr", key, K] = pyoracle.transcribe_ref(om, pcm, N_CTX, N_TOK, token_text, n_threads=threads(),
+                                                              window_fn=window)
+    return _REF[om.path, "tr", key, K]
 
 
 def token_text(i):
@@ -196,28 +189,6 @@ def token_text(i):
 
 
 # --- fixtures ----------------------------------------------------------------------------
-
-def write_segmenting_model(path, amp):
-    """test_timestamps.write_segmenting_model with the positional amplitude a parameter."""
-    hp = synth.MODEL_DIMS["micro"]
-    beg = hp["n_vocab"] - 1501
-    u = np.random.default_rng(5).standard_normal(hp["n_text_state"]).astype(np.float32)
-    u /= np.linalg.norm(u)
-
-    def hook(name, arr):
-        dt = arr.dtype
-        if name == "decoder.token_embedding.weight":
-            e = arr.astype(np.float32) * 10.0
-            j = np.arange(e.shape[0] - beg)
-            good = ((j >= 32) & (j < 64)).astype(np.float32)
-            e[beg:] = e[(j * 37) % 50000] * 0.5 + 10.0 * good[:, None] * u[None, :]
-            return e.astype(dt)
-        if name == "decoder.positional_embedding":
-            sgn = np.where(np.arange(arr.shape[0]) % 2 == 0, amp, -amp).astype(np.float32)
-            return (arr.astype(np.float32) + sgn[:, None] * u[None, :]).astype(dt)
-        return arr
-    synth.write_ggml(path, "micro", tensor_hook=hook)
-
 
 @pytest.fixture(scope="module")
 def seg(model_cache):
@@ -228,7 +199,7 @@ def seg(model_cache):
         if amp not in open_:
             path = os.path.join(model_cache, f"ggml-micro-segmenting-a{amp}.bin")
             if not os.path.exists(path):
-                write_segmenting_model(path, float(amp))
+                synth.write_ggml(path, "micro", tensor_hook=synth.segmenting_hook(synth.MODEL_DIMS["micro"], amp=float(amp)))
             open_[amp] = (path, pyoracle.OracleModel(path))
         return open_[amp]
     yield get
@@ -250,8 +221,7 @@ def wmi():
     return w
 
 
-def _init(sp):
-    return [sp["sot"]] + ([sp["sot"] + 1, sp["transcribe"]] if sp["multilingual"] else [])
+_init = pyoracle.init_prompt
 
 
 def _micro_ref(om, seed, K):
@@ -278,7 +248,7 @@ LANG, LANG_SEED = 34, TL.SEEDS[1]      # test_language.py: clip 1237 is detected
 
 
 def _lang_prompt(sp):
-    return [sp["sot"], sp["sot"] + 1 + LANG, sp["translate"]]
+    return pyoracle.init_prompt(sp, LANG, "translate")
 
 
 def _lang_ref(om):
@@ -291,7 +261,7 @@ def _ids(recs):
 
 
 def _seg_ids(segs):
-    return [s["ids"] if "ids" in s else [t["id"] for t in s["tokens"]] for s in segs]
+    return [[t["id"] for t in s["tokens"]] for s in segs]
 
 
 # --- CPU: the restatement alone ------------------------------------------------------------

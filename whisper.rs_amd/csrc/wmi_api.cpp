@@ -2374,12 +2374,6 @@ int64_t commit_ts_window(wmi_context *ctx, std::vector<TsRec> toks, const TsWind
     return seek_delta;
 }
 
-int64_t finish_ts_window(wmi_context *ctx, std::vector<TsRec> toks, int64_t seek, int64_t n_len, int window,
-                         wmi_context::SegList &res, std::vector<int32_t> *past) {
-    const TsWindowClass wc = classify_ts_window(ctx, toks, seek, n_len, window);
-    return commit_ts_window(ctx, std::move(toks), wc, seek, res, past);
-}
-
 // ---- temperature fallback (wmi_set_fallback) ---------------------------------
 // the temperatures of a window's attempts: T_j = temperature + j * inc while <= 1 + 1e-6
 std::vector<float> fb_temperatures(const wmi_fallback_params &fb) {
@@ -2435,257 +2429,295 @@ std::vector<int32_t> ts_init_prompt(const wmi_context *ctx, int lang) {
 int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, int K, int max_tokens,
                        std::vector<TsRec> *out, double *score, float *p_nosp = nullptr);
 
-// The end of a window under the fallback: its info record, and unless it was
-// skipped as silence its segments (commit_ts_window); a result of T > 0.5
-// clears the text context.  Returns the frames to advance.
-int64_t fb_finish_window(wmi_context *ctx, int clip, std::vector<TsRec> toks, const FbAttempt &att, bool silence, float T,
-                         int n_attempts, float p_nosp, int64_t seek, int window, std::vector<int32_t> *past) {
-    wmi_context::SegList &res = ctx->results[clip];
-    wmi_window_info wi{};
-    wi.seek = seek; wi.n_attempts = n_attempts; wi.temperature = T; wi.avg_logprob = (float)att.avg_logprob;
-    wi.entropy = (float)att.entropy; wi.no_speech_prob = p_nosp; wi.first_segment = (int32_t)res.segments.size();
-    int64_t delta = window;
-    if (silence) {
-        wi.flags = WIN_SILENCE;
-    } else {
-        delta = commit_ts_window(ctx, std::move(toks), att.wc, seek, res, past);
-        if (att.wc.failed) wi.flags |= WIN_FAILED;
-        if (att.rejected) wi.flags |= WIN_ALL_REJECTED;
-        if (T > 0.5f) {
-            wi.flags |= WIN_RESET;
-            if (past) past->clear();
-        }
-    }
-    wi.n_segments = (int32_t)res.segments.size() - wi.first_segment;
-    ctx->windows[clip].push_back(wi);
-    return delta;
-}
-
 // after attempt 0: probably silence (OpenAI's no_speech_threshold rule)
 bool fb_silence(const wmi_context *ctx, float p_nosp, const FbAttempt &att) {
     return p_nosp > ctx->fb.no_speech_thold && att.avg_logprob < (double)ctx->fb.logprob_thold;
 }
 
-// One window of wmi_transcribe under the fallback: the attempts at rising
-// temperature on the encoded clip 0 until one is accepted.  *n_samp counts the
-// recording's T > 0 attempts (the ordinal behind each attempt's stream key).
-int run_fb_window(wmi_context *ctx, const std::vector<int32_t> &prompt, int n_max, int64_t seek, int64_t n_len, int window,
-                  const std::vector<float> &temps, uint64_t *n_samp, std::vector<int32_t> *past, int64_t *delta) {
-    std::vector<TsRec> toks;
-    FbAttempt att{};
-    float p_nosp = 0.0f, T = 0.0f;
-    bool silence = false;
-    int j = 0;
-    for (;; ++j) {
-        T = temps[j];
-        double sum = 0.0;
-        if (T == 0.0f && ctx->beam_size > 1) {
-            float pn = 0.0f;
-            int rc = run_ts_beam_window(ctx, 0, prompt, ctx->beam_size, n_max, &toks, &sum, &pn);
-            if (rc) return rc;
-            if (j == 0) p_nosp = pn;
-        } else {
-            TsSampled sp;
-            sp.T[0] = T;
-            if (T > 0.0f) sp.key[0] = sm64(ctx->fb.seed + (*n_samp)++);
-            std::vector<std::vector<TsRec>> rows;
-            int rc = run_ts_rows(ctx, 0, 1, prompt, (int)prompt.size(), n_max, &rows, &sp);
-            if (rc) return rc;
-            toks = std::move(rows[0]);
-            for (float v : sp.plog[0]) sum += (double)v;
-            if (j == 0) p_nosp = sp.p_nosp[0];
-        }
-        ctx->tr_count[1] += ctx->last_run_steps;
-        ++ctx->tr_count[2];
-        att = fb_judge(ctx, toks, sum, seek, n_len, window);
-        silence = j == 0 && fb_silence(ctx, p_nosp, att);
-        if (silence || !att.rejected || j + 1 >= (int)temps.size()) break;
+// ---- whisper_full's loop: state, decode-attempt, settle ------------------------
+// One recording of a wmi_transcribe / wmi_transcribe_batch call.
+struct TrRec {
+    int clip;                   // its mel, segment list and window infos
+    int64_t seek, n_len;        // the current window's first frame, the recording's frames
+    int lang;                   // WMI_LANG_AUTO until its first window
+    float lang_p;               // the detection's probability (-1: set explicitly)
+    bool carry;                 // earlier text goes into later prompts (wmi_transcribe without no-context)
+    std::vector<int32_t> past;  // that text
+    int att;                    // the fallback's attempt at the current window
+    uint64_t n_samp;            // T > 0 attempts so far (the ordinal behind each attempt's stream key)
+    float p_nosp0;              // attempt 0's no-speech probability
+};
+struct TrRun {
+    int window, n_max;          // frames a window, sampled tokens a window at most
+    std::vector<float> temps;   // the fallback's temperatures (empty: off)
+    std::vector<TrRec> recs;
+};
+
+// A call's start: empty results and window infos, every recording at frame 0
+// with the language set for its clip.
+TrRun tr_begin(wmi_context *ctx, int R, int max_tokens, bool carry) {
+    const wmi_hparams &hp = ctx->hp;
+    TrRun tr;
+    tr.window = 2 * (ctx->cur_ctx > 0 ? ctx->cur_ctx : hp.n_audio_ctx);
+    tr.n_max = std::min(max_tokens, hp.n_text_ctx / 2 - 4);
+    if (ctx->fb_on) tr.temps = fb_temperatures(ctx->fb);
+    for (int r = 0; r < R; ++r) tr.recs.push_back({r, 0, ctx->n_len_host[r], ctx->lang_set[r], -1.0f, carry, {}, 0, 0, 0.0f});
+    ctx->results.assign((size_t)R, {});
+    ctx->windows.clear();
+    if (ctx->fb_on) ctx->windows.assign((size_t)R, {});
+    return tr;
+}
+
+// The languages of the recordings in the encoded rows 0..B-1: AUTO is detected
+// once, on a recording's first window (as whisper.cpp does; only such a round
+// runs the detection), and kept for every later window.
+int tr_resolve_languages(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows) {
+    const int B = (int)rows.size();
+    bool detect = false;
+    for (int r : rows) detect = detect || tr.recs[r].lang == WMI_LANG_AUTO;
+    int32_t det[DEC_ROWS] = {};
+    float p[DEC_ROWS] = {};
+    if (detect) {
+        int rc = run_lang_detect_sync(ctx);
+        if (rc) return rc;
+        HIPCHK(ctx, hipMemcpy(det, ctx->d_lang_det, (size_t)B * 4, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(p, ctx->d_lang_p, (size_t)B * 4, hipMemcpyDeviceToHost));
     }
-    ++ctx->tr_count[0];
-    *delta = fb_finish_window(ctx, 0, std::move(toks), att, silence, T, j + 1, p_nosp, seek, window, past);
+    for (int b = 0; b < B; ++b) {
+        TrRec &rec = tr.recs[rows[b]];
+        if (rec.lang == WMI_LANG_AUTO) { rec.lang = det[b]; rec.lang_p = p[b]; }
+        ctx->lang_used[rec.clip] = rec.lang;
+        ctx->lang_p[rec.clip] = rec.lang_p;
+    }
     return WMI_OK;
+}
+
+// a window's prompt: [prev] + the last min(n_text_ctx / 2, past) earlier tokens
+// (whisper_full's n_take; none without text context) + [sot (, language, task)]
+std::vector<int32_t> tr_prompt(const wmi_context *ctx, const TrRec &rec) {
+    std::vector<int32_t> prompt;
+    if (!rec.past.empty()) {
+        prompt.push_back(ctx->sp.prev);
+        const size_t keep = std::min(rec.past.size(), (size_t)(ctx->hp.n_text_ctx / 2));
+        prompt.insert(prompt.end(), rec.past.end() - keep, rec.past.end());
+    }
+    const std::vector<int32_t> init = ts_init_prompt(ctx, rec.lang);
+    prompt.insert(prompt.end(), init.begin(), init.end());
+    return prompt;
+}
+
+// One decoded attempt at a window.
+struct TrAttempt {
+    std::vector<TsRec> toks;
+    double logprob_sum;
+    float p_nosp, T;
+};
+// The recordings `rows` sit in the encoded rows 0..B-1 and row b is fed the np
+// tokens feed[b * np ..): each row's attempt at its recording's temperature.
+// Fallback off: the plain sampler (k_ts_sample), or with a beam size the beam
+// window, neither with quality figures.  Fallback on: every row through the
+// temperature sampler (at T = 0 too) with its own stream key; with a beam
+// size a T = 0 attempt is the beam window with k_no_speech behind it.
+int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows, const std::vector<int32_t> &feed, int np,
+                      std::vector<TrAttempt> *out) {
+    const int B = (int)rows.size();
+    const bool fb = !tr.temps.empty();
+    out->assign((size_t)B, {});
+    for (int b = 0; b < B; ++b) (*out)[b].T = fb ? tr.temps[tr.recs[rows[b]].att] : 0.0f;
+    if (ctx->beam_size > 1 && (*out)[0].T == 0.0f) {
+        if (B != 1) return set_err(ctx, WMI_E_UNSUPPORTED, "a beam window decodes one recording (%d rows)", B);
+        TrAttempt &a = (*out)[0];
+        return run_ts_beam_window(ctx, 0, feed, ctx->beam_size, tr.n_max, &a.toks, fb ? &a.logprob_sum : nullptr,
+                                  fb ? &a.p_nosp : nullptr);
+    }
+    TsSampled sp;
+    for (int b = 0; b < B && fb; ++b) {
+        sp.T[b] = (*out)[b].T;
+        if (sp.T[b] > 0.0f) sp.key[b] = sm64(ctx->fb.seed + tr.recs[rows[b]].n_samp++);
+    }
+    std::vector<std::vector<TsRec>> toks;
+    int rc = run_ts_rows(ctx, 0, B, feed, np, tr.n_max, &toks, fb ? &sp : nullptr);
+    if (rc) return rc;
+    for (int b = 0; b < B; ++b) {
+        TrAttempt &a = (*out)[b];
+        a.toks = std::move(toks[b]);
+        if (!fb) continue;
+        for (float v : sp.plog[b]) a.logprob_sum += (double)v;
+        a.p_nosp = sp.p_nosp[b];
+    }
+    return WMI_OK;
+}
+
+// A finished attempt is judged and the window committed or tried again.
+// Fallback off: one attempt, taken as it comes (classify_ts_window,
+// commit_ts_window), no window info.  Fallback on: a rejected attempt with a
+// temperature left moves the recording to its next attempt and leaves seek;
+// otherwise the window ends: its info record, and unless it was skipped as
+// silence its segments; a result of T > 0.5 clears the text context.
+// Returns whether the window is done (seek has then moved).
+bool tr_settle(wmi_context *ctx, const TrRun &tr, TrRec &rec, TrAttempt a) {
+    wmi_context::SegList &res = ctx->results[rec.clip];
+    std::vector<int32_t> *past = rec.carry ? &rec.past : nullptr;
+    if (tr.temps.empty()) {
+        const TsWindowClass wc = classify_ts_window(ctx, a.toks, rec.seek, rec.n_len, tr.window);
+        rec.seek += commit_ts_window(ctx, std::move(a.toks), wc, rec.seek, res, past);
+        return true;
+    }
+    const FbAttempt att = fb_judge(ctx, a.toks, a.logprob_sum, rec.seek, rec.n_len, tr.window);
+    if (rec.att == 0) rec.p_nosp0 = a.p_nosp;
+    const bool silence = rec.att == 0 && fb_silence(ctx, rec.p_nosp0, att);
+    if (!silence && att.rejected && rec.att + 1 < (int)tr.temps.size()) {
+        ++rec.att;
+        return false;
+    }
+    wmi_window_info wi{};
+    wi.seek = rec.seek; wi.n_attempts = rec.att + 1; wi.temperature = a.T; wi.avg_logprob = (float)att.avg_logprob;
+    wi.entropy = (float)att.entropy; wi.no_speech_prob = rec.p_nosp0; wi.first_segment = (int32_t)res.segments.size();
+    int64_t delta = tr.window;
+    if (silence) {
+        wi.flags = WIN_SILENCE;
+    } else {
+        delta = commit_ts_window(ctx, std::move(a.toks), att.wc, rec.seek, res, past);
+        if (att.wc.failed) wi.flags |= WIN_FAILED;
+        if (att.rejected) wi.flags |= WIN_ALL_REJECTED;
+        if (a.T > 0.5f) {
+            wi.flags |= WIN_RESET;
+            rec.past.clear();
+        }
+    }
+    wi.n_segments = (int32_t)res.segments.size() - wi.first_segment;
+    ctx->windows[rec.clip].push_back(wi);
+    rec.att = 0;
+    rec.seek += delta;
+    return true;
 }
 
 // whisper_full (whisper.cpp-1.0.3, the loop the reference's WhisperSegment /
 // WhisperTokenData / prompt_past fields belong to, main.rs:317-331, 353-362,
-// 599-604): windows of 2 * n_ctx mel frames from `seek`, prompt = [prev] +
-// the last min(n_text_ctx/2, past) tokens of earlier windows (whisper_full's
-// n_take; none with wmi_set_no_context) + [sot (, lang, transcribe)], at most n_text_ctx/2 - 4 sampled
-// tokens (1 + 224 + 3 + 220 = 448 positions at most), timestamp sampling; the
-// window's bookkeeping is finish_ts_window.  Restated op for op in
-// oracle/pyoracle.py transcribe_ref.
+// 599-604) of one recording: windows of 2 * n_ctx mel frames from `seek`,
+// prompt = tr_prompt, at most n_text_ctx/2 - 4 sampled tokens (1 + 224 + 3 +
+// 220 = 448 positions at most), timestamp sampling or the beam window; the
+// window's bookkeeping is tr_settle.  A rejected attempt is decoded again at
+// once, on the same encoder output.  Restated op for op in oracle/pyoracle.py
+// transcribe_ref.
 int run_transcribe(wmi_context *ctx, int max_tokens) {
-    const wmi_hparams &hp = ctx->hp;
-    const int64_t n_len = ctx->n_len_host[0];
-    const int n_ctx = ctx->cur_ctx > 0 ? ctx->cur_ctx : hp.n_audio_ctx;
-    const int window = 2 * n_ctx;
-    const int n_max = std::min(max_tokens, hp.n_text_ctx / 2 - 4);
-    // clip 0's language and the task; AUTO: detected once, on the first
-    // window (as whisper.cpp does), and kept for every later window
-    int lang = ctx->lang_set[0];
-    float lang_p = -1.0f;
-    std::vector<int32_t> init;
-    std::vector<int32_t> past;
-    ctx->results.assign(1, {});
+    TrRun tr = tr_begin(ctx, 1, max_tokens, !ctx->no_context);
+    TrRec &rec = tr.recs[0];
+    const std::vector<int> rows{0};
     ctx->tr_count[0] = ctx->tr_count[1] = ctx->tr_count[2] = 0;
-    ctx->windows.clear();
-    const std::vector<float> temps = ctx->fb_on ? fb_temperatures(ctx->fb) : std::vector<float>();
-    if (ctx->fb_on) ctx->windows.assign(1, {});
-    uint64_t n_samp = 0;
-    for (int64_t seek = 0; seek < n_len;) {
-        int rc = run_encode(ctx, (int)seek);
+    while (rec.seek < rec.n_len) {
+        int rc = run_encode(ctx, (int)rec.seek);
         if (rc) return rc;
-        if (init.empty()) {
-            if (lang == WMI_LANG_AUTO) {
-                rc = run_lang_detect_sync(ctx);
-                if (rc) return rc;
-                HIPCHK(ctx, hipMemcpy(&lang, ctx->d_lang_det, 4, hipMemcpyDeviceToHost));
-                HIPCHK(ctx, hipMemcpy(&lang_p, ctx->d_lang_p, 4, hipMemcpyDeviceToHost));
-            }
-            init = ts_init_prompt(ctx, lang);
-            ctx->lang_used[0] = lang;
-            ctx->lang_p[0] = lang_p;
-        }
-        std::vector<int32_t> prompt;
-        if (!past.empty()) {
-            prompt.push_back(ctx->sp.prev);
-            const size_t keep = std::min(past.size(), (size_t)(hp.n_text_ctx / 2));
-            prompt.insert(prompt.end(), past.end() - keep, past.end());
-        }
-        prompt.insert(prompt.end(), init.begin(), init.end());
-        if (ctx->fb_on) {  // the attempts of the temperature fallback
-            int64_t delta = 0;
-            rc = run_fb_window(ctx, prompt, n_max, seek, n_len, window, temps, &n_samp, ctx->no_context ? nullptr : &past,
-                               &delta);
+        rc = tr_resolve_languages(ctx, tr, rows);
+        if (rc) return rc;
+        const std::vector<int32_t> prompt = tr_prompt(ctx, rec);
+        for (bool done = false; !done;) {
+            std::vector<TrAttempt> att;
+            rc = tr_decode_attempt(ctx, tr, rows, prompt, (int)prompt.size(), &att);
             if (rc) return rc;
-            seek += delta;
-            continue;
+            ctx->tr_count[1] += ctx->last_run_steps;
+            if (ctx->fb_on) ++ctx->tr_count[2];
+            done = tr_settle(ctx, tr, rec, std::move(att[0]));
         }
-        std::vector<TsRec> toks;
-        rc = ctx->beam_size > 1 ? run_ts_beam_window(ctx, 0, prompt, ctx->beam_size, n_max, &toks, nullptr)
-                                : run_ts_window(ctx, 0, prompt, n_max, &toks);
-        if (rc) return rc;
         ++ctx->tr_count[0];
-        ctx->tr_count[1] += ctx->last_run_steps;
-        seek += finish_ts_window(ctx, std::move(toks), seek, n_len, window, ctx->results[0],
-                                 ctx->no_context ? nullptr : &past);
     }
     return WMI_OK;
 }
 
 // wmi_transcribe_batch: every loaded recording through whisper_full's loop
 // without text context, up to DEC_ROWS of them per decoder step.  All mels
-// stay resident; a recording holds host state (seek, language) and its own
-// segment list.  Per round the active recordings sit compacted in rows
-// 0..B-1: one encode of the B slots, each at its recording's seek
-// (k_mel_window's per-slot source and offset), one lockstep timestamp window
-// of B rows — every prompt is [sot (, language, task)], so the rows share the
-// decoder's one position — then each row's window bookkeeping.  A recording
-// that reached its end leaves its row; a waiting one takes a free row at the
+// stay resident; a recording holds host state (TrRec) and its own segment
+// list.  Per round the active recordings sit compacted in rows 0..B-1: one
+// encode of the B slots, each at its recording's seek (k_mel_window's per-slot
+// source and offset), one lockstep timestamp window of B rows — every prompt
+// is [sot (, language, task)], so the rows share the decoder's one position —
+// then each row's tr_settle.  A recording that reached its end leaves its
+// row; a waiting one takes a free row at the next round; under the fallback a
+// rejected recording stays at its seek and takes its next temperature in the
 // next round.
 int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
-    const wmi_hparams &hp = ctx->hp;
     const int R = ctx->n_clips;
-    const int n_ctx = ctx->cur_ctx > 0 ? ctx->cur_ctx : hp.n_audio_ctx;
-    const int window = 2 * n_ctx;
-    const int n_max = std::min(max_tokens, hp.n_text_ctx / 2 - 4);
     if (!ctx->d_win) HIPCHK(ctx, hipMalloc(&ctx->d_win, 2 * DEC_ROWS * 4));
-    std::vector<int64_t> seek((size_t)R, 0);
-    std::vector<int> lang((size_t)R);
+    TrRun tr = tr_begin(ctx, R, max_tokens, false);
     for (int r = 0; r < R; ++r) {
-        lang[r] = ctx->lang_set[r];
-        ctx->lang_used[r] = lang[r];  // (AUTO: until the recording's first window detects it)
+        ctx->lang_used[r] = tr.recs[r].lang;  // (AUTO: until the recording's first window detects it)
         ctx->lang_p[r] = -1.0f;
     }
-    ctx->results.assign((size_t)R, {});
-    // the temperature fallback: each recording's attempt at its current window
-    // (a rejected recording stays at its seek and takes its next temperature
-    // in the next round), its T > 0 attempts so far, attempt 0's no-speech
-    // probability
-    ctx->windows.clear();
-    const std::vector<float> temps = ctx->fb_on ? fb_temperatures(ctx->fb) : std::vector<float>();
-    if (ctx->fb_on) ctx->windows.assign((size_t)R, {});
-    std::vector<int> att_j((size_t)R, 0);
-    std::vector<uint64_t> n_samp((size_t)R, 0);
-    std::vector<float> p_nosp0((size_t)R, 0.0f);
     std::vector<int> rows;  // recording of each decoder row
     int next = 0;
     for (;;) {
         size_t k = 0;
         for (int r : rows)
-            if (seek[r] < ctx->n_len_host[r]) rows[k++] = r;
+            if (tr.recs[r].seek < tr.recs[r].n_len) rows[k++] = r;
         rows.resize(k);
         for (; next < R && rows.size() < (size_t)DEC_ROWS; ++next)
-            if (ctx->n_len_host[next] > 0) rows.push_back(next);
+            if (tr.recs[next].n_len > 0) rows.push_back(next);
         if (rows.empty()) break;
         const int B = (int)rows.size();
         int32_t win[2 * DEC_ROWS] = {};
         for (int b = 0; b < B; ++b) {
             win[b] = rows[b];
-            win[DEC_ROWS + b] = (int32_t)seek[rows[b]];
+            win[DEC_ROWS + b] = (int32_t)tr.recs[rows[b]].seek;
         }
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_win, win, sizeof win, hipMemcpyHostToDevice, ctx->stream));
         int rc = run_encode(ctx, 0, B, ctx->d_win, ctx->d_win + DEC_ROWS);
         if (rc) return rc;
-        bool detect = false;
-        for (int b = 0; b < B; ++b) detect = detect || lang[rows[b]] == WMI_LANG_AUTO;
-        if (detect) {  // (only in a round that holds an AUTO recording's first window)
-            rc = run_lang_detect_sync(ctx);
-            if (rc) return rc;
-            int32_t det[DEC_ROWS];
-            float p[DEC_ROWS];
-            HIPCHK(ctx, hipMemcpy(det, ctx->d_lang_det, (size_t)B * 4, hipMemcpyDeviceToHost));
-            HIPCHK(ctx, hipMemcpy(p, ctx->d_lang_p, (size_t)B * 4, hipMemcpyDeviceToHost));
-            for (int b = 0; b < B; ++b)
-                if (lang[rows[b]] == WMI_LANG_AUTO) {
-                    lang[rows[b]] = det[b];
-                    ctx->lang_used[rows[b]] = det[b];
-                    ctx->lang_p[rows[b]] = p[b];
-                }
-        }
+        rc = tr_resolve_languages(ctx, tr, rows);
+        if (rc) return rc;
         std::vector<int32_t> feed;
         int np = 0;
-        for (int b = 0; b < B; ++b) {
-            const std::vector<int32_t> init = ts_init_prompt(ctx, lang[rows[b]]);
-            np = (int)init.size();
-            feed.insert(feed.end(), init.begin(), init.end());
+        for (int r : rows) {
+            const std::vector<int32_t> prompt = tr_prompt(ctx, tr.recs[r]);
+            np = (int)prompt.size();
+            feed.insert(feed.end(), prompt.begin(), prompt.end());
         }
-        std::vector<std::vector<TsRec>> toks;
-        if (ctx->fb_on) {  // every row at its recording's temperature, with its own stream key
-            TsSampled sp;
-            for (int b = 0; b < B; ++b) {
-                const int r = rows[b];
-                sp.T[b] = temps[att_j[r]];
-                if (sp.T[b] > 0.0f) sp.key[b] = sm64(ctx->fb.seed + n_samp[r]++);
-            }
-            rc = run_ts_rows(ctx, 0, B, feed, np, n_max, &toks, &sp);
-            if (rc) return rc;
-            for (int b = 0; b < B; ++b) {
-                const int r = rows[b], j = att_j[r];
-                double sum = 0.0;
-                for (float v : sp.plog[b]) sum += (double)v;
-                const FbAttempt att = fb_judge(ctx, toks[b], sum, seek[r], ctx->n_len_host[r], window);
-                if (j == 0) p_nosp0[r] = sp.p_nosp[b];
-                const bool silence = j == 0 && fb_silence(ctx, p_nosp0[r], att);
-                if (!silence && att.rejected && j + 1 < (int)temps.size()) {
-                    ++att_j[r];
-                    continue;
-                }
-                seek[r] += fb_finish_window(ctx, r, std::move(toks[b]), att, silence, sp.T[b], j + 1, p_nosp0[r], seek[r],
-                                            window, nullptr);
-                att_j[r] = 0;
-            }
-            continue;
-        }
-        rc = run_ts_rows(ctx, 0, B, feed, np, n_max, &toks);
+        std::vector<TrAttempt> att;
+        rc = tr_decode_attempt(ctx, tr, rows, feed, np, &att);
         if (rc) return rc;
-        for (int b = 0; b < B; ++b) {
-            const int r = rows[b];
-            seek[r] += finish_ts_window(ctx, std::move(toks[b]), seek[r], ctx->n_len_host[r], window, ctx->results[r],
-                                        nullptr);
-        }
+        for (int b = 0; b < B; ++b) tr_settle(ctx, tr, tr.recs[rows[b]], std::move(att[b]));
     }
     return WMI_OK;
+}
+
+// ---- what the two beam runs share ---------------------------------------------
+// a beam run's start: one active hypothesis, every row's KV history its own
+int start_beam_run(wmi_context *ctx) {
+    BeamState init{};
+    init.n_active = 1;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->dbstate, &init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->dkvsrc, ctx->kvsrc_init.data(), ctx->kvsrc_init.size() * 4, hipMemcpyHostToDevice,
+                               ctx->stream));
+    return WMI_OK;
+}
+
+// The result of a search of n_steps steps: the best score / length among the
+// first K of finished hypotheses in order, then active ones in slot order.
+// src 0: finished hypothesis i, 1: active slot i, -1: there was none.
+struct BeamPick { int src, i; };
+BeamPick pick_beam_hypothesis(const BeamState &bs, int K, int n_steps) {
+    double best = -INFINITY;
+    BeamPick pk{-1, 0};
+    int considered = 0;
+    for (int f = 0; f < bs.n_fin && considered < K; ++f, ++considered) {
+        const double sc = bs.fin_score[f] / (double)(bs.fin_t[f] > 0 ? bs.fin_t[f] : 1);
+        if (sc > best) { best = sc; pk = {0, f}; }
+    }
+    for (int a = 0; a < bs.n_active && considered < K; ++a, ++considered) {
+        const double sc = bs.score[a] / (double)n_steps;
+        if (sc > best) { best = sc; pk = {1, a}; }
+    }
+    return pk;
+}
+
+// steps 0..tlast of the hypothesis in `slot` at step tlast, through the parents' history
+template <typename T>
+std::vector<T> beam_backtrack(const std::vector<int32_t> &hpar, const std::vector<T> &hist, int tlast, int slot) {
+    std::vector<T> seq((size_t)tlast + 1);
+    for (int t = tlast; t >= 0; --t) {
+        seq[t] = hist[(size_t)t * BEAM_MAX + slot];
+        slot = hpar[(size_t)t * BEAM_MAX + slot];
+    }
+    return seq;
 }
 
 // beam search (config C5) of every encoded clip, one clip (K decoder rows) at
@@ -2709,8 +2741,6 @@ int run_beam(wmi_context *ctx, int K, int n_gen, int suppress_eot, bool early_st
     int32_t feed[64];
     for (int b = 0; b < 8; ++b)
         for (int i = 0; i < np; ++i) feed[b * np + i] = prompt[i];
-    BeamState init{};
-    init.n_active = 1;
     if (out_tokens) out_tokens->assign(Bt, {});
     if (out_scores) out_scores->assign(Bt, 0.0);
     do {
@@ -2727,9 +2757,8 @@ int run_beam(wmi_context *ctx, int K, int n_gen, int suppress_eot, bool early_st
                 rc = enqueue_prompt_feed(ctx, prompt, np, clip, 0);
                 if (rc) return rc;
             }
-            HIPCHK(ctx, hipMemcpyAsync(ctx->dbstate, &init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(ctx->dkvsrc, ctx->kvsrc_init.data(), ctx->kvsrc_init.size() * 4,
-                                       hipMemcpyHostToDevice, ctx->stream));
+            rc = start_beam_run(ctx);
+            if (rc) return rc;
             const int total_steps = np + n_gen - 1;
             int done_steps = 0;
             while (done_steps < total_steps) {
@@ -2759,35 +2788,18 @@ int run_beam(wmi_context *ctx, int K, int n_gen, int suppress_eot, bool early_st
             std::vector<int32_t> hpar((size_t)ns * BEAM_MAX), htok((size_t)ns * BEAM_MAX);
             HIPCHK(ctx, hipMemcpy(hpar.data(), ctx->dhist_par, hpar.size() * 4, hipMemcpyDeviceToHost));
             HIPCHK(ctx, hipMemcpy(htok.data(), ctx->dhist_tok, htok.size() * 4, hipMemcpyDeviceToHost));
-            auto backtrack = [&](int tlast, int slot) {
-                std::vector<int32_t> seq(tlast + 1);
-                for (int t = tlast; t >= 0; --t) {
-                    seq[t] = htok[(size_t)t * BEAM_MAX + slot];
-                    slot = hpar[(size_t)t * BEAM_MAX + slot];
-                }
-                return seq;
-            };
-            // finished hypotheses in order, then active ones in slot order, first K
-            double best = -INFINITY;
-            int best_src = -1, best_i = 0, considered = 0;
-            for (int f = 0; f < bs.n_fin && considered < K; ++f, ++considered) {
-                const double sc = bs.fin_score[f] / (double)(bs.fin_t[f] > 0 ? bs.fin_t[f] : 1);
-                if (sc > best) { best = sc; best_src = 0; best_i = f; }
-            }
-            for (int a = 0; a < bs.n_active && considered < K; ++a, ++considered) {
-                const double sc = bs.score[a] / (double)ns;
-                if (sc > best) { best = sc; best_src = 1; best_i = a; }
-            }
+            // (no hypothesis at all reads as active slot 0, as it always has)
+            const BeamPick pk = pick_beam_hypothesis(bs, K, ns);
             std::vector<int32_t> seq;
             double score;
-            if (best_src == 0) {
-                const int t = bs.fin_t[best_i];
-                if (t > 0) seq = backtrack(t - 1, bs.fin_beam[best_i]);
+            if (pk.src == 0) {
+                const int t = bs.fin_t[pk.i];
+                if (t > 0) seq = beam_backtrack(hpar, htok, t - 1, bs.fin_beam[pk.i]);
                 seq.push_back(ctx->sp.eot);
-                score = bs.fin_score[best_i];
+                score = bs.fin_score[pk.i];
             } else {
-                seq = backtrack(ns - 1, best_i);
-                score = bs.score[best_i];
+                seq = beam_backtrack(hpar, htok, ns - 1, pk.i);
+                score = bs.score[pk.i];
             }
             if (out_tokens) (*out_tokens)[clip] = seq;
             if (out_scores) (*out_scores)[clip] = score;
@@ -2825,8 +2837,6 @@ int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &p
     feed.reserve((size_t)K * np);
     for (int b = 0; b < K; ++b) feed.insert(feed.end(), prompt.begin(), prompt.end());
     ctx->ts_prompt = feed;
-    BeamState init{};
-    init.n_active = 1;
     DecRun run{RUN_BEAM, clip, K, np, np, 0, 1, K, max_tokens};
     run.ts_beam = 1;
     if (p_nosp) {  // (the fallback's attempt 0: k_no_speech behind the first generated step)
@@ -2840,9 +2850,8 @@ int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &p
         const RunGrid gr = run_grid(ctx, run);
         rc = reset_run(ctx, true, gr.G, gr.Gh, false, feed.data(), K * np);
         if (rc) return rc;
-        HIPCHK(ctx, hipMemcpyAsync(ctx->dbstate, &init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->dkvsrc, ctx->kvsrc_init.data(), ctx->kvsrc_init.size() * 4, hipMemcpyHostToDevice,
-                                   ctx->stream));
+        rc = start_beam_run(ctx);
+        if (rc) return rc;
         for (int done = 0; done < total;) {
             // (the prompt in one chunk, then 16 steps between looks at BeamState::done)
             const int chunk = std::min(done < np - 1 ? np - 1 - done + 16 : 16, total - done);
@@ -2869,35 +2878,17 @@ int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &p
     HIPCHK(ctx, hipMemcpy(hrec.data(), ctx->d_tsb_rec, hrec.size() * sizeof(TsRec), hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(frec.data(), ctx->d_tsb_rec + (size_t)hp.n_text_ctx * BEAM_MAX, frec.size() * sizeof(TsRec),
                           hipMemcpyDeviceToHost));
-    auto backtrack = [&](int tlast, int slot) {
-        std::vector<TsRec> seq((size_t)tlast + 1);
-        for (int t = tlast; t >= 0; --t) {
-            seq[t] = hrec[(size_t)t * BEAM_MAX + slot];
-            slot = hpar[(size_t)t * BEAM_MAX + slot];
-        }
-        return seq;
-    };
-    // finished hypotheses in order, then active ones in slot order, first K
-    double best = -INFINITY;
-    int best_src = -1, best_i = 0, considered = 0;
-    for (int f = 0; f < bs.n_fin && considered < K; ++f, ++considered) {
-        const double sc = bs.fin_score[f] / (double)(bs.fin_t[f] > 0 ? bs.fin_t[f] : 1);
-        if (sc > best) { best = sc; best_src = 0; best_i = f; }
-    }
-    for (int a = 0; a < bs.n_active && considered < K; ++a, ++considered) {
-        const double sc = bs.score[a] / (double)ns;
-        if (sc > best) { best = sc; best_src = 1; best_i = a; }
-    }
-    if (best_src < 0) return set_err(ctx, WMI_E_HIP, "beam search left no hypothesis");
-    if (best_src == 0) {
-        const int t = bs.fin_t[best_i];
+    const BeamPick pk = pick_beam_hypothesis(bs, K, ns);
+    if (pk.src < 0) return set_err(ctx, WMI_E_HIP, "beam search left no hypothesis");
+    if (pk.src == 0) {
+        const int t = bs.fin_t[pk.i];
         out->clear();
-        if (t > 0) *out = backtrack(t - 1, bs.fin_beam[best_i]);
-        out->push_back(frec[best_i]);
-        if (score) *score = bs.fin_score[best_i];
+        if (t > 0) *out = beam_backtrack(hpar, hrec, t - 1, bs.fin_beam[pk.i]);
+        out->push_back(frec[pk.i]);
+        if (score) *score = bs.fin_score[pk.i];
     } else {
-        *out = backtrack(ns - 1, best_i);
-        if (score) *score = bs.score[best_i];
+        *out = beam_backtrack(hpar, hrec, ns - 1, pk.i);
+        if (score) *score = bs.score[pk.i];
     }
     return WMI_OK;
 }
@@ -3244,65 +3235,67 @@ static void to_token_data(const TsRec &r, wmi_token_data *d) {
     d->t0 = -1; d->t1 = -1; d->vlen = 0.0f;  // token-level timestamps are not computed (as whisper.cpp-1.0.3 by default)
 }
 
-static int wmi_decode_timestamps_impl(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens, wmi_token_data *out,
-                          int32_t *n_out) {
-    if (!valid(ctx) || !prompt || n_prompt < 1 || !out || !n_out) return WMI_E_INVALID_ARG;
+// what the four wmi_decode_timestamps* entry points ask of their arguments
+static int check_ts_args(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens, const wmi_token_data *out,
+                         const int32_t *n_out) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (!prompt || n_prompt < 1 || max_tokens < 1 || !out || !n_out)
+        return set_err(ctx, WMI_E_INVALID_ARG, "null prompt / out / n_out, or n_prompt %d / max_tokens %d below 1", n_prompt,
+                       max_tokens);
     for (int i = 0; i < n_prompt; ++i)
         if (prompt[i] < 0 || prompt[i] >= ctx->hp.n_vocab) return set_err(ctx, WMI_E_INVALID_ARG, "token id %d", prompt[i]);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    std::vector<TsRec> rec;
-    int rc = run_ts_window(ctx, 0, std::vector<int32_t>(prompt, prompt + n_prompt), max_tokens, &rec);
-    if (rc) return rc;
+    return WMI_OK;
+}
+// a row's records as the caller's wmi_token_data
+static void copy_out_tokens(const std::vector<TsRec> &rec, wmi_token_data *out, int32_t *n_out) {
     for (size_t i = 0; i < rec.size(); ++i) to_token_data(rec[i], out + i);
     *n_out = (int32_t)rec.size();
+}
+
+static int wmi_decode_timestamps_impl(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens, wmi_token_data *out,
+                          int32_t *n_out) {
+    int rc = check_ts_args(ctx, prompt, n_prompt, max_tokens, out, n_out);
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<TsRec> rec;
+    rc = run_ts_window(ctx, 0, std::vector<int32_t>(prompt, prompt + n_prompt), max_tokens, &rec);
+    if (rc) return rc;
+    copy_out_tokens(rec, out, n_out);
     return WMI_OK;
 }
 
 static int wmi_decode_timestamps_sampled_impl(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens,
                                               float temperature, uint64_t seed, int n, wmi_token_data *out, int32_t *n_out,
                                               float *plog, float *p_nosp) {
-    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
-    if (!prompt || n_prompt < 1 || max_tokens < 1 || !out || !n_out)
-        return set_err(ctx, WMI_E_INVALID_ARG, "null prompt / out / n_out, or n_prompt %d / max_tokens %d below 1", n_prompt,
-                       max_tokens);
+    int rc = check_ts_args(ctx, prompt, n_prompt, max_tokens, out, n_out);
+    if (rc) return rc;
     if (!(temperature >= 0.0f && temperature <= 1.0f) || n < 0)
         return set_err(ctx, WMI_E_INVALID_ARG, "temperature %g outside [0, 1], or attempt ordinal %d below 0",
                        (double)temperature, n);
-    for (int i = 0; i < n_prompt; ++i)
-        if (prompt[i] < 0 || prompt[i] >= ctx->hp.n_vocab) return set_err(ctx, WMI_E_INVALID_ARG, "token id %d", prompt[i]);
-    int rc0 = samp_supported(ctx);
-    if (rc0) return rc0;
+    rc = samp_supported(ctx);
+    if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TsSampled sp;
     sp.T[0] = temperature;
     if (temperature > 0.0f) sp.key[0] = sm64(seed + (uint64_t)n);
     std::vector<std::vector<TsRec>> rows;
-    int rc = run_ts_rows(ctx, 0, 1, std::vector<int32_t>(prompt, prompt + n_prompt), n_prompt, max_tokens, &rows, &sp);
+    rc = run_ts_rows(ctx, 0, 1, std::vector<int32_t>(prompt, prompt + n_prompt), n_prompt, max_tokens, &rows, &sp);
     if (rc) return rc;
-    const std::vector<TsRec> &rec = rows[0];
-    for (size_t i = 0; i < rec.size(); ++i) {
-        to_token_data(rec[i], out + i);
-        if (plog) plog[i] = sp.plog[0][i];
-    }
-    *n_out = (int32_t)rec.size();
+    copy_out_tokens(rows[0], out, n_out);
+    if (plog) std::copy(sp.plog[0].begin(), sp.plog[0].end(), plog);
     if (p_nosp) *p_nosp = sp.p_nosp[0];
     return WMI_OK;
 }
 
 static int wmi_decode_timestamps_beam_impl(wmi_context *ctx, int beam_size, const int32_t *prompt, int n_prompt,
                                            int max_tokens, wmi_token_data *out, int32_t *n_out, double *score) {
-    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
-    if (!prompt || n_prompt < 1 || max_tokens < 1 || !out || !n_out)
-        return set_err(ctx, WMI_E_INVALID_ARG, "null prompt / out / n_out, or n_prompt %d / max_tokens %d below 1", n_prompt,
-                       max_tokens);
-    for (int i = 0; i < n_prompt; ++i)
-        if (prompt[i] < 0 || prompt[i] >= ctx->hp.n_vocab) return set_err(ctx, WMI_E_INVALID_ARG, "token id %d", prompt[i]);
+    int rc = check_ts_args(ctx, prompt, n_prompt, max_tokens, out, n_out);
+    if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::vector<TsRec> rec;
-    int rc = run_ts_beam_window(ctx, 0, std::vector<int32_t>(prompt, prompt + n_prompt), beam_size, max_tokens, &rec, score);
+    rc = run_ts_beam_window(ctx, 0, std::vector<int32_t>(prompt, prompt + n_prompt), beam_size, max_tokens, &rec, score);
     if (rc) return rc;
-    for (size_t i = 0; i < rec.size(); ++i) to_token_data(rec[i], out + i);
-    *n_out = (int32_t)rec.size();
+    copy_out_tokens(rec, out, n_out);
     return WMI_OK;
 }
 
@@ -3321,12 +3314,8 @@ static int wmi_transcribe_impl(wmi_context *ctx, const float *pcm, size_t n_samp
 
 static int wmi_decode_timestamps_batch_impl(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens,
                                             wmi_token_data *out, int32_t *n_out) {
-    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
-    if (!prompt || n_prompt < 1 || max_tokens < 1 || !out || !n_out)
-        return set_err(ctx, WMI_E_INVALID_ARG, "null prompt / out / n_out, or n_prompt %d / max_tokens %d below 1", n_prompt,
-                       max_tokens);
-    for (int i = 0; i < n_prompt; ++i)
-        if (prompt[i] < 0 || prompt[i] >= ctx->hp.n_vocab) return set_err(ctx, WMI_E_INVALID_ARG, "token id %d", prompt[i]);
+    int rc = check_ts_args(ctx, prompt, n_prompt, max_tokens, out, n_out);
+    if (rc) return rc;
     if (ctx->enc_T <= 0 || ctx->enc_clips < 1) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int Bt = ctx->enc_clips;
@@ -3335,12 +3324,9 @@ static int wmi_decode_timestamps_batch_impl(wmi_context *ctx, const int32_t *pro
         std::vector<int32_t> feed;
         for (int b = 0; b < B; ++b) feed.insert(feed.end(), prompt, prompt + n_prompt);
         std::vector<std::vector<TsRec>> rec;
-        int rc = run_ts_rows(ctx, b0, B, feed, n_prompt, max_tokens, &rec);
+        rc = run_ts_rows(ctx, b0, B, feed, n_prompt, max_tokens, &rec);
         if (rc) return rc;
-        for (int b = 0; b < B; ++b) {
-            for (size_t i = 0; i < rec[b].size(); ++i) to_token_data(rec[b][i], out + (size_t)(b0 + b) * max_tokens + i);
-            n_out[b0 + b] = (int32_t)rec[b].size();
-        }
+        for (int b = 0; b < B; ++b) copy_out_tokens(rec[b], out + (size_t)(b0 + b) * max_tokens, n_out + b0 + b);
     }
     return WMI_OK;
 }

@@ -388,6 +388,52 @@ def xsharp_lv3_hook(name: str, arr: np.ndarray) -> np.ndarray:
     return arr
 
 
+def segmenting_hook(hp: dict, scale: float = 10.0, amp: float = 60.0, eot_like=None):
+    """A hook that makes the windows of a random model alternate <|ts|> text
+    <|ts|> text ... (random weights settle on one token forever: all
+    timestamps, so no segment has text).  <|0.00|> is id n_vocab - 1501.  The
+    text rows of decoder.token_embedding are scaled by `scale`, the timestamp
+    rows are made from text rows with a unit direction u added to timestamps
+    32..63, and u is added with alternating sign and amplitude `amp` to the
+    decoder positional embedding: even steps pick a timestamp (seek_delta
+    64..126 frames), odd steps a text token.  With `eot_like` the EOT row is
+    1.05 x that text row, so windows end in EOT where that token would come."""
+    beg = hp["n_vocab"] - 1501
+    eot = 50256 + (hp["n_vocab"] >= 51865)
+    u = np.random.default_rng(5).standard_normal(hp["n_text_state"]).astype(np.float32)
+    u /= np.linalg.norm(u)
+
+    def hook(name, arr):
+        dt = arr.dtype
+        if name == "decoder.token_embedding.weight":
+            e = arr.astype(np.float32) * scale
+            j = np.arange(e.shape[0] - beg)
+            good = ((j >= 32) & (j < 64)).astype(np.float32)
+            e[beg:] = e[(j * 37) % 50000] * 0.5 + 10.0 * good[:, None] * u[None, :]
+            if eot_like is not None:
+                e[eot] = 1.05 * e[eot_like]
+            return e.astype(dt)
+        if name == "decoder.positional_embedding":
+            sgn = np.where(np.arange(arr.shape[0]) % 2 == 0, amp, -amp).astype(np.float32)
+            return (arr.astype(np.float32) + sgn[:, None] * u[None, :]).astype(dt)
+        return arr
+    return hook
+
+
+def audio_hook(inner=None):
+    """`inner`, then encoder.conv1.weight x 20 and every decoder
+    cross_attn.out.weight x 100: the tokens follow the audio, so the
+    recordings of a batch decode differently."""
+    def hook(name, arr):
+        arr = inner(name, arr) if inner else arr
+        if name == "encoder.conv1.weight":
+            return (arr.astype(np.float32) * 20.0).astype(arr.dtype)
+        if name.startswith("decoder.blocks.") and name.endswith(".cross_attn.out.weight"):
+            return (arr.astype(np.float32) * 100.0).astype(arr.dtype)
+        return arr
+    return hook
+
+
 LNMEAN_OFFSET = 16.0
 
 
