@@ -349,6 +349,67 @@ typedef struct wmi_window_info {
 int wmi_get_window_count(const wmi_context *ctx, int clip, int32_t *n);
 int wmi_get_window_info(const wmi_context *ctx, int clip, int i, wmi_window_info *out);
 
+/* OpenAI's decoding rules (SuppressTokens and ApplyTimestampRules restated)
+ * for every window of wmi_transcribe / wmi_transcribe_batch and for
+ * wmi_decode_timestamps_ruled, in the place of the whisper.cpp-1.0.3 rule.
+ * Per decoder row and generated-token index t, s[0..t) the ids the row has
+ * sampled in this window, all arithmetic in float64 on the f32 logits:
+ *   M0 masked always: sot, prev, solm, not, translate, transcribe, every
+ *      language id, the suppress list (with suppress_non_speech also
+ *      wmi_non_speech_tokens).
+ *   M1 last = s[t-1] is a timestamp, penult = t < 2 or s[t-2] is one.
+ *      last and penult: no timestamp.  last and not penult: no id below eot
+ *      (a timestamp or EOT follows).  x = the last timestamp sampled: no
+ *      timestamp below x (last and not penult) or below x + 1 (otherwise).
+ *   M2 t = 0: timestamps only, none above beg + max_initial_ts (if >= 0).
+ * Over the ids left (A'): sum_ts = P(timestamps), p_tx = the largest P of an id
+ * below beg (EOT included); the pick is among the timestamps of A' if sum_ts >
+ * p_tx, else among A': its argmax at temperature 0 (ties: lowest id), the
+ * draw of wmi_decode_timestamps_sampled otherwise.  Records: tid = id for a
+ * timestamp, else the likeliest timestamp of A' (of all, with pt 0, if A'
+ * holds none); p, pt and ptsum under the softmax over A'; the log-probability
+ * under the softmax over the set picked from.  SuppressBlank is not built: it
+ * acts on the first token only, which M2 restricts to timestamps.
+ * enable 0 (also params = NULL): every call decodes exactly as without this
+ * interface (the same kernels).  A suppress id outside [0, eot):
+ * WMI_E_INVALID_ARG; the vocabulary conditions of wmi_set_fallback:
+ * WMI_E_UNSUPPORTED.  With rules enabled a beam size above 1 is
+ * WMI_E_UNSUPPORTED in wmi_transcribe and wmi_decode_timestamps_beam (the
+ * mask would have to follow each hypothesis through the parent selection).
+ * Holds until changed. */
+typedef struct wmi_decode_rules {
+    int32_t enable;               /* 0 (default, also params = NULL): the sampler as before */
+    int32_t max_initial_ts;       /* first timestamp <= beg + this, in 20 ms units; < 0: no cap (OpenAI: 50) */
+    int32_t suppress_non_speech;  /* add wmi_non_speech_tokens to the list */
+    const int32_t *suppress;      /* copied */
+    int32_t n_suppress;
+} wmi_decode_rules;
+int wmi_set_decode_rules(wmi_context *ctx, const wmi_decode_rules *params);
+/* The ids below eot whose token bytes are exactly s or " " + s for s one of
+ * " # ( ) * + / : ; < = > @ [ \ ] ^ _ ` { | } ~ 「 」 『 』 << >> <<< >>> -- ---
+ * -( -[ (' (" (( )) ((( ))) [[ ]] {{ }} ♪♪ ♪♪♪ ♩ ♪ ♫ ♬ ♭ ♮ ♯, and the tokens " -"
+ * and " '" (whisper.cpp's list; a vocabulary lookup, host only): ascending,
+ * unique.  *n = their count; WMI_E_NO_SPACE if cap is below it (ids may be
+ * NULL to ask for the count). */
+int wmi_non_speech_tokens(const wmi_context *ctx, int32_t *ids, size_t cap, int32_t *n);
+/* 1 if the len bytes are one of those tokens, else 0 (the lookup's test of one
+ * vocabulary entry; needs no context and no device). */
+int wmi_is_non_speech_token(const char *bytes, size_t len);
+/* wmi_decode_timestamps_sampled under the rules set (WMI_E_INVALID_ARG if
+ * none are enabled). */
+int wmi_decode_timestamps_ruled(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens,
+                                float temperature, uint64_t seed, int n, wmi_token_data *out, int32_t *n_out,
+                                float *plog, float *p_nosp);
+/* Text ids (below eot, else WMI_E_INVALID_ARG) in front of the text context
+ * of wmi_transcribe: window 0 decodes from [prev] + ids + [sot ..], later
+ * windows see the tail of ids + text (at most n_text_ctx / 2 ids, of which
+ * the last are kept here too); a fallback result of T > 0.5 clears them with
+ * the rest.  With wmi_set_no_context(1) and in wmi_transcribe_batch (one
+ * prompt for all recordings) every window decodes from [prev] + ids +
+ * [sot ..] — OpenAI prompts the first window only; this keeps the rows of a
+ * batch at one decoder position.  n = 0 clears.  Independent of the rules. */
+int wmi_set_initial_prompt(wmi_context *ctx, const int32_t *ids, int n);
+
 /* ---- device-resident benchmark path --------------------------------- */
 
 /* Upload n_clips PCM clips to HBM once (untimed). */
@@ -424,8 +485,10 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * window), 20 = the windows and the decoder steps of the last wmi_transcribe
  * (int64 [2], host; every attempt's steps under wmi_set_fallback, and a third
  * int64: the attempts).  13 to 15 also hold the last wmi_decode_timestamps_beam
- * window; 13 also the last sampled window (wmi_decode_timestamps_sampled, a
- * window of wmi_transcribe under wmi_set_fallback; row b in row b). */
+ * window; 13 also the last sampled or ruled window
+ * (wmi_decode_timestamps_sampled, wmi_decode_timestamps_ruled, a window of
+ * wmi_transcribe under wmi_set_fallback or wmi_set_decode_rules; row b in
+ * row b). */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <map>
 #include <memory>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -239,6 +240,12 @@ struct wmi_context {
     std::vector<std::vector<wmi_window_info>> windows;  // per recording of the last transcribe under fb_on
     int32_t *d_win = nullptr;   // batched transcription: source recording [8], then mel offset [8] of each encoder slot
     bool no_context = false;    // wmi_set_no_context: windows of wmi_transcribe take no earlier text
+    // OpenAI decoding rules (wmi_set_decode_rules) and the initial prompt (wmi_set_initial_prompt)
+    bool rules_on = false;
+    int max_initial_ts = -1;
+    uint32_t *d_rule_m0 = nullptr;      // [ceil(n_vocab / 32)] bit i: id i is masked always
+    RuleHist *d_rule_hist = nullptr;    // [8] the rows' history (same allocation, behind dts_done)
+    std::vector<int32_t> init_prompt;   // text ids in front of the first window's context
     struct Segment { int64_t t0, t1; int first, count; std::string text; };
     struct SegList {
         std::vector<Segment> segments;  // result_all (main.rs:353)
@@ -1394,6 +1401,7 @@ struct DecRun {
     int mk = 512;                 // key capacity of the self-attention launch being enqueued (run_dec_steps)
     int ts_beam = 0;              // RUN_BEAM: the hypotheses follow the timestamp rule and keep token records
     int sampled = 0;              // RUN_TS: the temperature sampler (k_ts_sample_t) with the rows' T and keys in d_samp_rows
+    int ruled = 0;                // RUN_TS with sampled: that sampler under the decoding rules (k_ts_sample_r)
     int nosp = 0;                 // RUN_BEAM with ts_beam: the first generated step also yields the no-speech probability
 };
 
@@ -1436,6 +1444,12 @@ int enqueue_step_tail(wmi_context *ctx, const DecRun &run) {
         TsSampArgs sa{};
         sa.t = ts_args(ctx, run);
         sa.rows = ctx->d_samp_rows; sa.plog = ctx->d_samp_plog; sa.p_nosp = ctx->d_samp_nosp;
+        if (run.ruled) {
+            TsRuleArgs ra{};
+            ra.s = sa; ra.m0 = ctx->d_rule_m0; ra.hist = ctx->d_rule_hist; ra.max_initial_ts = ctx->max_initial_ts;
+            HIPCHK(ctx, launch_ts_sample_r(ctx->stream, ra));
+            return WMI_OK;
+        }
         HIPCHK(ctx, launch_ts_sample_t(ctx->stream, sa));
         return WMI_OK;
     }
@@ -1665,7 +1679,7 @@ int run_dec_steps(wmi_context *ctx, const DecRun &run0, int pos0, int steps) {
             snprintf(key, sizeof key, "%d/%d/%d/%d/%d/%d/%d/%d/%p/%p/%d/%d/%d/%d/%d", run.b0, run.B, run.feed_len,
                      run.feed_stride, run.suppress_eot, run.out_stride, ctx->enc_T, ctx->enc_clips, (void *)ctx->dfeed,
                      (void *)ctx->dtokens, run.K, run.max_tokens, mk,
-                     run.kind == RUN_TS ? (run.sampled ? 3 : 1) : run.ts_beam ? (run.nosp ? 4 : 2) : 0, reps);
+                     run.kind == RUN_TS ? (run.ruled ? 5 : run.sampled ? 3 : 1) : run.ts_beam ? (run.nosp ? 4 : 2) : 0, reps);
             auto it = ctx->graphs.find(key);
             if (it == ctx->graphs.end()) {
                 if (ctx->graphs.size() >= 32) ctx->clear_graphs();
@@ -1850,11 +1864,11 @@ PersistArgs persist_args(wmi_context *ctx, const DecRun &run, int G) {
 // the error word once per run (`first` block, unless language detection has
 // run in front and zeroed it: the caller reads the word after its own
 // launches), step state, argmax shards, chain sync words, a timestamp run's
-// done words, and the exchange
+// done words (and a ruled run's row histories), and the exchange
 // blocks of a persistent grid G (and of the split grids Gh).  A feed of up to
 // 64 words rides in the launch; a longer one is copied.
 int reset_run(wmi_context *ctx, bool first, int G, int Gh, bool err_cleared, const int32_t *feed, int n_feed,
-              bool ts = false) {
+              bool ts = false, bool ruled = false) {
     ResetArgs ra{};
     auto zero = [&](void *p, size_t bytes) {
         ra.ptr[ra.n] = p;
@@ -1871,7 +1885,8 @@ int reset_run(wmi_context *ctx, bool first, int G, int Gh, bool err_cleared, con
     zero(ctx->dstate, sizeof(DecState));
     zero(ctx->damax, 8 * AMAX_SHARDS * 8);
     zero(ctx->dsync, ctx->sync_bytes);
-    if (ts) zero(ctx->dts_done, DEC_ROWS * 4);  // (a timestamp run: no row has met EOT)
+    // (a timestamp run: no row has met EOT; a ruled one: nor sampled anything, the histories lie behind the done words)
+    if (ts) zero(ctx->dts_done, DEC_ROWS * 4 + (ruled ? DEC_ROWS * sizeof(RuleHist) : 0));
     if (G > 0) zero(ctx->d_xg, ctx->xg_bytes);
     if (Gh > 0) {
         zero(ctx->d_xg2, ctx->xg_bytes);
@@ -2182,7 +2197,9 @@ bool valid(const wmi_context *ctx) { return ctx != nullptr && ctx->d_model != nu
 // With `samp` the run is a sampled one (k_ts_sample_t): row b decodes at
 // temperature samp->T[b] with the draws of stream key samp->key[b], and the
 // run also yields each record's log-probability and each row's no-speech
-// probability.
+// probability.  With `ruled` (only together with `samp`; T = 0 rows where no
+// fallback is set) that sampler is k_ts_sample_r under the context's decoding
+// rules: the reset launch zeroes the rows' histories with their done words.
 struct TsSampled {
     float T[DEC_ROWS] = {};
     uint64_t key[DEC_ROWS] = {};
@@ -2219,7 +2236,7 @@ int ensure_samp_buffers(wmi_context *ctx) {
 }
 
 int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &feed, int np, int max_tokens,
-                std::vector<std::vector<TsRec>> *out, TsSampled *samp = nullptr) {
+                std::vector<std::vector<TsRec>> *out, TsSampled *samp = nullptr, bool ruled = false) {
     const wmi_hparams &hp = ctx->hp;
     if (ctx->enc_T <= 0) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
     if (B < 1 || B > DEC_ROWS || b0 < 0 || b0 + B > ctx->enc_clips)
@@ -2228,9 +2245,11 @@ int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &fee
         return set_err(ctx, WMI_E_INVALID_ARG, "prompt %d + max_tokens %d exceed n_text_ctx %d", np, max_tokens,
                        hp.n_text_ctx);
     if (!ctx->dts_tok) {
-        HIPCHK(ctx, hipMalloc(&ctx->dts_tok, 2 * DEC_ROWS * 4));
-        HIPCHK(ctx, hipMemset(ctx->dts_tok, 0, 2 * DEC_ROWS * 4));
+        const size_t nb = 2 * DEC_ROWS * 4 + DEC_ROWS * sizeof(RuleHist);
+        HIPCHK(ctx, hipMalloc(&ctx->dts_tok, nb));
+        HIPCHK(ctx, hipMemset(ctx->dts_tok, 0, nb));
         ctx->dts_done = ctx->dts_tok + DEC_ROWS;
+        ctx->d_rule_hist = (RuleHist *)(ctx->dts_done + DEC_ROWS);
         HIPCHK(ctx, hipMalloc(&ctx->dts_rec, (size_t)DEC_ROWS * hp.n_text_ctx * sizeof(TsRec)));
         ctx->clear_graphs();
     }
@@ -2243,13 +2262,14 @@ int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &fee
         rc = ensure_samp_buffers(ctx);
         if (rc) return rc;
         run.sampled = 1;
+        run.ruled = ruled ? 1 : 0;
         for (int b = 0; b < B; ++b) { srows[b].T = samp->T[b]; srows[b].key = samp->key[b]; }
     }
     const int total = np + max_tokens - 1;
     int have = 0;
     do {
         const RunGrid gr = run_grid(ctx, run);
-        rc = reset_run(ctx, true, gr.G, gr.Gh, false, feed.data(), B * np, true);
+        rc = reset_run(ctx, true, gr.G, gr.Gh, false, feed.data(), B * np, true, run.ruled != 0);
         if (rc) return rc;
         if (samp) HIPCHK(ctx, hipMemcpyAsync(ctx->d_samp_rows, srows, sizeof srows, hipMemcpyHostToDevice, ctx->stream));
         have = 0;
@@ -2461,7 +2481,10 @@ TrRun tr_begin(wmi_context *ctx, int R, int max_tokens, bool carry) {
     tr.window = 2 * (ctx->cur_ctx > 0 ? ctx->cur_ctx : hp.n_audio_ctx);
     tr.n_max = std::min(max_tokens, hp.n_text_ctx / 2 - 4);
     if (ctx->fb_on) tr.temps = fb_temperatures(ctx->fb);
-    for (int r = 0; r < R; ++r) tr.recs.push_back({r, 0, ctx->n_len_host[r], ctx->lang_set[r], -1.0f, carry, {}, 0, 0, 0.0f});
+    // (with text context the initial prompt seeds it: window 0 sees it, later windows the tail of it + text)
+    for (int r = 0; r < R; ++r)
+        tr.recs.push_back({r, 0, ctx->n_len_host[r], ctx->lang_set[r], -1.0f, carry,
+                           carry ? ctx->init_prompt : std::vector<int32_t>{}, 0, 0, 0.0f});
     ctx->results.assign((size_t)R, {});
     ctx->windows.clear();
     if (ctx->fb_on) ctx->windows.assign((size_t)R, {});
@@ -2493,13 +2516,15 @@ int tr_resolve_languages(wmi_context *ctx, TrRun &tr, const std::vector<int> &ro
 }
 
 // a window's prompt: [prev] + the last min(n_text_ctx / 2, past) earlier tokens
-// (whisper_full's n_take; none without text context) + [sot (, language, task)]
+// (whisper_full's n_take; without text context the initial prompt, if any, in
+// every window: the rows of a batch stay at one position) + [sot (, language, task)]
 std::vector<int32_t> tr_prompt(const wmi_context *ctx, const TrRec &rec) {
     std::vector<int32_t> prompt;
-    if (!rec.past.empty()) {
+    const std::vector<int32_t> &past = rec.carry ? rec.past : ctx->init_prompt;
+    if (!past.empty()) {
         prompt.push_back(ctx->sp.prev);
-        const size_t keep = std::min(rec.past.size(), (size_t)(ctx->hp.n_text_ctx / 2));
-        prompt.insert(prompt.end(), rec.past.end() - keep, rec.past.end());
+        const size_t keep = std::min(past.size(), (size_t)(ctx->hp.n_text_ctx / 2));
+        prompt.insert(prompt.end(), past.end() - keep, past.end());
     }
     const std::vector<int32_t> init = ts_init_prompt(ctx, rec.lang);
     prompt.insert(prompt.end(), init.begin(), init.end());
@@ -2515,7 +2540,8 @@ struct TrAttempt {
 // The recordings `rows` sit in the encoded rows 0..B-1 and row b is fed the np
 // tokens feed[b * np ..): each row's attempt at its recording's temperature.
 // Fallback off: the plain sampler (k_ts_sample), or with a beam size the beam
-// window, neither with quality figures.  Fallback on: every row through the
+// window, neither with quality figures.  Decoding rules on (never with a beam
+// size): k_ts_sample_r in the place of either sampler.  Fallback on: every row through the
 // temperature sampler (at T = 0 too) with its own stream key; with a beam
 // size a T = 0 attempt is the beam window with k_no_speech behind it.
 int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows, const std::vector<int32_t> &feed, int np,
@@ -2535,8 +2561,10 @@ int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows,
         sp.T[b] = (*out)[b].T;
         if (sp.T[b] > 0.0f) sp.key[b] = sm64(ctx->fb.seed + tr.recs[rows[b]].n_samp++);
     }
+    // (under the decoding rules every row goes through k_ts_sample_r: fallback off at T = 0, no figures kept)
+    const bool ruled = ctx->rules_on;
     std::vector<std::vector<TsRec>> toks;
-    int rc = run_ts_rows(ctx, 0, B, feed, np, tr.n_max, &toks, fb ? &sp : nullptr);
+    int rc = run_ts_rows(ctx, 0, B, feed, np, tr.n_max, &toks, fb || ruled ? &sp : nullptr, ruled);
     if (rc) return rc;
     for (int b = 0; b < B; ++b) {
         TrAttempt &a = (*out)[b];
@@ -2630,7 +2658,8 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
 // list.  Per round the active recordings sit compacted in rows 0..B-1: one
 // encode of the B slots, each at its recording's seek (k_mel_window's per-slot
 // source and offset), one lockstep timestamp window of B rows — every prompt
-// is [sot (, language, task)], so the rows share the decoder's one position —
+// is [sot (, language, task)], after [prev] + the one initial prompt if there
+// is one, so the rows share the decoder's one position —
 // then each row's tr_settle.  A recording that reached its end leaves its
 // row; a waiting one takes a free row at the next round; under the fallback a
 // rejected recording stays at its seek and takes its next temperature in the
@@ -3053,6 +3082,7 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->d_tsb_rec) (void)hipFree(ctx->d_tsb_rec);
     if (ctx->d_win) (void)hipFree(ctx->d_win);
     if (ctx->d_samp_rows) (void)hipFree(ctx->d_samp_rows);
+    if (ctx->d_rule_m0) (void)hipFree(ctx->d_rule_m0);
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -3287,9 +3317,44 @@ static int wmi_decode_timestamps_sampled_impl(wmi_context *ctx, const int32_t *p
     return WMI_OK;
 }
 
+// A history-dependent mask needs per-hypothesis state that follows the beam
+// step's parent selection (the follow-up work); no silent fall-back to the
+// old rule, as for a beam size in wmi_transcribe_batch.
+static int rules_beam_unsupported(wmi_context *ctx, int beam_size) {
+    if (ctx->rules_on && beam_size > 1)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "the decoding rules are not built into the beam window: beam size %d is set "
+                       "(wmi_set_beam_size(ctx, 1), or wmi_set_decode_rules(ctx, NULL))", beam_size);
+    return WMI_OK;
+}
+
+// wmi_decode_timestamps_sampled under the context's decoding rules
+static int wmi_decode_timestamps_ruled_impl(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens,
+                                            float temperature, uint64_t seed, int n, wmi_token_data *out, int32_t *n_out,
+                                            float *plog, float *p_nosp) {
+    int rc = check_ts_args(ctx, prompt, n_prompt, max_tokens, out, n_out);
+    if (rc) return rc;
+    if (!(temperature >= 0.0f && temperature <= 1.0f) || n < 0)
+        return set_err(ctx, WMI_E_INVALID_ARG, "temperature %g outside [0, 1], or attempt ordinal %d below 0",
+                       (double)temperature, n);
+    if (!ctx->rules_on) return set_err(ctx, WMI_E_INVALID_ARG, "no decoding rules are enabled (wmi_set_decode_rules)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    TsSampled sp;
+    sp.T[0] = temperature;
+    if (temperature > 0.0f) sp.key[0] = sm64(seed + (uint64_t)n);
+    std::vector<std::vector<TsRec>> rows;
+    rc = run_ts_rows(ctx, 0, 1, std::vector<int32_t>(prompt, prompt + n_prompt), n_prompt, max_tokens, &rows, &sp, true);
+    if (rc) return rc;
+    copy_out_tokens(rows[0], out, n_out);
+    if (plog) std::copy(sp.plog[0].begin(), sp.plog[0].end(), plog);
+    if (p_nosp) *p_nosp = sp.p_nosp[0];
+    return WMI_OK;
+}
+
 static int wmi_decode_timestamps_beam_impl(wmi_context *ctx, int beam_size, const int32_t *prompt, int n_prompt,
                                            int max_tokens, wmi_token_data *out, int32_t *n_out, double *score) {
     int rc = check_ts_args(ctx, prompt, n_prompt, max_tokens, out, n_out);
+    if (rc) return rc;
+    rc = rules_beam_unsupported(ctx, beam_size);
     if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::vector<TsRec> rec;
@@ -3301,6 +3366,8 @@ static int wmi_decode_timestamps_beam_impl(wmi_context *ctx, int beam_size, cons
 
 static int wmi_transcribe_impl(wmi_context *ctx, const float *pcm, size_t n_samples, int max_tokens, int32_t *n_segments) {
     if (!valid(ctx) || (!pcm && n_samples) || max_tokens < 1 || !n_segments) return WMI_E_INVALID_ARG;
+    int rcr = rules_beam_unsupported(ctx, ctx->beam_size);
+    if (rcr) return rcr;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const float *pp[1] = {pcm};
     const size_t nn[1] = {n_samples};
@@ -3359,6 +3426,105 @@ int wmi_set_no_context(wmi_context *ctx, int no_context) {
     if (no_context != 0 && no_context != 1) return set_err(ctx, WMI_E_INVALID_ARG, "no_context %d is neither 0 nor 1", no_context);
     ctx->no_context = no_context != 0;
     return WMI_OK;
+}
+
+// whisper.cpp's non_speech_tokens: symbols whose tokens (bare or after a space) the rules may suppress
+static const char *const NON_SPEECH[] = {
+    "\"", "#", "(", ")", "*", "+", "/", ":", ";", "<", "=", ">", "@", "[", "\\", "]", "^", "_", "`", "{", "|", "}", "~",
+    "\xe3\x80\x8c", "\xe3\x80\x8d", "\xe3\x80\x8e", "\xe3\x80\x8f",
+    "<<", ">>", "<<<", ">>>", "--", "---", "-(", "-[", "('", "(\"", "((", "))", "(((", ")))", "[[", "]]", "{{", "}}",
+    "\xe2\x99\xaa\xe2\x99\xaa", "\xe2\x99\xaa\xe2\x99\xaa\xe2\x99\xaa",
+    "\xe2\x99\xa9", "\xe2\x99\xaa", "\xe2\x99\xab", "\xe2\x99\xac", "\xe2\x99\xad", "\xe2\x99\xae", "\xe2\x99\xaf"};
+
+static const std::set<std::string> &non_speech_set() {
+    static const std::set<std::string> want = [] {
+        std::set<std::string> w{" -", " '"};
+        for (const char *s : NON_SPEECH) {
+            w.insert(s);
+            w.insert(std::string(" ") + s);
+        }
+        return w;
+    }();
+    return want;
+}
+
+int wmi_is_non_speech_token(const char *bytes, size_t len) {
+    return guarded(nullptr, [&] { return bytes && non_speech_set().count(std::string(bytes, len)) ? 1 : 0; });
+}
+
+static std::vector<int32_t> non_speech_ids(const wmi_context *ctx) {
+    const std::set<std::string> &want = non_speech_set();
+    std::vector<int32_t> ids;
+    const int32_t n = std::min<int32_t>(ctx->sp.eot, (int32_t)ctx->vocab.size());
+    for (int32_t i = 0; i < n; ++i)
+        if (want.count(ctx->vocab[i])) ids.push_back(i);
+    return ids;
+}
+
+int wmi_non_speech_tokens(const wmi_context *ctx, int32_t *ids, size_t cap, int32_t *n) {
+    return guarded(const_cast<wmi_context *>(ctx), [&] {
+        if (!valid(ctx) || !n) return (int)WMI_E_INVALID_ARG;
+        const std::vector<int32_t> v = non_speech_ids(ctx);
+        *n = (int32_t)v.size();
+        if (!ids || cap < v.size()) return (int)WMI_E_NO_SPACE;
+        std::copy(v.begin(), v.end(), ids);
+        return (int)WMI_OK;
+    });
+}
+
+static int wmi_set_decode_rules_impl(wmi_context *ctx, const wmi_decode_rules *params) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (!params || !params->enable) {
+        ctx->rules_on = false;
+        return WMI_OK;
+    }
+    const wmi_special_tokens &sp = ctx->sp;
+    const int V = ctx->hp.n_vocab;
+    if (params->n_suppress < 0 || (params->n_suppress > 0 && !params->suppress))
+        return set_err(ctx, WMI_E_INVALID_ARG, "suppress list: %d ids, null pointer", params->n_suppress);
+    for (int i = 0; i < params->n_suppress; ++i)
+        if (params->suppress[i] < 0 || params->suppress[i] >= sp.eot)
+            return set_err(ctx, WMI_E_INVALID_ARG, "suppress id %d outside [0, eot = %d)", params->suppress[i], sp.eot);
+    int rc = samp_supported(ctx);
+    if (rc) return rc;
+    if (sp.eot < 0 || sp.eot >= sp.beg || V < sp.beg + 2)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "the decoding rules need eot below beg (%d, %d) and two timestamps (n_vocab %d)",
+                       sp.eot, sp.beg, V);
+    // M0: the ids no step may sample
+    std::vector<uint32_t> m0((size_t)(V + 31) / 32, 0u);
+    auto mask = [&](int32_t i) {  // (never EOT or a timestamp: the allowed set must not run empty)
+        if (i >= 0 && i < sp.beg && i != sp.eot) m0[(size_t)i >> 5] |= 1u << (i & 31);
+    };
+    for (int32_t i : {sp.sot, sp.prev, sp.solm, sp.not_, sp.translate, sp.transcribe}) mask(i);
+    for (int i = 1; i <= ctx->n_lang; ++i) mask(sp.sot + i);
+    for (int i = 0; i < params->n_suppress; ++i) mask(params->suppress[i]);
+    if (params->suppress_non_speech)
+        for (int32_t i : non_speech_ids(ctx)) mask(i);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (!ctx->d_rule_m0) HIPCHK(ctx, hipMalloc(&ctx->d_rule_m0, m0.size() * 4));
+    HIPCHK(ctx, hipMemcpy(ctx->d_rule_m0, m0.data(), m0.size() * 4, hipMemcpyHostToDevice));
+    ctx->max_initial_ts = params->max_initial_ts < 0 ? -1 : params->max_initial_ts;
+    ctx->rules_on = true;
+    ctx->clear_graphs();  // (a cached step graph holds the cap it was captured with)
+    return WMI_OK;
+}
+
+int wmi_set_decode_rules(wmi_context *ctx, const wmi_decode_rules *params) {
+    return guarded(ctx, [&] { return wmi_set_decode_rules_impl(ctx, params); });
+}
+
+int wmi_set_initial_prompt(wmi_context *ctx, const int32_t *ids, int n) {
+    return guarded(ctx, [&] {
+        if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+        if (n < 0 || (n > 0 && !ids)) return set_err(ctx, WMI_E_INVALID_ARG, "initial prompt: %d ids, null pointer", n);
+        for (int i = 0; i < n; ++i)
+            if (ids[i] < 0 || ids[i] >= ctx->sp.eot)
+                return set_err(ctx, WMI_E_INVALID_ARG, "initial prompt id %d is no text id (eot = %d)", ids[i], ctx->sp.eot);
+        const int keep = std::min(n, ctx->hp.n_text_ctx / 2);  // (the take rule of a window's earlier text)
+        ctx->init_prompt.assign(ids + (n - keep), ids + n);
+        return (int)WMI_OK;
+    });
 }
 
 int wmi_set_fallback(wmi_context *ctx, const wmi_fallback_params *params) {
@@ -4022,6 +4188,14 @@ int wmi_decode_timestamps_sampled(wmi_context *ctx, const int32_t *prompt, int n
     return guarded(ctx, [&] {
         return wmi_decode_timestamps_sampled_impl(ctx, prompt, n_prompt, max_tokens, temperature, seed, n, out, n_out, plog,
                                                   p_nosp);
+    });
+}
+
+int wmi_decode_timestamps_ruled(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens, float temperature,
+                                uint64_t seed, int n, wmi_token_data *out, int32_t *n_out, float *plog, float *p_nosp) {
+    return guarded(ctx, [&] {
+        return wmi_decode_timestamps_ruled_impl(ctx, prompt, n_prompt, max_tokens, temperature, seed, n, out, n_out, plog,
+                                                p_nosp);
     });
 }
 

@@ -330,6 +330,21 @@ struct TsSampArgs {
     float *p_nosp;           // [B] P(solm) under the unmasked softmax of the first generated step
 };
 hipError_t launch_ts_sample_t(hipStream_t s, const TsSampArgs &a);
+// ---- the sampler under OpenAI's decoding rules (wmi_rules.hip; DESIGN.md
+// "OpenAI decoding rules"): k_ts_sample_t's conventions, the allowed set from
+// the suppress bitmask and the row's history of this window ----------------
+struct RuleHist {            // per decoder row, in device memory behind the rows' done words (reset with them)
+    int32_t last, pen;       // the last / the last but one sampled id was a timestamp
+    int32_t lts1;            // the last timestamp sampled + 1 (0: none yet)
+    int32_t pad;
+};
+struct TsRuleArgs {
+    TsSampArgs s;
+    const uint32_t *m0;      // [ceil(V / 32)] bit i set: id i is masked always (M0)
+    RuleHist *hist;          // [B]
+    int max_initial_ts;      // first timestamp <= beg + this (< 0: no cap)
+};
+hipError_t launch_ts_sample_r(hipStream_t s, const TsRuleArgs &a);
 struct NoSpeechArgs {        // a beam window's no-speech probability (row 0 of its first generated step)
     const float *logits;     // [V]
     int V, solm, feed_len;

@@ -272,9 +272,10 @@ def quantize_q5_1(w: np.ndarray) -> bytes:
 
 def write_ggml(path: str, model: str = "base", hp_override: dict | None = None,
                wscale: float = 0.02, n_vocab_file: int | None = None, tensor_hook=None,
-               quant: str | None = None) -> dict:
+               quant: str | None = None, vocab_replace: dict | None = None) -> dict:
     """Write a synthetic ggml-v1 Whisper file; returns the hparams used.
     tensor_hook(name, array) -> array may edit tensors before they are written.
+    vocab_replace {id: bytes} replaces those entries of the file's vocabulary.
     quant "f32" writes an ftype-0 file (hparams.f16 = 0: every matrix and conv
     kernel f32, main.rs:817-821); "q5_1", "q8_0", ... store every 2-D weight matrix in that ggml block format,
     as whisper.cpp's quantize tool does (conv kernels, biases, LN parameters
@@ -296,7 +297,9 @@ def write_ggml(path: str, model: str = "base", hp_override: dict | None = None,
         f.write(struct.pack("<ii", filt.shape[0], filt.shape[1]))
         f.write(filt.astype("<f4").tobytes())
         f.write(struct.pack("<i", n_vocab_file))
-        for tok in _vocab_tokens(n_vocab_file):
+        for i, tok in enumerate(_vocab_tokens(n_vocab_file)):
+            if vocab_replace and i in vocab_replace:
+                tok = vocab_replace[i]
             f.write(struct.pack("<I", len(tok)))
             f.write(tok)
         for name, shape, kind in tensor_specs(hp):

@@ -67,6 +67,8 @@ EXPORTS = (
     "wmi_set_no_context", "wmi_decode_timestamps_batch", "wmi_transcribe_batch", "wmi_get_segment_of",
     "wmi_get_segment_tokens_of", "wmi_decode_timestamps_beam", "wmi_set_beam_size",
     "wmi_set_fallback", "wmi_decode_timestamps_sampled", "wmi_get_window_count", "wmi_get_window_info",
+    "wmi_set_decode_rules", "wmi_non_speech_tokens", "wmi_decode_timestamps_ruled", "wmi_set_initial_prompt",
+    "wmi_is_non_speech_token",
     "wmi_pcm_to_mel", "wmi_pcm_to_mel_batch", "wmi_encode", "wmi_decode_greedy", "wmi_decode_logits",
     "wmi_decode_beam", "wmi_full", "wmi_stage_pcm", "wmi_run_staged", "wmi_run_staged_beam", "wmi_get_tokens", "wmi_get_timings", "wmi_sync",
     "wmi_get_mel", "wmi_get_checksums", "wmi_get_encoder_out", "wmi_get_cross_kv", "wmi_bench_kernel", "wmi_decode_alg_bytes",
@@ -106,6 +108,12 @@ class FallbackParams(C.Structure):
     """wmi_fallback_params."""
     _fields_ = [("temperature", C.c_float), ("temperature_inc", C.c_float), ("logprob_thold", C.c_float),
                 ("entropy_thold", C.c_float), ("no_speech_thold", C.c_float), ("seed", C.c_uint64)]
+
+
+class DecodeRules(C.Structure):
+    """wmi_decode_rules."""
+    _fields_ = [("enable", C.c_int32), ("max_initial_ts", C.c_int32), ("suppress_non_speech", C.c_int32),
+                ("suppress", C.c_void_p), ("n_suppress", C.c_int32)]
 
 
 class WindowInfo(C.Structure):
@@ -165,6 +173,14 @@ def lib():
         L.wmi_set_fallback.argtypes = [vp, C.POINTER(FallbackParams)]
         L.wmi_decode_timestamps_sampled.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, vp,
                                                     C.POINTER(i32), vp, C.POINTER(C.c_float)]
+        # (an older build selected with WMI_LIB for an A/B run, scripts/lib_equal.py, has no decoding rules;
+        # calling them on it raises AttributeError)
+        if hasattr(L, "wmi_set_decode_rules"):
+            L.wmi_set_decode_rules.argtypes = [vp, C.POINTER(DecodeRules)]
+            L.wmi_non_speech_tokens.argtypes = [vp, vp, sz, C.POINTER(i32)]
+            L.wmi_decode_timestamps_ruled.argtypes = L.wmi_decode_timestamps_sampled.argtypes
+            L.wmi_set_initial_prompt.argtypes = [vp, vp, C.c_int]
+            L.wmi_is_non_speech_token.argtypes = [C.c_char_p, sz]
         L.wmi_get_window_count.argtypes = [vp, C.c_int, C.POINTER(i32)]
         L.wmi_get_window_info.argtypes = [vp, C.c_int, C.c_int, C.POINTER(WindowInfo)]
         L.wmi_decode_timestamps_batch.argtypes =[vp, vp, C.c_int, C.c_int, vp, vp]
@@ -210,6 +226,12 @@ def _raise(rc: int, ctx=None):
     msg = (L.wmi_last_error(ctx) if ctx else L.wmi_last_error_global()) or b""
     cls = _ERRORS.get(rc, WsError)
     raise cls(f"{L.wmi_strerror(rc).decode()}: {msg.decode(errors='replace')}", rc)
+
+
+def is_non_speech_token(tok: bytes) -> bool:
+    """Whether the bytes are a token set_decode_rules(suppress_non_speech=True) masks
+    (wmi_is_non_speech_token: host-only, no device)."""
+    return lib().wmi_is_non_speech_token(tok, len(tok)) == 1
 
 
 def decode_alg_bytes(hp: dict, rows: int, steps: int, beam: bool = False, q5: bool = False):
@@ -484,6 +506,48 @@ class WhisperContext:
                                                    int(seed) & 0xFFFFFFFFFFFFFFFF, n, out, C.byref(cnt), _ptr(plog),
                                                    C.byref(pn)), self._h)
         return [out[i].as_dict() for i in range(cnt.value)], plog[:cnt.value].copy(), pn.value
+
+    # --- OpenAI decoding rules and the initial prompt -----------------------
+    def set_decode_rules(self, enable: bool = True, max_initial_ts: int = -1, suppress_non_speech: bool = False,
+                         suppress=(), default: bool = False) -> None:
+        """OpenAI's SuppressTokens / ApplyTimestampRules for transcribe(),
+        transcribe_batch() and decode_timestamps_ruled() (wmi_set_decode_rules);
+        enable=False (or default=True: a NULL parameter block) switches them off."""
+        if default:
+            _raise(lib().wmi_set_decode_rules(self._h, None), self._h)
+            return
+        ids = np.ascontiguousarray(suppress, dtype=np.int32)
+        p = DecodeRules(int(bool(enable)), int(max_initial_ts), int(bool(suppress_non_speech)),
+                        ids.ctypes.data if ids.size else None, ids.size)
+        _raise(lib().wmi_set_decode_rules(self._h, C.byref(p)), self._h)
+
+    def non_speech_tokens(self):
+        """The ids set_decode_rules(suppress_non_speech=True) adds (wmi_non_speech_tokens)."""
+        n = C.c_int32()
+        rc = lib().wmi_non_speech_tokens(self._h, None, 0, C.byref(n))
+        if rc != NotEnoughSpace.code:
+            _raise(rc, self._h)
+        ids = np.zeros(max(1, n.value), np.int32)
+        if n.value:
+            _raise(lib().wmi_non_speech_tokens(self._h, _ptr(ids), n.value, C.byref(n)), self._h)
+        return ids[:n.value].tolist()
+
+    def decode_timestamps_ruled(self, prompt, max_tokens: int, temperature: float = 0.0, seed: int = 0, n: int = 0):
+        """decode_timestamps_sampled under the rules set."""
+        prompt = np.ascontiguousarray(prompt, dtype=np.int32)
+        out = (TokenData * max(1, max_tokens))()
+        cnt = C.c_int32()
+        plog = np.zeros(max(1, max_tokens), np.float32)
+        pn = C.c_float()
+        _raise(lib().wmi_decode_timestamps_ruled(self._h, _ptr(prompt), prompt.size, max_tokens, temperature,
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, n, out, C.byref(cnt), _ptr(plog),
+                                                 C.byref(pn)), self._h)
+        return [out[i].as_dict() for i in range(cnt.value)], plog[:cnt.value].copy(), pn.value
+
+    def set_initial_prompt(self, ids=()) -> None:
+        """Text ids in front of the first window's context (wmi_set_initial_prompt); () clears."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        _raise(lib().wmi_set_initial_prompt(self._h, _ptr(ids) if ids.size else None, ids.size), self._h)
 
     def windows_of(self, clip: int = 0):
         """Window infos of recording `clip` of the last transcribe() /
