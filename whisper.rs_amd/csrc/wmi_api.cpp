@@ -3052,6 +3052,7 @@ static int wmi_init_from_file_impl(const char *path, int device, int max_clips, 
     knob("WMI_GEMM_P", tn.gemm_p, 0);
     knob("WMI_GELU_CALC", tn.gelu_calc, 0);
     knob("WMI_MEL_G", tn.mel_g, 0);
+    knob("WMI_GEMM32_TILE", tn.gemm32_tile, 0);
     *out = ctx.release();
     return WMI_OK;
 }

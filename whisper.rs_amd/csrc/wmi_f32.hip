@@ -200,7 +200,8 @@ static hipError_t gemm32_epi(hipStream_t s, int epi, const GemmArgs &a) {
 template <bool CONV, bool AF32>
 static hipError_t gemm32_tiles(hipStream_t s, int epi, const GemmArgs &a) {
     const int64_t t128 = (int64_t)cdiv32(a.M, 128) * cdiv32(a.N, 128);
-    if (t128 >= 240) return gemm32_epi<128, 128, CONV, AF32>(s, epi, a);
+    const int tile = tune_of(a.tune).gemm32_tile;  // 0: by tile count
+    if (tile == 128 || (tile != 64 && t128 >= GEMM32_T128_MIN_TILES)) return gemm32_epi<128, 128, CONV, AF32>(s, epi, a);
     return gemm32_epi<64, 64, CONV, AF32>(s, epi, a);
 }
 

@@ -87,11 +87,15 @@ struct Tune {
     int epi_staged = 1;     // WMI_GEMM_EPI: GEMM epilogues through LDS, 16 / 8-byte stores (0: per-lane 2 / 4-byte stores)
     int gelu_calc = 1;      // WMI_GELU_CALC: encoder GELU epilogues compute the table's values above the scanned threshold (0: table only)
     int gemm_p = 1;         // WMI_GEMM_P: one-clip encoder GEMMs on k_gemm_p (LDS-DMA ring); 0: k_gemm
+    int gemm32_tile = 0;    // WMI_GEMM32_TILE: k_gemm32 tile of f32 files (0 auto: 128 x 128 from GEMM32_T128_MIN_TILES tiles; 64; 128)
 };
 // (fixed since round 5; their alternatives measured slower and are removed:
 // chain logits grid cap at K <= 512, cooperative chain cross-attention up to
 // 512 workgroups, k_gemm_g from 240 128 x 128 tiles)
 constexpr int CHAIN_LOGITS_CAP2 = 1024, CHAIN_COOP_MAX = 512, GEMM_G_MIN_TILES = 240;
+// k_gemm32 (f32 files) takes its 128 x 128 tile from this many 128 x 128 tiles
+// (a rule of its own: GEMM_G_MIN_TILES picks between two f16 kernels)
+constexpr int GEMM32_T128_MIN_TILES = 240;
 extern const Tune kTuneDefault;
 inline const Tune &tune_of(const Tune *t) { return t ? *t : kTuneDefault; }
 
