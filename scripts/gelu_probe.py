@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """How often does the device's f32 GELU round to a different f16 than the
-host-built ggml table (build_tables in wmi_api.cpp: f16(0.5 f (1 + tanhf(
+host-built ggml table (build_tables in wmi_host.cpp: f16(0.5 f (1 + tanhf(
 sqrt(2/pi) f (1 + 0.044715 f f)))) with the host's libm tanhf)?  Evaluates
 the same expression, one rounding per operation, for every finite f16 input
 on the GPU (torch's f32 tanh: the device math library the kernels call) and

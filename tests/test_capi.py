@@ -115,23 +115,29 @@ def test_bad_magic_and_truncation(tmp_path, micro_model):
         wmi.WhisperContext.new(os.path.join(str(tmp_path), "does-not-exist.bin"))
 
 
-def test_f32_model_parses(tmp_path):
-    """ftype-0 files load (main.rs:817-821, 1423-1427: every matrix f32): the
-    host parse passes and only device init remains; an f16 record in such a
-    file is a wrong-bytes error, as in the reference's record loop."""
-    path = _write_variant(str(tmp_path), "f32.bin",
+def _write_f32_and_mixed(d):
+    """An ftype-0 micro file (every matrix f32), and an f16 file whose header claims ftype 0."""
+    path = _write_variant(d, "f32.bin",
                           lambda n, ne, ft, p: (n, ne, 0, np.frombuffer(p, "<f2").astype("<f4").tobytes()) if ft else (n, ne, ft, p))
     raw = bytearray(open(path, "rb").read())
     raw[4 + 40:4 + 44] = struct.pack("<i", 0)
     open(path, "wb").write(raw)
+    mixed = os.path.join(d, "mixed.bin")
+    data = open(_write_variant(d, "f16.bin", lambda *r: r), "rb").read()
+    open(mixed, "wb").write(data[:44] + struct.pack("<i", 0) + data[48:])
+    return path, mixed
+
+
+def test_f32_model_parses(tmp_path):
+    """ftype-0 files load (main.rs:817-821, 1423-1427: every matrix f32): the
+    host parse passes and only device init remains; an f16 record in such a
+    file is a wrong-bytes error, as in the reference's record loop."""
+    path, mixed = _write_f32_and_mixed(str(tmp_path))
     try:
         wmi.WhisperContext.new(path).close()
     except wmi.HipError as e:
         assert "no HIP device" in str(e)
     pyoracle.OracleModel(path).close()
-    mixed = os.path.join(str(tmp_path), "mixed.bin")
-    data = open(_write_variant(str(tmp_path), "f16.bin", lambda *r: r), "rb").read()
-    open(mixed, "wb").write(data[:44] + struct.pack("<i", 0) + data[48:])
     with pytest.raises(wmi.WrongBytesTensor):
         wmi.WhisperContext.new(mixed)
 
@@ -154,27 +160,31 @@ def test_pcm_conversion_matches_reference():
                                   np.array([-1.0, -1 / 32768, 0.0, 1 / 32768, 32767 / 32768], np.float32))
 
 
+def _write_hostile_headers(d, micro_model):
+    data = open(micro_model, "rb").read()
+    big = os.path.join(d, "hp.bin")  # n_vocab = 2^30
+    open(big, "wb").write(data[:4] + struct.pack("<i", 1 << 30) + data[8:])
+    nfilt = struct.unpack("<ii", data[48:56])
+    voc_off = 56 + 4 * nfilt[0] * nfilt[1]
+    nv = os.path.join(d, "nv.bin")  # vocabulary of 2^31 - 1 entries in a small file
+    open(nv, "wb").write(data[:voc_off] + struct.pack("<i", 0x7FFFFFFF) + data[voc_off + 4:])
+    wav = os.path.join(d, "huge.wav")  # data chunk claims 4 GiB - 2
+    body = b"WAVE" + b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, 16000, 32000, 2, 16)
+    body += b"data" + struct.pack("<I", 0xFFFFFFFE) + b"\x00\x01" * 8
+    open(wav, "wb").write(b"RIFF" + struct.pack("<I", len(body)) + body)
+    return big, nv, wav
+
+
 def test_hostile_headers_allocate_nothing(tmp_path, micro_model):
     """Header fields that would size huge host allocations are checked
     against the file first: out-of-range hparams, a vocabulary
     count or a WAV data chunk larger than the file — each a status code, not
     a std::bad_alloc escaping the C ABI."""
-    data = open(micro_model, "rb").read()
-    d = str(tmp_path)
-    big = os.path.join(d, "hp.bin")  # n_vocab = 2^30
-    open(big, "wb").write(data[:4] + struct.pack("<i", 1 << 30) + data[8:])
+    big, nv, wav = _write_hostile_headers(str(tmp_path), micro_model)
     with pytest.raises(wmi.Unexpected):
         wmi.WhisperContext.new(big)
-    nfilt = struct.unpack("<ii", data[48:56])
-    voc_off = 56 + 4 * nfilt[0] * nfilt[1]
-    nv = os.path.join(d, "nv.bin")  # vocabulary of 2^31 - 1 entries in a small file
-    open(nv, "wb").write(data[:voc_off] + struct.pack("<i", 0x7FFFFFFF) + data[voc_off + 4:])
     with pytest.raises(wmi.UnexpectIO):
         wmi.WhisperContext.new(nv)
-    wav = os.path.join(d, "huge.wav")  # data chunk claims 4 GiB - 2
-    body = b"WAVE" + b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, 16000, 32000, 2, 16)
-    body += b"data" + struct.pack("<I", 0xFFFFFFFE) + b"\x00\x01" * 8
-    open(wav, "wb").write(b"RIFF" + struct.pack("<I", len(body)) + body)
     with pytest.raises(wmi.UnexpectIO):
         wmi.read_wav(wav)
 
@@ -220,14 +230,8 @@ REJECTED_SHAPES = {
 }
 
 
-@pytest.mark.parametrize("case", sorted(REJECTED_SHAPES))
-def test_unsupported_shapes_rejected_at_load(tmp_path, micro_model, case):
-    """The shapes the kernels do not implement (n_text_state != n_audio_state,
-    n_text_ctx > 512, a width that is no multiple of 128 or above 1280, a head
-    dim other than 64) are refused when the header is parsed — Unsupported
-    from WhisperContext.new, before a tensor is read or a device touched —
-    not at the first encode: a micro file with only its header fields
-    rewritten, and the same header with every tensor record cut off."""
+def _rejected_shape(micro_model, case):
+    """The micro file with the case's header fields rewritten, and the offset of its first tensor record."""
     data = bytearray(open(micro_model, "rb").read())
     for k, v in REJECTED_SHAPES[case].items():
         data[HP_OFF[k]:HP_OFF[k] + 4] = struct.pack("<i", v)
@@ -238,6 +242,18 @@ def test_unsupported_shapes_rejected_at_load(tmp_path, micro_model, case):
     off += 4
     for _ in range(n_tok):
         off += 4 + struct.unpack("<I", data[off:off + 4])[0]
+    return data, off
+
+
+@pytest.mark.parametrize("case", sorted(REJECTED_SHAPES))
+def test_unsupported_shapes_rejected_at_load(tmp_path, micro_model, case):
+    """The shapes the kernels do not implement (n_text_state != n_audio_state,
+    n_text_ctx > 512, a width that is no multiple of 128 or above 1280, a head
+    dim other than 64) are refused when the header is parsed — Unsupported
+    from WhisperContext.new, before a tensor is read or a device touched —
+    not at the first encode: a micro file with only its header fields
+    rewritten, and the same header with every tensor record cut off."""
+    data, off = _rejected_shape(micro_model, case)
     for name, blob in (("full.bin", data), ("header.bin", data[:off])):
         path = os.path.join(str(tmp_path), name)
         open(path, "wb").write(blob)
@@ -249,3 +265,61 @@ def test_unsupported_shapes_rejected_at_load(tmp_path, micro_model, case):
     open(ok, "wb").write(open(micro_model, "rb").read()[:off])
     with pytest.raises(wmi.UnexpectIO):
         wmi.WhisperContext.new(ok)
+
+
+# --- the host-only unit under ASan + UBSan, as a program of its own -----------
+
+def _library_status(path):
+    """The status the library's own entry gives the file (0: it parsed; without a device init then stops)."""
+    try:
+        if path.endswith(".wav"):
+            wmi.read_wav(path)
+        else:
+            wmi.WhisperContext.new(path).close()
+    except wmi.HipError as e:
+        assert "no HIP device" in str(e)
+    except wmi.WsError as e:
+        return e.code
+    return 0
+
+
+def test_loader_check_sanitized(tmp_path, micro_model):
+    """csrc/loader_check.cpp: wmi_host.cpp (parser, dequantiser, WAV reader)
+    built with ASan + UBSan into a program that links no device runtime, run
+    once over every malformed file of this module and the valid micro model.
+    A sanitizer report aborts and writes to stderr; each file's status is the
+    one WhisperContext.new / read_wav raises for it."""
+    csrc = os.path.join(ROOT, "whisper.rs_amd", "csrc")
+    subprocess.run(["make", "-s", "-C", csrc, "loader_check"], check=True)
+    d = str(tmp_path)
+    want = {}  # path -> the status this module's other tests pin down for it
+    for case, (mutate, _, code) in sorted(CASES.items()):
+        want[_write_variant(d, case + ".bin", mutate)] = code
+    data = open(micro_model, "rb").read()
+    for name, blob, code in (("bad.bin", b"ggjt" + data[4:], 2), ("trunc.bin", data[: len(data) - 1000], 1)):
+        open(os.path.join(d, name), "wb").write(blob)
+        want[os.path.join(d, name)] = code
+    want[os.path.join(d, "does-not-exist.bin")] = 1
+    f32, mixed = _write_f32_and_mixed(d)
+    want[f32], want[mixed] = 0, 8
+    big, nv, wav = _write_hostile_headers(d, micro_model)
+    want[big], want[nv], want[wav] = 10, 1, 1
+    for case in sorted(REJECTED_SHAPES):
+        blob, off = _rejected_shape(micro_model, case)
+        for name, b in ((case + "-full.bin", blob), (case + "-header.bin", blob[:off])):
+            open(os.path.join(d, name), "wb").write(b)
+            want[os.path.join(d, name)] = 13
+    open(os.path.join(d, "ok-header.bin"), "wb").write(data[:off])  # the shape checks pass, the records are missing
+    want[os.path.join(d, "ok-header.bin")] = 1
+    want[micro_model] = 0
+    paths = list(want)
+    r = subprocess.run([os.path.join(csrc, "build_asan", "loader_check")] + paths, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert r.stderr == ""
+    got = {}
+    for line in r.stdout.splitlines():
+        path, status, _ = line.split("\t", 2)
+        got[path] = int(status)
+    assert list(got) == paths
+    for path in paths:
+        assert got[path] == want[path] == _library_status(path), (path, got[path], want[path])

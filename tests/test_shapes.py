@@ -2,7 +2,7 @@
 
 The parity suite runs five widths (128, 384, 512, 768, 1280), all with equal
 encoder / decoder depth, n_text_ctx 448 and n_audio_ctx 1500.  The loader
-(check_shape, wmi_api.cpp) accepts every width that is a multiple of 128 up to
+(check_shape, wmi_host.cpp) accepts every width that is a multiple of 128 up to
 1280 with head dim 64, any pair of depths, n_text_ctx <= 512 and any
 n_audio_ctx.  The fixtures here are the micro dimensions with one field
 changed, written with synth.sharp_hook (long decisive greedy runs):

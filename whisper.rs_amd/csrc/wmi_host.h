@@ -1,0 +1,71 @@
+// wmi_host.h — the host-only unit (wmi_host.cpp): everything that reads an
+// untrusted file or builds a table on the CPU, with no HIP or RCCL dependency.
+//
+// This header and wmi_host.cpp include only the public header and the
+// standard library, so the unit compiles as plain C++ and links into a
+// stand-alone program (loader_check.cpp) without a device runtime.  Functions
+// here report failure as a status code plus a message in `err`; the ABI entry
+// in another unit passes it to set_err.
+//
+// The file parser reproduces the reference loader's checks and error order
+// (main.rs:1384-1475); wmi_api.cpp then packs the weights once for the
+// kernels into one device arena, in place of the reference's four fixed-size
+// byte arenas (main.rs:402-418), with a workspace planned from the hparams.
+#pragma once
+#include <stdint.h>
+
+#include <map>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../../include/whisper_mi355x.h"
+
+// what crosses a unit boundary inside the library is never exported from it
+#define WMI_LOCAL __attribute__((visibility("hidden")))
+
+namespace wmi WMI_LOCAL {
+
+uint16_t f32_to_f16(float f);
+uint16_t f64_to_f16(double v);
+float f16_to_f32(uint16_t h);
+void build_tables(std::vector<uint16_t> &gelu, std::vector<uint16_t> &expt);
+
+struct HostTensor {
+    int dtype = 0;  // 0 f32, 1 f16 (quantised matrices are dequantised to f16)
+    int qtype = 0;  // ggml type of a quantised matrix in the file (7 = q5_1), else 0
+    std::vector<uint8_t> qraw;  // its blocks as read (q5_1 only: the decoder GEMVs read them)
+    int n_dims = 0;
+    int64_t ne[3] = {1, 1, 1};
+    std::vector<uint8_t> data;
+    int64_t nel() const { return ne[0] * ne[1] * ne[2]; }
+    const float *f32() const { return (const float *)data.data(); }
+    const uint16_t *f16() const { return (const uint16_t *)data.data(); }
+};
+
+struct Expected {
+    int dtype;
+    int n_dims;
+    int64_t ne[3];
+};
+
+struct ParsedModel {
+    wmi_hparams hp{};
+    int32_t n_filt_mel = 0, n_filt_ff = 0;
+    std::vector<float> filters;
+    std::vector<std::string> vocab;
+    std::map<std::string, HostTensor> tensors;
+};
+
+int qblock_bytes(int t);
+void dequant_f16(int t, const uint8_t *src, int64_t nel, uint16_t *dst);
+int check_shape(const wmi_hparams &hp, std::string &err);
+int parse_file(const char *path, ParsedModel &pm, std::string &err);
+void init_specials(int32_t n_vocab, wmi_special_tokens &sp);
+int read_wav(const char *path, int16_t *samples, size_t cap, size_t *n_samples, int32_t *sample_rate, int32_t *channels,
+             std::string &err);
+int tokens_to_text(const std::vector<std::string> &vocab, int32_t eot, const int32_t *ids, int n, char *buf, size_t cap,
+                   size_t *len);
+const std::set<std::string> &non_speech_set();
+
+}  // namespace wmi
