@@ -488,7 +488,11 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * window; 13 also the last sampled or ruled window
  * (wmi_decode_timestamps_sampled, wmi_decode_timestamps_ruled, a window of
  * wmi_transcribe under wmi_set_fallback or wmi_set_decode_rules; row b in
- * row b). */
+ * row b).  21 = the conv-1 input of the last encode, [slots][2 * n_ctx + 2]
+ * [up32(n_mels)] (f16 bits; f32 models: float; rows 0 and 2 * n_ctx + 1 are
+ * conv-1's zero padding), 22 = the slots of the last round of
+ * wmi_transcribe_batch, then the recording [8] and the mel offset [8] of each
+ * slot (int32 [17], host copy; 0 slots before the first round). */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

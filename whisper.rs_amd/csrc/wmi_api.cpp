@@ -144,6 +144,8 @@ struct wmi_context {
     float *d_samp_nosp = nullptr, *d_samp_plog = nullptr;
     std::vector<std::vector<wmi_window_info>> windows;  // per recording of the last transcribe under fb_on
     int32_t *d_win = nullptr;   // batched transcription: source recording [8], then mel offset [8] of each encoder slot
+    int32_t win_host[2 * DEC_ROWS] = {};  // host copy of the last d_win upload (debug read 22)
+    int win_slots = 0;                    // and its slot count (0: no batched round yet)
     bool no_context = false;    // wmi_set_no_context: windows of wmi_transcribe take no earlier text
     // OpenAI decoding rules (wmi_set_decode_rules) and the initial prompt (wmi_set_initial_prompt)
     bool rules_on = false;
@@ -2297,6 +2299,8 @@ int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
             win[DEC_ROWS + b] = (int32_t)tr.recs[rows[b]].seek;
         }
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_win, win, sizeof win, hipMemcpyHostToDevice, ctx->stream));
+        memcpy(ctx->win_host, win, sizeof win);
+        ctx->win_slots = B;
         int rc = run_encode(ctx, 0, B, ctx->d_win, ctx->d_win + DEC_ROWS);
         if (rc) return rc;
         rc = tr_resolve_languages(ctx, tr, rows);
@@ -3506,6 +3510,19 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
         }
         case 20: {  // host: windows, decoder steps (every attempt's) and fallback attempts of the last wmi_transcribe, int64 [3]
             memcpy(out, ctx->tr_count, std::min(sizeof ctx->tr_count, bytes));
+            return WMI_OK;
+        }
+        case 21: {  // conv-1 input of the last encode, [slots][2 * T + 2][Cp1] (f16 bits; f32 models: float)
+            if (ctx->enc_T <= 0) return WMI_E_INVALID_ARG;
+            src = ctx->xconv;
+            have = (size_t)ctx->enc_clips * (2 * (size_t)ctx->enc_T + 2) * ctx->Cp1 * (ctx->wf32 ? 4 : 2);
+            break;
+        }
+        case 22: {  // host: slots of the last wmi_transcribe_batch round, then their recording [8] and mel offset [8] (int32 [17])
+            int32_t v[1 + 2 * DEC_ROWS];
+            v[0] = ctx->win_slots;
+            memcpy(v + 1, ctx->win_host, sizeof ctx->win_host);
+            memcpy(out, v, std::min(sizeof v, bytes));
             return WMI_OK;
         }
         case 11: {  // host: decodes re-run on the kernel chain after a persistent exchange timeout

@@ -272,10 +272,11 @@ def quantize_q5_1(w: np.ndarray) -> bytes:
 
 def write_ggml(path: str, model: str = "base", hp_override: dict | None = None,
                wscale: float = 0.02, n_vocab_file: int | None = None, tensor_hook=None,
-               quant: str | None = None, vocab_replace: dict | None = None) -> dict:
+               quant: str | None = None, vocab_replace: dict | None = None, filters=None) -> dict:
     """Write a synthetic ggml-v1 Whisper file; returns the hparams used.
     tensor_hook(name, array) -> array may edit tensors before they are written.
     vocab_replace {id: bytes} replaces those entries of the file's vocabulary.
+    filters: an [n_mels][201] array written in place of mel_filterbank(n_mels).
     quant "f32" writes an ftype-0 file (hparams.f16 = 0: every matrix and conv
     kernel f32, main.rs:817-821); "q5_1", "q8_0", ... store every 2-D weight matrix in that ggml block format,
     as whisper.cpp's quantize tool does (conv kernels, biases, LN parameters
@@ -293,7 +294,8 @@ def write_ggml(path: str, model: str = "base", hp_override: dict | None = None,
     with open(tmp, "wb") as f:
         f.write(struct.pack("<I", GGML_MAGIC))
         f.write(struct.pack("<11i", *[hp[k] for k in HPARAM_ORDER]))
-        filt = mel_filterbank(hp["n_mels"])
+        filt = mel_filterbank(hp["n_mels"]) if filters is None else np.asarray(filters, np.float32)
+        assert filt.shape == (hp["n_mels"], 1 + N_FFT // 2), filt.shape
         f.write(struct.pack("<ii", filt.shape[0], filt.shape[1]))
         f.write(filt.astype("<f4").tobytes())
         f.write(struct.pack("<i", n_vocab_file))

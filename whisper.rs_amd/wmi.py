@@ -666,6 +666,23 @@ class WhisperContext:
         tok = np.frombuffer(self.debug_read(15, n_steps * 8 * 4), np.int32).reshape(n_steps, 8).copy()
         return par, tok
 
+    def conv_input(self, slots: int) -> np.ndarray:
+        """The conv-1 input of the last encode (debug read 21), [slots][2 *
+        n_ctx + 2][up32(n_mels)]: float16, float32 for f32 models; rows 0 and
+        2 * n_ctx + 1 are the convolution's zero padding."""
+        cp = (self.hparams["n_mels"] + 31) // 32 * 32
+        dt = np.float16 if self.hparams["f16"] else np.float32
+        shape = (slots, 2 * self.n_ctx + 2, cp)
+        raw = self.debug_read(21, int(np.prod(shape)) * np.dtype(dt).itemsize)
+        return np.frombuffer(raw, dt).reshape(shape).copy()
+
+    def batch_windows(self):
+        """(src, off) of the last round of transcribe_batch (debug read 22):
+        slot b encoded recording src[b]'s window at mel frame off[b]."""
+        v = np.frombuffer(self.debug_read(22, 17 * 4), np.int32)
+        n = int(v[0])
+        return v[1:1 + n].copy(), v[9:9 + n].copy()
+
     # --- parity getters -----------------------------------------------------
     def mel(self, clip: int = 0) -> np.ndarray:
         nm, nl = C.c_int32(), C.c_int32()
