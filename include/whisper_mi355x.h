@@ -209,7 +209,9 @@ int wmi_full(wmi_context *ctx, const float *pcm, size_t n_samples, int max_token
 /* WhisperTokenData (main.rs:317-331) as sampled: id, tid = most probable
  * timestamp token, p = P(id), pt = P(tid) / (sum of timestamp
  * probabilities + 1e-10), ptsum = that sum.  Token-level t0 / t1 are not
- * computed (-1) and vlen is 0, as in whisper.cpp-1.0.3 by default. */
+ * computed (-1) and vlen is 0, as in whisper.cpp-1.0.3 by default; under
+ * wmi_set_token_timestamps the segment getters of wmi_transcribe /
+ * wmi_transcribe_batch fill them (10 ms units), as does wmi_token_times. */
 typedef struct wmi_token_data {
     int32_t id, tid;
     float p, pt, ptsum;
@@ -410,6 +412,68 @@ int wmi_decode_timestamps_ruled(wmi_context *ctx, const int32_t *prompt, int n_p
  * batch at one decoder position.  n = 0 clears.  Independent of the rules. */
 int wmi_set_initial_prompt(wmi_context *ctx, const int32_t *ids, int n);
 
+/* ---- token-level timestamps, max_len / split_on_word -------------------- */
+
+/* whisper.cpp-1.0.3's token_timestamps, max_len (-ml) and split_on_word
+ * (-sow): a start and an end for every token of every segment, and segments
+ * cut into pieces at those times.  Restated order-independently; times in
+ * 10 ms units; a text token has id < eot; a segment has tokens tau_0 ..
+ * tau_{n-1}, bounds T0, T1 and W = the frame its window started at; N = the
+ * recording's samples (at most 2^26 with the feature on, else
+ * WMI_E_UNSUPPORTED).
+ *   Energy  a_i = min(rint(min(|pcm_i|, 16) * 2^20), 2^24), NaN -> 0;
+ *      E_i = sum of a_j over |j - i| <= 32 inside [0, N) (uint32);
+ *      P_k = sum of E_i over i < k (uint64).
+ *   A  vlen of a text token: over its bytes, in f32, ' ' adds 0.01, ',' 2,
+ *      each of . ! ? 0 .. 9 adds 3, any other byte 1.  Other tokens: 0.
+ *   B  Text tokens k = 1 .. m, b_0 = T0, b_m = T1, ta = T0.  For k = 2 .. m,
+ *      tt = W + 2 (tid_k - beg): if pt_k > thold_pt, ptsum_k > thold_ptsum,
+ *      tt > ta and tt <= T1 then b_{k-1} = tt, ta = tt.  A run of unset
+ *      boundaries between set b_p and b_q: psum = sum of (double) vlen_k over
+ *      k = p+1 .. q; b_r = b_{r-1} + trunc((double)(b_q - b_p) * (double)
+ *      vlen_r / psum) (b_{r-1} if psum is 0).  Token k: t0 = b_{k-1}, t1 = b_k.
+ *   C  (N > 0) For k = 1 .. m in order: s0 = clamp(160 t0, 0, N-1), s1 likewise
+ *      of t1; ss0 = max(s0 - 2000, 0), ss1 = min(s1 + 2000, N), ns = ss1 - ss0,
+ *      S = P[ss1] - P[ss0]; above(i): 2 ns E_i > S, below(i): 2 ns E_i < S.
+ *      Start: j = s0.  If above(s0) and k > 1: while j > 0 and above(j), j--;
+ *      t0 = j / 160; if t0 < t1 of token k-1 (final), t0 = that, else s0 = j.
+ *      Otherwise: while below(j) and j < s1, j++; s0 = j, t0 = j / 160.
+ *      End: j = s1.  If above(s1): while j < N-1 and above(j), j++; t1 =
+ *      j / 160; if k < m and t1 > t0 of token k+1 (from B), t1 = that, else
+ *      s1 = j.  Otherwise: while below(j) and j > s0, j--; s1 = j, t1 = j / 160.
+ *   D  Another token takes t0 = t1 = T0 before the first text token, T1 after
+ *      the last, else the final t1 of the text token before it (m = 0: T0).
+ *   E  (max_len > 0) acc = 0; a text token of L bytes closes the piece before
+ *      it if acc > 0, acc + L > max_len and (not split_on_word, or its first
+ *      byte is ' '): the piece ends and the next starts at this token's t0, acc
+ *      = 0; then acc += L.  The last piece ends at T1; a piece's text is its
+ *      text tokens' bytes; other tokens stay in the piece they follow.
+ * enable != 0: every later wmi_transcribe / wmi_transcribe_batch computes the
+ * envelope once per recording and A - E for each window's result, whatever
+ * beam size, fallback, rules or prompt chose it; the segment getters, counts
+ * and wmi_window_info.first_segment / n_segments then speak of pieces.  The
+ * text context of later windows is not affected.  enable 0 (default, also
+ * params = NULL): every call runs exactly the kernels it ran without this
+ * interface, t0 = t1 = -1 and vlen = 0.  The thresholds and max_len are kept
+ * either way (params = NULL: 0.01, 0.01, 0, 0).  NaN thresholds or a negative
+ * max_len: WMI_E_INVALID_ARG.  Holds until changed. */
+typedef struct wmi_token_ts_params {
+    int32_t enable;              /* 0 (default, also params = NULL) */
+    float thold_pt, thold_ptsum; /* whisper.cpp: 0.01, 0.01 */
+    int32_t max_len;             /* 0: no splitting */
+    int32_t split_on_word;
+} wmi_token_ts_params;
+int wmi_set_token_timestamps(wmi_context *ctx, const wmi_token_ts_params *params);
+/* Steps A - D for the n tokens of one segment [t0, t1) of the window at frame
+ * seek, under the thresholds set (enabled or not): vlen, t0 and t1 of tokens
+ * are written, the rest is read.  pcm [n_samples]: the recording, whose
+ * envelope is computed and kept as clip 0's; pcm = NULL: the envelope of the
+ * last recording given here or transcribed as clip 0 with the feature on
+ * (none yet: WMI_E_INVALID_ARG).  The single-window calls
+ * (wmi_decode_timestamps*) leave t0 / t1 at -1: pass their records here. */
+int wmi_token_times(wmi_context *ctx, const float *pcm, size_t n_samples, int64_t seek, int64_t t0, int64_t t1,
+                    wmi_token_data *tokens, int n);
+
 /* ---- device-resident benchmark path --------------------------------- */
 
 /* Upload n_clips PCM clips to HBM once (untimed). */
@@ -492,7 +556,9 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * [up32(n_mels)] (f16 bits; f32 models: float; rows 0 and 2 * n_ctx + 1 are
  * conv-1's zero padding), 22 = the slots of the last round of
  * wmi_transcribe_batch, then the recording [8] and the mel offset [8] of each
- * slot (int32 [17], host copy; 0 slots before the first round). */
+ * slot (int32 [17], host copy; 0 slots before the first round), 23 / 24 =
+ * clip 0's energy envelope E (uint32 [N]) / its running sum P (uint64 [N + 1])
+ * of the token-level timestamps (WMI_E_INVALID_ARG before one was computed). */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

@@ -153,10 +153,26 @@ struct wmi_context {
     uint32_t *d_rule_m0 = nullptr;      // [ceil(n_vocab / 32)] bit i: id i is masked always
     RuleHist *d_rule_hist = nullptr;    // [8] the rows' history (same allocation, behind dts_done)
     std::vector<int32_t> init_prompt;   // text ids in front of the first window's context
+    // token-level timestamps (wmi_set_token_timestamps): per clip the energy envelope E [N] and its running
+    // sum P [N + 1] of the last recording uploaded with the feature on (tt_n: its samples, -1: none)
+    bool tt_on = false;
+    TokParams tt;
+    std::vector<uint32_t *> tt_E;
+    std::vector<unsigned long long *> tt_P;
+    std::vector<size_t> tt_cap;
+    std::vector<int64_t> tt_n;
+    unsigned long long *tt_tsum = nullptr;  // the tile sums of one energy pass
+    size_t tt_tsum_cap = 0;
+    float *tt_pcm = nullptr;                // wmi_token_times' own recording
+    size_t tt_pcm_cap = 0;
+    char *tt_spans = nullptr;               // one window's VadSeg [segments], then t0, t1 [text tokens]
+    size_t tt_spans_cap = 0;
+    struct TokTime { int64_t t0, t1; float vlen; };
     struct Segment { int64_t t0, t1; int first, count; std::string text; };
     struct SegList {
         std::vector<Segment> segments;  // result_all (main.rs:353)
         std::vector<TsRec> tokens;      // their tokens, in order
+        std::vector<TokTime> times;     // and, under wmi_set_token_timestamps, each token's t0 / t1 / vlen (else empty)
     };
     // per recording of the last transcribe (one) / transcribe_batch
     std::vector<SegList> results = std::vector<SegList>(1);
@@ -2004,6 +2020,142 @@ int64_t commit_ts_window(wmi_context *ctx, std::vector<TsRec> toks, const TsWind
     return seek_delta;
 }
 
+// ---- token-level timestamps (wmi_set_token_timestamps) --------------------------
+// The energy envelope and its running sum of the N samples at d_pcm, kept as
+// clip's (three launches on the context's stream; N = 0: nothing to compute).
+int tt_energy(wmi_context *ctx, int clip, const float *d_pcm, int64_t N) {
+    if (N > TT_MAX_SAMPLES)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "token-level timestamps take at most 2^26 samples a recording (clip %d: %lld)",
+                       clip, (long long)N);
+    if ((int)ctx->tt_n.size() < ctx->max_clips) {
+        ctx->tt_E.resize(ctx->max_clips, nullptr);
+        ctx->tt_P.resize(ctx->max_clips, nullptr);
+        ctx->tt_cap.resize(ctx->max_clips, 0);
+        ctx->tt_n.resize(ctx->max_clips, -1);
+    }
+    ctx->tt_n[clip] = -1;
+    if (N > 0) {
+        if ((size_t)N > ctx->tt_cap[clip]) {
+            if (ctx->tt_E[clip]) HIPCHK(ctx, hipFree(ctx->tt_E[clip]));
+            if (ctx->tt_P[clip]) HIPCHK(ctx, hipFree(ctx->tt_P[clip]));
+            ctx->tt_E[clip] = nullptr; ctx->tt_P[clip] = nullptr; ctx->tt_cap[clip] = 0;
+            HIPCHK(ctx, hipMalloc(&ctx->tt_E[clip], (size_t)N * 4));
+            HIPCHK(ctx, hipMalloc(&ctx->tt_P[clip], ((size_t)N + 1) * 8));
+            ctx->tt_cap[clip] = (size_t)N;
+        }
+        const size_t tiles = ((size_t)N + 1023) / 1024;
+        if (tiles > ctx->tt_tsum_cap) {
+            if (ctx->tt_tsum) HIPCHK(ctx, hipFree(ctx->tt_tsum));
+            ctx->tt_tsum = nullptr; ctx->tt_tsum_cap = 0;
+            HIPCHK(ctx, hipMalloc(&ctx->tt_tsum, tiles * 8));
+            ctx->tt_tsum_cap = tiles;
+        }
+        HIPCHK(ctx, launch_energy(ctx->stream, d_pcm, (long long)N, ctx->tt_E[clip], ctx->tt_tsum, ctx->tt_P[clip]));
+    }
+    ctx->tt_n[clip] = N;
+    return WMI_OK;
+}
+
+// Steps A to D for the n tokens of one or more segments that follow each other
+// in tok (segment s: n_of[s] tokens, bounds [T0[s], T1[s]), window frame W):
+// A and B on the host, one k_token_vad launch over clip's envelope for all of
+// them (skipped for a recording of no samples), the spans copied back, then D.
+int tt_times(wmi_context *ctx, int clip, int64_t W, const std::vector<int> &n_of, const std::vector<int64_t> &T0,
+             const std::vector<int64_t> &T1, wmi_token_data *tok) {
+    const int S = (int)n_of.size();
+    std::vector<VadSeg> segs;
+    std::vector<long long> t0, t1;
+    std::vector<std::vector<int>> tx((size_t)S);
+    int at = 0;
+    for (int s = 0; s < S; at += n_of[s], ++s) {
+        tx[s] = token_bounds(ctx->vocab, ctx->sp.eot, ctx->sp.beg, ctx->tt, W, T0[s], T1[s], tok + at, n_of[s]);
+        if (tx[s].empty()) continue;
+        segs.push_back({(int32_t)t0.size(), (int32_t)tx[s].size()});
+        for (int i : tx[s]) { t0.push_back(tok[at + i].t0); t1.push_back(tok[at + i].t1); }
+    }
+    const int64_t N = clip < (int)ctx->tt_n.size() ? ctx->tt_n[clip] : -1;
+    if (N < 0) return set_err(ctx, WMI_E_INVALID_ARG, "no energy envelope of clip %d (no recording given yet)", clip);
+    if (N > 0 && !segs.empty()) {
+        const size_t o_t0 = up((int64_t)(segs.size() * sizeof(VadSeg)), 16), o_t1 = o_t0 + t0.size() * 8;
+        const size_t need = o_t1 + t1.size() * 8;
+        if (need > ctx->tt_spans_cap) {
+            if (ctx->tt_spans) HIPCHK(ctx, hipFree(ctx->tt_spans));
+            ctx->tt_spans = nullptr; ctx->tt_spans_cap = 0;
+            HIPCHK(ctx, hipMalloc(&ctx->tt_spans, 2 * need));
+            ctx->tt_spans_cap = 2 * need;
+        }
+        char *d = ctx->tt_spans;
+        HIPCHK(ctx, hipMemcpyAsync(d, segs.data(), segs.size() * sizeof(VadSeg), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d + o_t0, t0.data(), t0.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d + o_t1, t1.data(), t1.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        VadArgs va{ctx->tt_E[clip], ctx->tt_P[clip], (long long)N, (const VadSeg *)d, (long long *)(d + o_t0),
+                   (long long *)(d + o_t1)};
+        HIPCHK(ctx, launch_token_vad(ctx->stream, va, (int)segs.size()));
+        HIPCHK(ctx, hipMemcpyAsync(t0.data(), d + o_t0, t0.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(t1.data(), d + o_t1, t1.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    at = 0;
+    size_t k = 0;
+    for (int s = 0; s < S; at += n_of[s], ++s) {
+        for (int i : tx[s]) { tok[at + i].t0 = t0[k]; tok[at + i].t1 = t1[k]; ++k; }
+        token_fill_others(ctx->sp.eot, T0[s], T1[s], tok + at, n_of[s]);
+    }
+    return WMI_OK;
+}
+
+// A committed window's segments res.segments[seg_first ..) of the window at
+// frame W: their tokens' times (tt_times), then step E, which puts each
+// segment's pieces in its place.
+int tt_window(wmi_context *ctx, int clip, wmi_context::SegList &res, size_t seg_first, int64_t W) {
+    res.times.resize(res.tokens.size(), {-1, -1, 0.0f});
+    if (seg_first >= res.segments.size()) return WMI_OK;
+    const int tok_first = res.segments[seg_first].first;
+    std::vector<wmi_token_data> tok(res.tokens.size() - (size_t)tok_first);
+    for (size_t i = 0; i < tok.size(); ++i) {
+        const TsRec &r = res.tokens[(size_t)tok_first + i];
+        tok[i] = wmi_token_data{r.id, r.tid, r.p, r.pt, r.ptsum, -1, -1, 0.0f};
+    }
+    std::vector<int> n_of;
+    std::vector<int64_t> T0, T1;
+    for (size_t s = seg_first; s < res.segments.size(); ++s) {
+        n_of.push_back(res.segments[s].count);
+        T0.push_back(res.segments[s].t0);
+        T1.push_back(res.segments[s].t1);
+    }
+    int rc = tt_times(ctx, clip, W, n_of, T0, T1, tok.data());
+    if (rc) return rc;
+    for (size_t i = 0; i < tok.size(); ++i) res.times[(size_t)tok_first + i] = {tok[i].t0, tok[i].t1, tok[i].vlen};
+    if (ctx->tt.max_len <= 0) return WMI_OK;
+    std::vector<wmi_context::Segment> pieces;
+    for (size_t s = seg_first; s < res.segments.size(); ++s) {
+        const wmi_context::Segment &sg = res.segments[s];
+        for (TokPiece &pc : split_segment(ctx->vocab, ctx->sp.eot, ctx->tt, sg.t0, sg.t1, tok.data() + (sg.first - tok_first),
+                                          sg.count))
+            pieces.push_back({pc.t0, pc.t1, sg.first + pc.first, pc.count, std::move(pc.text)});
+    }
+    res.segments.resize(seg_first);
+    res.segments.insert(res.segments.end(), pieces.begin(), pieces.end());
+    return WMI_OK;
+}
+
+// a transcribe under the feature: refused before anything is uploaded if a recording is too long ...
+int tt_check_samples(wmi_context *ctx, int n_clips, const size_t *n_samples) {
+    for (int c = 0; ctx->tt_on && c < n_clips; ++c)
+        if (n_samples[c] > (size_t)TT_MAX_SAMPLES)
+            return set_err(ctx, WMI_E_UNSUPPORTED, "token-level timestamps take at most 2^26 samples a recording (clip %d: %zu)",
+                           c, n_samples[c]);
+    return WMI_OK;
+}
+// ... and every recording's envelope once, from the PCM just uploaded
+int tt_energy_of_clips(wmi_context *ctx, int n_clips) {
+    for (int c = 0; ctx->tt_on && c < n_clips; ++c) {
+        int rc = tt_energy(ctx, c, ctx->pcm_dev[c], ctx->n_samp_host[c]);
+        if (rc) return rc;
+    }
+    return WMI_OK;
+}
+
 // ---- temperature fallback (wmi_set_fallback) ---------------------------------
 // the temperatures of a window's attempts: T_j = temperature + j * inc while <= 1 + 1e-6
 std::vector<float> fb_temperatures(const wmi_fallback_params &fb) {
@@ -2192,21 +2344,31 @@ int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows,
 // temperature left moves the recording to its next attempt and leaves seek;
 // otherwise the window ends: its info record, and unless it was skipped as
 // silence its segments; a result of T > 0.5 clears the text context.
-// Returns whether the window is done (seek has then moved).
-bool tr_settle(wmi_context *ctx, const TrRun &tr, TrRec &rec, TrAttempt a) {
+// *done: whether the window is done (seek has then moved).  Under
+// wmi_set_token_timestamps a committed window's segments get their token
+// times, and are split, before they are counted (tt_window).
+int tr_settle(wmi_context *ctx, const TrRun &tr, TrRec &rec, TrAttempt a, bool *done) {
     wmi_context::SegList &res = ctx->results[rec.clip];
     std::vector<int32_t> *past = rec.carry ? &rec.past : nullptr;
+    const size_t seg_first = res.segments.size();
+    *done = true;
     if (tr.temps.empty()) {
         const TsWindowClass wc = classify_ts_window(ctx, a.toks, rec.seek, rec.n_len, tr.window);
-        rec.seek += commit_ts_window(ctx, std::move(a.toks), wc, rec.seek, res, past);
-        return true;
+        const int64_t delta = commit_ts_window(ctx, std::move(a.toks), wc, rec.seek, res, past);
+        if (ctx->tt_on) {
+            int rc = tt_window(ctx, rec.clip, res, seg_first, rec.seek);
+            if (rc) return rc;
+        }
+        rec.seek += delta;
+        return WMI_OK;
     }
     const FbAttempt att = fb_judge(ctx, a.toks, a.logprob_sum, rec.seek, rec.n_len, tr.window);
     if (rec.att == 0) rec.p_nosp0 = a.p_nosp;
     const bool silence = rec.att == 0 && fb_silence(ctx, rec.p_nosp0, att);
     if (!silence && att.rejected && rec.att + 1 < (int)tr.temps.size()) {
         ++rec.att;
-        return false;
+        *done = false;
+        return WMI_OK;
     }
     wmi_window_info wi{};
     wi.seek = rec.seek; wi.n_attempts = rec.att + 1; wi.temperature = a.T; wi.avg_logprob = (float)att.avg_logprob;
@@ -2222,12 +2384,16 @@ bool tr_settle(wmi_context *ctx, const TrRun &tr, TrRec &rec, TrAttempt a) {
             wi.flags |= WIN_RESET;
             rec.past.clear();
         }
+        if (ctx->tt_on) {
+            int rc = tt_window(ctx, rec.clip, res, seg_first, rec.seek);
+            if (rc) return rc;
+        }
     }
     wi.n_segments = (int32_t)res.segments.size() - wi.first_segment;
     ctx->windows[rec.clip].push_back(wi);
     rec.att = 0;
     rec.seek += delta;
-    return true;
+    return WMI_OK;
 }
 
 // whisper_full (whisper.cpp-1.0.3, the loop the reference's WhisperSegment /
@@ -2255,7 +2421,8 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
             if (rc) return rc;
             ctx->tr_count[1] += ctx->last_run_steps;
             if (ctx->fb_on) ++ctx->tr_count[2];
-            done = tr_settle(ctx, tr, rec, std::move(att[0]));
+            rc = tr_settle(ctx, tr, rec, std::move(att[0]), &done);
+            if (rc) return rc;
         }
         ++ctx->tr_count[0];
     }
@@ -2315,7 +2482,11 @@ int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
         std::vector<TrAttempt> att;
         rc = tr_decode_attempt(ctx, tr, rows, feed, np, &att);
         if (rc) return rc;
-        for (int b = 0; b < B; ++b) tr_settle(ctx, tr, tr.recs[rows[b]], std::move(att[b]));
+        for (int b = 0; b < B; ++b) {
+            bool done;
+            rc = tr_settle(ctx, tr, tr.recs[rows[b]], std::move(att[b]), &done);
+            if (rc) return rc;
+        }
     }
     return WMI_OK;
 }
@@ -2655,6 +2826,11 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
     ctx->clear_graphs();
     for (float *p : ctx->pcm_dev) if (p) (void)hipFree(p);
+    for (uint32_t *p : ctx->tt_E) if (p) (void)hipFree(p);
+    for (unsigned long long *p : ctx->tt_P) if (p) (void)hipFree(p);
+    if (ctx->tt_tsum) (void)hipFree(ctx->tt_tsum);
+    if (ctx->tt_pcm) (void)hipFree(ctx->tt_pcm);
+    if (ctx->tt_spans) (void)hipFree(ctx->tt_spans);
     if (ctx->d_mel) (void)hipFree(ctx->d_mel);
     if (ctx->dfeed) (void)hipFree(ctx->dfeed);
     if (ctx->dtokens) (void)hipFree(ctx->dtokens);
@@ -2785,6 +2961,12 @@ static void to_token_data(const TsRec &r, wmi_token_data *d) {
     d->t0 = -1; d->t1 = -1; d->vlen = 0.0f;  // token-level timestamps are not computed (as whisper.cpp-1.0.3 by default)
 }
 
+// token i of a recording's segment list, with its times if the transcribe computed them
+static void seg_token(const wmi_context::SegList &res, size_t i, wmi_token_data *d) {
+    to_token_data(res.tokens[i], d);
+    if (i < res.times.size()) { d->t0 = res.times[i].t0; d->t1 = res.times[i].t1; d->vlen = res.times[i].vlen; }
+}
+
 // what the four wmi_decode_timestamps* entry points ask of their arguments
 static int check_ts_args(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens, const wmi_token_data *out,
                          const int32_t *n_out) {
@@ -2891,7 +3073,11 @@ static int wmi_transcribe_impl(wmi_context *ctx, const float *pcm, size_t n_samp
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const float *pp[1] = {pcm};
     const size_t nn[1] = {n_samples};
-    int rc = wmi_pcm_to_mel_batch(ctx, 1, pp, nn);
+    int rc = tt_check_samples(ctx, 1, nn);
+    if (rc) return rc;
+    rc = wmi_pcm_to_mel_batch(ctx, 1, pp, nn);
+    if (rc) return rc;
+    rc = tt_energy_of_clips(ctx, 1);
     if (rc) return rc;
     rc = run_transcribe(ctx, max_tokens);
     if (rc) return rc;
@@ -2933,7 +3119,11 @@ static int wmi_transcribe_batch_impl(wmi_context *ctx, int n_clips, const float 
             return set_err(ctx, WMI_E_INVALID_ARG, "language %d / task %d on an English-only model (clip %d)",
                            ctx->lang_set[c], ctx->task, c);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc = wmi_pcm_to_mel_batch(ctx, n_clips, pcm, n_samples);
+    int rc = tt_check_samples(ctx, n_clips, n_samples);
+    if (rc) return rc;
+    rc = wmi_pcm_to_mel_batch(ctx, n_clips, pcm, n_samples);
+    if (rc) return rc;
+    rc = tt_energy_of_clips(ctx, n_clips);
     if (rc) return rc;
     rc = run_transcribe_batch(ctx, max_tokens);
     if (rc) return rc;
@@ -3027,6 +3217,50 @@ int wmi_set_initial_prompt(wmi_context *ctx, const int32_t *ids, int n) {
     });
 }
 
+int wmi_set_token_timestamps(wmi_context *ctx, const wmi_token_ts_params *params) {
+    return guarded(ctx, [&] {
+        if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+        const wmi_token_ts_params def{0, 0.01f, 0.01f, 0, 0};
+        const wmi_token_ts_params p = params ? *params : def;
+        if (std::isnan(p.thold_pt) || std::isnan(p.thold_ptsum)) return set_err(ctx, WMI_E_INVALID_ARG, "NaN threshold");
+        if (p.max_len < 0) return set_err(ctx, WMI_E_INVALID_ARG, "max_len %d is negative", p.max_len);
+        ctx->tt.thold_pt = p.thold_pt;
+        ctx->tt.thold_ptsum = p.thold_ptsum;
+        ctx->tt.max_len = p.max_len;
+        ctx->tt.split_on_word = p.split_on_word != 0;
+        ctx->tt_on = p.enable != 0;
+        return (int)WMI_OK;
+    });
+}
+
+static int wmi_token_times_impl(wmi_context *ctx, const float *pcm, size_t n_samples, int64_t seek, int64_t t0, int64_t t1,
+                                wmi_token_data *tokens, int n) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (n < 0 || (n > 0 && !tokens)) return set_err(ctx, WMI_E_INVALID_ARG, "%d tokens, null pointer", n);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (pcm) {
+        if (n_samples > (size_t)TT_MAX_SAMPLES)
+            return set_err(ctx, WMI_E_UNSUPPORTED, "token-level timestamps take at most 2^26 samples a recording (%zu)", n_samples);
+        if (n_samples + 4 > ctx->tt_pcm_cap) {
+            if (ctx->tt_pcm) HIPCHK(ctx, hipFree(ctx->tt_pcm));
+            ctx->tt_pcm = nullptr; ctx->tt_pcm_cap = 0;
+            HIPCHK(ctx, hipMalloc(&ctx->tt_pcm, (n_samples + 4) * 4));
+            ctx->tt_pcm_cap = n_samples + 4;
+        }
+        if (n_samples) HIPCHK(ctx, hipMemcpyAsync(ctx->tt_pcm, pcm, n_samples * 4, hipMemcpyHostToDevice, ctx->stream));
+        int rc = tt_energy(ctx, 0, ctx->tt_pcm, (int64_t)n_samples);
+        if (rc) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the caller's pcm is free again)
+    }
+    if (n == 0) return WMI_OK;
+    return tt_times(ctx, 0, seek, {n}, {t0}, {t1}, tokens);
+}
+
+int wmi_token_times(wmi_context *ctx, const float *pcm, size_t n_samples, int64_t seek, int64_t t0, int64_t t1,
+                    wmi_token_data *tokens, int n) {
+    return guarded(ctx, [&] { return wmi_token_times_impl(ctx, pcm, n_samples, seek, t0, t1, tokens, n); });
+}
+
 int wmi_set_fallback(wmi_context *ctx, const wmi_fallback_params *params) {
     if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
     const wmi_fallback_params def{0.0f, 0.0f, -INFINITY, -INFINITY, INFINITY, 0};
@@ -3110,7 +3344,7 @@ int wmi_get_segment_tokens_of(const wmi_context *ctx, int clip, int i, wmi_token
     const auto &sg = ctx->results[clip].segments[i];
     *n = sg.count;
     if (!out || cap < (size_t)sg.count) return WMI_E_NO_SPACE;
-    for (int k = 0; k < sg.count; ++k) to_token_data(ctx->results[clip].tokens[sg.first + k], out + k);
+    for (int k = 0; k < sg.count; ++k) seg_token(ctx->results[clip], (size_t)(sg.first + k), out + k);
     return WMI_OK;
 }
 
@@ -3130,7 +3364,7 @@ int wmi_get_segment_tokens(const wmi_context *ctx, int i, wmi_token_data *out, s
     const auto &sg = ctx->results[0].segments[i];
     *n = sg.count;
     if (!out || cap < (size_t)sg.count) return WMI_E_NO_SPACE;
-    for (int k = 0; k < sg.count; ++k) to_token_data(ctx->results[0].tokens[sg.first + k], out + k);
+    for (int k = 0; k < sg.count; ++k) seg_token(ctx->results[0], (size_t)(sg.first + k), out + k);
     return WMI_OK;
 }
 
@@ -3525,6 +3759,12 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
             memcpy(out, v, std::min(sizeof v, bytes));
             return WMI_OK;
         }
+        case 23:  // token-level timestamps: clip 0's energy envelope E, uint32 [N]
+        case 24:  // ... and its running sum P, uint64 [N + 1]
+            if (ctx->tt_n.empty() || ctx->tt_n[0] < 1) return WMI_E_INVALID_ARG;
+            if (which == 23) { src = ctx->tt_E[0]; have = (size_t)ctx->tt_n[0] * 4; }
+            else { src = ctx->tt_P[0]; have = ((size_t)ctx->tt_n[0] + 1) * 8; }
+            break;
         case 11: {  // host: decodes re-run on the kernel chain after a persistent exchange timeout
             const int32_t v = ctx->n_fallbacks;
             memcpy(out, &v, std::min(sizeof v, bytes));

@@ -495,6 +495,116 @@ const std::set<std::string> &non_speech_set() {
     return want;
 }
 
+// ---- token-level timestamps: steps A, B, D and E ------------------------------
+// (whisper.cpp-1.0.3's whisper_exp_compute_token_level_timestamps and
+// whisper_wrap_segment, restated in include/whisper_mi355x.h; this unit is
+// compiled with -ffp-contract=off: the fill's multiply and divide round apart)
+namespace {
+const std::string &token_bytes(const std::vector<std::string> &vocab, int32_t id) {
+    static const std::string none;
+    return id >= 0 && (size_t)id < vocab.size() ? vocab[(size_t)id] : none;
+}
+bool is_text(int32_t id, int32_t eot) { return id >= 0 && id < eot; }
+}  // namespace
+
+float token_vlen(const std::string &bytes) {
+    float v = 0.0f;
+    for (const char c : bytes) {
+        if (c == ' ') v += 0.01f;
+        else if (c == ',') v += 2.0f;
+        else if (c == '.' || c == '!' || c == '?' || (c >= '0' && c <= '9')) v += 3.0f;
+        else v += 1.0f;
+    }
+    return v;
+}
+
+std::vector<int> token_bounds(const std::vector<std::string> &vocab, int32_t eot, int32_t beg, const TokParams &p, int64_t W,
+                              int64_t T0, int64_t T1, wmi_token_data *tok, int n) {
+    std::vector<int> tx;
+    for (int i = 0; i < n; ++i) {
+        const bool text = is_text(tok[i].id, eot);
+        tok[i].vlen = text ? token_vlen(token_bytes(vocab, tok[i].id)) : 0.0f;
+        if (text) tx.push_back(i);
+    }
+    const int m = (int)tx.size();
+    if (m == 0) return tx;
+    // b[k]: the boundary behind text token k (1-based), b[0] = T0, b[m] = T1
+    std::vector<int64_t> b((size_t)m + 1, 0);
+    std::vector<char> set((size_t)m + 1, 0);
+    b[0] = T0; b[(size_t)m] = T1;
+    set[0] = set[(size_t)m] = 1;
+    int64_t ta = T0;
+    for (int k = 2; k <= m; ++k) {
+        const wmi_token_data &t = tok[tx[(size_t)k - 1]];
+        const int64_t tt = W + 2 * ((int64_t)t.tid - beg);
+        if (t.pt > p.thold_pt && t.ptsum > p.thold_ptsum && tt > ta && tt <= T1) {
+            b[(size_t)k - 1] = tt;
+            set[(size_t)k - 1] = 1;
+            ta = tt;
+        }
+    }
+    for (int pp = 0; pp < m;) {
+        int q = pp + 1;
+        while (!set[(size_t)q]) ++q;
+        if (q > pp + 1) {
+            double psum = 0.0;
+            for (int k = pp + 1; k <= q; ++k) psum += (double)tok[tx[(size_t)k - 1]].vlen;
+            for (int r = pp + 1; r < q; ++r) {
+                int64_t step = 0;
+                if (psum != 0.0) {
+                    const double num = (double)(b[(size_t)q] - b[(size_t)pp]) * (double)tok[tx[(size_t)r - 1]].vlen;
+                    step = (int64_t)(num / psum);
+                }
+                b[(size_t)r] = b[(size_t)r - 1] + step;
+            }
+        }
+        pp = q;
+    }
+    for (int k = 1; k <= m; ++k) {
+        tok[tx[(size_t)k - 1]].t0 = b[(size_t)k - 1];
+        tok[tx[(size_t)k - 1]].t1 = b[(size_t)k];
+    }
+    return tx;
+}
+
+void token_fill_others(int32_t eot, int64_t T0, int64_t T1, wmi_token_data *tok, int n) {
+    int last_text = -1;
+    for (int i = 0; i < n; ++i)
+        if (is_text(tok[i].id, eot)) last_text = i;
+    int64_t cur = T0;  // before the first text token (and with none at all)
+    for (int i = 0; i < n; ++i) {
+        if (is_text(tok[i].id, eot)) {
+            cur = tok[i].t1;
+            continue;
+        }
+        tok[i].t0 = tok[i].t1 = last_text >= 0 && i > last_text ? T1 : cur;
+    }
+}
+
+std::vector<TokPiece> split_segment(const std::vector<std::string> &vocab, int32_t eot, const TokParams &p, int64_t T0,
+                                    int64_t T1, const wmi_token_data *tok, int n) {
+    std::vector<TokPiece> out;
+    TokPiece cur{T0, T1, 0, 0, {}};
+    int64_t acc = 0;
+    for (int i = 0; i < n; ++i) {
+        if (is_text(tok[i].id, eot)) {
+            const std::string &s = token_bytes(vocab, tok[i].id);
+            const int64_t L = (int64_t)s.size();
+            if (p.max_len > 0 && acc > 0 && acc + L > p.max_len && (!p.split_on_word || (!s.empty() && s[0] == ' '))) {
+                cur.t1 = tok[i].t0;
+                out.push_back(cur);
+                cur = TokPiece{tok[i].t0, T1, i, 0, {}};
+                acc = 0;
+            }
+            acc += L;
+            cur.text += s;
+        }
+        ++cur.count;
+    }
+    out.push_back(cur);
+    return out;
+}
+
 }  // namespace wmi
 
 extern "C" {

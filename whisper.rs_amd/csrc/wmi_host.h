@@ -68,4 +68,28 @@ int tokens_to_text(const std::vector<std::string> &vocab, int32_t eot, const int
                    size_t *len);
 const std::set<std::string> &non_speech_set();
 
+// ---- token-level timestamps: the host steps (DESIGN.md "Token-level
+// timestamps"; step C, the voice-activity pass, runs on the device between
+// B and D).  A text token has 0 <= id < eot; its bytes are vocab[id]. --------
+struct TokParams {
+    float thold_pt = 0.01f, thold_ptsum = 0.01f;
+    int32_t max_len = 0, split_on_word = 0;
+};
+// step A: 0.01 a space, 2 a comma, 3 each of . ! ? and the digits, 1 any other byte, summed in f32 in byte order
+float token_vlen(const std::string &bytes);
+// steps A and B for the n tokens of a segment [T0, T1) of the window at frame W:
+// every token's vlen, the text tokens' t0 / t1; returns the text tokens' indices
+std::vector<int> token_bounds(const std::vector<std::string> &vocab, int32_t eot, int32_t beg, const TokParams &p, int64_t W,
+                              int64_t T0, int64_t T1, wmi_token_data *tok, int n);
+// step D: t0 = t1 of the other tokens
+void token_fill_others(int32_t eot, int64_t T0, int64_t T1, wmi_token_data *tok, int n);
+// step E: the pieces of a segment under max_len / split_on_word (one piece with max_len 0)
+struct TokPiece {
+    int64_t t0, t1;
+    int first, count;  // its tokens
+    std::string text;
+};
+std::vector<TokPiece> split_segment(const std::vector<std::string> &vocab, int32_t eot, const TokParams &p, int64_t T0,
+                                    int64_t T1, const wmi_token_data *tok, int n);
+
 }  // namespace wmi

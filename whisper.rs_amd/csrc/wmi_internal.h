@@ -349,6 +349,22 @@ struct TsRuleArgs {
     int max_initial_ts;      // first timestamp <= beg + this (< 0: no cap)
 };
 hipError_t launch_ts_sample_r(hipStream_t s, const TsRuleArgs &a);
+// ---- token-level timestamps (wmi_toktime.hip; DESIGN.md "Token-level
+// timestamps"): a recording's energy envelope E [N] and its running sum
+// P [N + 1], and the voice-activity pass over each segment's text tokens ------
+constexpr long long TT_MAX_SAMPLES = 1ll << 26;  // (2^26 * 65 * 2^24 * 2 ns stays inside 64 bits)
+// E, the tile sums (tsum: ceil(N / 1024) words of scratch) and P, three launches
+hipError_t launch_energy(hipStream_t s, const float *pcm, long long N, uint32_t *E, unsigned long long *tsum,
+                         unsigned long long *P);
+struct VadSeg { int32_t first, m; };  // a segment's text tokens: spans [first, first + m)
+struct VadArgs {
+    const uint32_t *E;
+    const unsigned long long *P;
+    long long N;
+    const VadSeg *segs;      // one workgroup each
+    long long *t0, *t1;      // the spans after step B, in 10 ms units; moved in place
+};
+hipError_t launch_token_vad(hipStream_t s, const VadArgs &a, int n_segs);
 struct NoSpeechArgs {        // a beam window's no-speech probability (row 0 of its first generated step)
     const float *logits;     // [V]
     int V, solm, feed_len;

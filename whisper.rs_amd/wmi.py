@@ -68,7 +68,7 @@ EXPORTS = (
     "wmi_get_segment_tokens_of", "wmi_decode_timestamps_beam", "wmi_set_beam_size",
     "wmi_set_fallback", "wmi_decode_timestamps_sampled", "wmi_get_window_count", "wmi_get_window_info",
     "wmi_set_decode_rules", "wmi_non_speech_tokens", "wmi_decode_timestamps_ruled", "wmi_set_initial_prompt",
-    "wmi_is_non_speech_token",
+    "wmi_is_non_speech_token", "wmi_set_token_timestamps", "wmi_token_times",
     "wmi_pcm_to_mel", "wmi_pcm_to_mel_batch", "wmi_encode", "wmi_decode_greedy", "wmi_decode_logits",
     "wmi_decode_beam", "wmi_full", "wmi_stage_pcm", "wmi_run_staged", "wmi_run_staged_beam", "wmi_get_tokens", "wmi_get_timings", "wmi_sync",
     "wmi_get_mel", "wmi_get_checksums", "wmi_get_encoder_out", "wmi_get_cross_kv", "wmi_bench_kernel", "wmi_decode_alg_bytes",
@@ -114,6 +114,12 @@ class DecodeRules(C.Structure):
     """wmi_decode_rules."""
     _fields_ = [("enable", C.c_int32), ("max_initial_ts", C.c_int32), ("suppress_non_speech", C.c_int32),
                 ("suppress", C.c_void_p), ("n_suppress", C.c_int32)]
+
+
+class TokenTsParams(C.Structure):
+    """wmi_token_ts_params."""
+    _fields_ = [("enable", C.c_int32), ("thold_pt", C.c_float), ("thold_ptsum", C.c_float), ("max_len", C.c_int32),
+                ("split_on_word", C.c_int32)]
 
 
 class WindowInfo(C.Structure):
@@ -181,6 +187,9 @@ def lib():
             L.wmi_decode_timestamps_ruled.argtypes = L.wmi_decode_timestamps_sampled.argtypes
             L.wmi_set_initial_prompt.argtypes = [vp, vp, C.c_int]
             L.wmi_is_non_speech_token.argtypes = [C.c_char_p, sz]
+        if hasattr(L, "wmi_set_token_timestamps"):  # (as above: an older build has no token-level timestamps)
+            L.wmi_set_token_timestamps.argtypes = [vp, C.POINTER(TokenTsParams)]
+            L.wmi_token_times.argtypes = [vp, vp, sz, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int]
         L.wmi_get_window_count.argtypes = [vp, C.c_int, C.POINTER(i32)]
         L.wmi_get_window_info.argtypes = [vp, C.c_int, C.c_int, C.POINTER(WindowInfo)]
         L.wmi_decode_timestamps_batch.argtypes =[vp, vp, C.c_int, C.c_int, vp, vp]
@@ -548,6 +557,45 @@ class WhisperContext:
         """Text ids in front of the first window's context (wmi_set_initial_prompt); () clears."""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         _raise(lib().wmi_set_initial_prompt(self._h, _ptr(ids) if ids.size else None, ids.size), self._h)
+
+    # --- token-level timestamps, max_len / split_on_word ----------------------
+    def set_token_timestamps(self, enable: bool = True, thold_pt: float = 0.01, thold_ptsum: float = 0.01,
+                             max_len: int = 0, split_on_word: bool = False, default: bool = False) -> None:
+        """t0 / t1 / vlen of every token of transcribe() / transcribe_batch(),
+        and with max_len > 0 their segments cut into pieces at those times
+        (wmi_set_token_timestamps); enable=False (or default=True: a NULL
+        parameter block) switches it off."""
+        if default:
+            _raise(lib().wmi_set_token_timestamps(self._h, None), self._h)
+            return
+        p = TokenTsParams(int(bool(enable)), thold_pt, thold_ptsum, int(max_len), int(bool(split_on_word)))
+        _raise(lib().wmi_set_token_timestamps(self._h, C.byref(p)), self._h)
+
+    def token_times(self, tokens, seek: int, t0: int, t1: int, pcm=None):
+        """The token times of one segment [t0, t1) of the window at frame seek
+        (wmi_token_times): tokens as [WhisperTokenData dict] (id, tid, pt and
+        ptsum are read), returned with t0, t1 and vlen filled.  pcm None: the
+        envelope of the last recording given."""
+        arr = (TokenData * max(1, len(tokens)))()
+        for i, t in enumerate(tokens):
+            arr[i] = TokenData(int(t["id"]), int(t["tid"]), float(t.get("p", 0.0)), float(t["pt"]), float(t["ptsum"]),
+                               -1, -1, 0.0)
+        if pcm is None:
+            ptr, ns = None, 0
+        else:
+            pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+            # (an empty array still stands for a recording, of no samples)
+            ptr, ns = (_ptr(pcm) if pcm.size else C.cast(C.pointer(C.c_float()), C.c_void_p)), pcm.size
+        _raise(lib().wmi_token_times(self._h, ptr, ns, int(seek), int(t0), int(t1), arr, len(tokens)), self._h)
+        return [arr[i].as_dict() for i in range(len(tokens))]
+
+    def energy(self, n: int):
+        """Clip 0's energy envelope of the token-level timestamps: (E uint32
+        [n], P uint64 [n + 1]) of the last recording given, of n samples (debug
+        reads 23, 24)."""
+        E = np.frombuffer(self.debug_read(23, 4 * n), np.uint32)
+        P = np.frombuffer(self.debug_read(24, 8 * (n + 1)), np.uint64)
+        return E, P
 
     def windows_of(self, clip: int = 0):
         """Window infos of recording `clip` of the last transcribe() /
