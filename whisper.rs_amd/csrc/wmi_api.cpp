@@ -254,6 +254,10 @@ struct wmi_context {
     // (n = 768, PersistArgs::vreg; round 4: small decode 42.3 -> 41.0 ms)
     bool persist_vreg = true;
     bool use_xshare = true;           // WMI_XSHARE=0: beam rows read the cross K / V per row
+    // one-row greedy launches (n <= PX_EOP_NMAX): cross tasks beside the self-attention
+    // workgroups, their operands requested a phase early (PersistArgs::early_ops;
+    // WMI_EARLY_OPERANDS=0: tasks from workgroup 0, operands requested in phase E)
+    int early_ops = 1;
     // greedy blocks of at least split_rows clips decode as two concurrent
     // half-grid launches (rows [0, B/2) and [B/2, B), each on half the CUs, a
     // second stream): a workgroup's all-to-all gathers carry half the rows
@@ -1333,13 +1337,16 @@ int run_dec_steps(wmi_context *ctx, const DecRun &run0, int pos0, int steps) {
 size_t hp_ptrace_slots(const wmi_hparams &hp) { return (size_t)hp.n_text_ctx * (hp.n_text_layer + 1) * 32 * 2; }
 
 // WMI_PTRACE: average phase durations of the persistent decoder's first
-// launch (workgroups 0 and G / 2), from the phase-end clocks (100 MHz)
-int ptrace_dump(wmi_context *ctx, int steps) {
+// launch (workgroups 0 and wg1: persist_trace_wg; beam launches G / 2), from
+// the phase-end clocks (100 MHz)
+int ptrace_dump(wmi_context *ctx, int steps, int wg1 = -1) {
     const int L = ctx->hp.n_text_layer;
     std::vector<unsigned long long> t(hp_ptrace_slots(ctx->hp));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, hipMemcpy(t.data(), ctx->d_ptrace, t.size() * 8, hipMemcpyDeviceToHost));
     auto at = [&](int st, int l, int k, int w) { return t[(((size_t)st * (L + 1) + l) * 32 + k) * 2 + w]; };
+    char wname[2][40] = {"0", "G/2"};
+    if (wg1 >= 0) snprintf(wname[1], sizeof wname[1], "%d (first E task)", wg1);
     static const char *nm[12] = {"A qkv", "B self", "C wo", "D xq", "E xscore", "F1 xexp", "F2 xpv", "G1 xred", "G2 wco", "H mlp0", "I mlp1", "logits"};
     for (int w = 0; w < 2; ++w) {
         double ph[12] = {0}, pw[12] = {0}, tot = 0;
@@ -1367,13 +1374,13 @@ int ptrace_dump(wmi_context *ctx, int steps) {
             l3 += (double)(at(st, L, 3, w) - e) * 0.01;
         }
         fprintf(stderr, "[wmi ptrace] wg %s: logits LN done %.2f, resident rows done %.2f, streamed rows done %.2f us\n",
-                w ? "G/2" : "0", l1 / ns, l2 / ns, l3 / ns);
+                wname[w], l1 / ns, l2 / ns, l3 / ns);
         if (steps > 2) {
             const double dc = (double)(at(steps - 1, L, 4, w) - at(1, L, 4, w));
             const double dt = (double)(at(steps - 1, L, 0, w) - at(1, L, 0, w)) * 10e-9;
-            fprintf(stderr, "[wmi ptrace] wg %s: shader clock %.3f GHz\n", w ? "G/2" : "0", dc / dt * 1e-9);
+            fprintf(stderr, "[wmi ptrace] wg %s: shader clock %.3f GHz\n", wname[w], dc / dt * 1e-9);
         }
-        fprintf(stderr, "[wmi ptrace] wg %s: step %.2f us; per phase (per layer) total / until input arrived:\n", w ? "G/2" : "0", tot / ns);
+        fprintf(stderr, "[wmi ptrace] wg %s: step %.2f us; per phase (per layer) total / until input arrived:\n", wname[w], tot / ns);
         for (int k = 0; k < 12; ++k) {
             const double d = k < 11 ? (double)ns * L : (double)ns;
             fprintf(stderr, "[wmi ptrace]   %-9s %6.2f / %6.2f\n", nm[k], ph[k] / d, pw[k] / d);
@@ -1452,6 +1459,7 @@ PersistArgs persist_args(wmi_context *ctx, const DecRun &run, int G) {
     a.xg = ctx->d_xg; a.err = ctx->derr;
     a.nres = ctx->persist_nres[B];
     a.vreg = ctx->persist_vreg ? 1 : 0;
+    a.early_ops = ctx->early_ops;
     a.stall_wg = -1;
     if (ctx->fault_inject == 1) {  // once per context: its first persistent launch
         a.stall_wg = G - 1;
@@ -1595,6 +1603,7 @@ int advance_run(wmi_context *ctx, const DecRun &run, RunGrid gr, int pos0, int s
         pa.n_steps = steps;
         pa.ptrace = ptrace;
         HIPCHK(ctx, launch_dec_persist(ctx->stream, pa, G));
+        if (ptrace && persist_trace_wg(pa, G) != G / 2) return ptrace_dump(ctx, steps, persist_trace_wg(pa, G));
     }
     return ptrace ? ptrace_dump(ctx, steps) : WMI_OK;
 }
@@ -2782,6 +2791,7 @@ static int wmi_init_from_file_impl(const char *path, int device, int max_clips, 
     if (const char *c = getenv("WMI_CHECKSUMS")) ctx->checksums = atoi(c) != 0;
     if (const char *c = getenv("WMI_FAULT_INJECT")) ctx->fault_inject = atoi(c) ? 1 : 0;
     if (const char *c = getenv("WMI_XSHARE")) ctx->use_xshare = atoi(c) != 0;
+    if (const char *c = getenv("WMI_EARLY_OPERANDS")) ctx->early_ops = atoi(c) != 0;
     if (const char *c = getenv("WMI_SPLIT_ROWS")) ctx->split_rows = atoi(c);
     ctx->dec_layers = ctx->hp.n_text_layer;
     if (const char *c = getenv("WMI_DEC_LAYERS")) ctx->dec_layers = std::max(1, std::min(atoi(c), ctx->hp.n_text_layer));

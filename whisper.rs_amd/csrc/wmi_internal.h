@@ -526,7 +526,46 @@ struct PersistArgs {
     // quarter-wave slot, at most 128 rows a workgroup) instead of streaming
     // every step (0: streamed; past 128 rows the kernel streams them anyway)
     int vreg;
+    // WMI_EARLY_OPERANDS (one-row greedy instances of n <= PX_EOP_NMAX): the cross
+    // tasks run on workgroups H .. H + ntask - 1 (px_e_first_task) and request
+    // their K / V rows, Wcq rows and LNc parameters in phase C, ahead of C's
+    // poll (0: tasks on workgroups 0 .., operands requested in phase E)
+    int early_ops;
 };
+// One-row cross-attention task placement: workgroup wg runs tasks first,
+// first + G, ... below ntask.  early (and room for it: H + ntask <= G): task t
+// on workgroup H + t, off the H workgroups whose self-attention task (phase B)
+// is on the step's critical path; else task t on workgroup t % G.
+__host__ __device__ constexpr bool px_e_early(bool early, int H, int ntask, int G) { return early && H + ntask <= G; }
+__host__ __device__ constexpr int px_e_first_task(bool early, int wg, int H, int ntask, int G) {
+    return px_e_early(early, H, ntask, G) ? (wg >= H ? wg - H : ntask) : wg;
+}
+// every task taken by exactly one workgroup, once
+constexpr bool px_e_tasks_once(bool early, int H, int nch, int G) {
+    const int ntask = H * nch;
+    for (int t = 0; t < ntask; ++t) {
+        int cnt = 0;
+        for (int wg = 0; wg < G; ++wg)
+            for (int u = px_e_first_task(early, wg, H, ntask, G); u < ntask; u += G) cnt += u == t;
+        if (cnt != 1) return false;
+    }
+    return true;
+}
+static_assert(px_e_tasks_once(true, 2, 12, 256) && px_e_tasks_once(true, 6, 12, 256) && px_e_tasks_once(true, 8, 12, 256) &&
+                  px_e_tasks_once(true, 12, 12, 256) && px_e_tasks_once(true, 12, 12, 192) && px_e_tasks_once(true, 2, 1, 256),
+              "cross tasks beside the self-attention workgroups");
+static_assert(px_e_tasks_once(true, 12, 24, 192) && px_e_tasks_once(false, 8, 12, 256) && px_e_tasks_once(false, 12, 12, 64),
+              "cross tasks where they do not fit beside them, or the knob is off");
+// the one-row instances that take the early placement: up to this n (at
+// n = 768 the operands do not fit beside the register-resident vocabulary
+// rows without scratch memory)
+constexpr int PX_EOP_NMAX = 512;
+// WMI_PTRACE's second stamped workgroup: G / 2, or the first cross-task
+// workgroup where workgroup 0 has none (px_e_first_task)
+inline int persist_trace_wg(const PersistArgs &a, int G) {
+    const int H = a.n / 64;
+    return a.B == 1 && !a.beam && a.n <= PX_EOP_NMAX && px_e_early(a.early_ops != 0, H, H * a.nch, G) ? H : G / 2;
+}
 hipError_t launch_dec_persist(hipStream_t s, const PersistArgs &a, int G);
 // the inputs whose f32 exp is too close to an f16 midpoint, with their table
 // values, into list[64] (count in *n; > 64 means the list is unusable)

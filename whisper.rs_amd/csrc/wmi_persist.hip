@@ -944,10 +944,13 @@ __device__ __forceinline__ float exp_f16_hash(float arg, const uint32_t *fbt, ui
     const int lane = tid & 63, w = tid >> 6, q = lane >> 4, l16 = lane & 15, slot = w * 4 + q; \
     (void)q; (void)l16; (void)slot;
 
-// WMI_PTRACE: thread 0 of workgroups 0 and G / 2 stamps the 100 MHz device
-// clock at the end of every phase of the first launch (host prints averages)
+// WMI_PTRACE: thread 0 of workgroups 0 and PTWG (G / 2, or the first cross-task
+// workgroup where those run beside the self-attention ones: workgroup 0 then
+// has no E task) stamps the 100 MHz device clock at the end of every phase of
+// the first launch (host prints averages)
+#define PTWG (EOP && eop ? H : G / 2)
 #define PSTAMP(ph)                                                                                    \
-    if (a.ptrace && threadIdx.x == 0 && (wg == 0 || wg == G / 2))                                     \
+    if (a.ptrace && threadIdx.x == 0 && (wg == 0 || wg == PTWG))                                      \
         a.ptrace[(((int64_t)step * (L + 1) + (ph) / 32) * 32 + ((ph) & 31)) * 2 + (wg == 0 ? 0 : 1)] = \
             __builtin_amdgcn_s_memrealtime();
 
@@ -958,6 +961,18 @@ __device__ __forceinline__ float exp_f16_hash(float arg, const uint32_t *fbt, ui
 // (the workgroup barrier in front of every poll stays even where no LDS
 // hazard needs it: without it the waves' polls spread out and the base step
 // took 142.5 vs 136.2 us, profiles/r04/prepoll_barrier_ab_REJECTED.txt)
+
+// A one-row cross task's operands where phase C requests them for phase E
+// (PersistArgs::early_ops): key and value rows, the head's 64 Wcq rows and the
+// LNc parameters, live across C's poll and dot.  Empty in the other instances.
+template <int NS, int NKE, bool ON>
+struct XOps {
+    half8 kf[NKE][4], vf[NKE][4];
+    WSet<NS / 128, 4> S;
+    Ln1P<NS> l1;
+};
+template <int NS, int NKE>
+struct XOps<NS, NKE, false> {};
 
 // BT: rows at compile time (1) or at most (8, runtime B); BEAM: beam-search
 // launches (self-attention history through kv_src; its index registers stay
@@ -992,6 +1007,12 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int L = a.L, T = a.T, tctx = a.tctx, nch = a.nch, CL = a.cl;
     const int nsub = (T + 127) >> 7;  // 128-key P.V partials per (row, head)
+    // one row, cross q inside the score tasks: task t on workgroup H + t, its
+    // operands requested in phase C (px_e_first_task; every other instance:
+    // task t on workgroup t % G, operands requested in E)
+    constexpr bool EOP = BT == 1 && XQF && NS <= PX_EOP_NMAX;
+    const bool eop = EOP && px_e_early(a.early_ops != 0, H, H * nch, G);
+    const int et0 = EOP ? px_e_first_task(eop, wg, H, H * nch, G) : wg;  // this workgroup's first E task
     // granules in flight per thread for the all-to-all polls (8-byte sc1
     // loads; one round of loads per L2/MALL round trip): the whole vector
     // in one round where registers allow
@@ -1080,6 +1101,40 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
         }
         __syncthreads();
         return true;
+    };
+
+    // key / value rows of cross task t = ((b * H + h) * nch + c) of layer l:
+    // the task's phase E requests them, or (eop) phase C ahead of it
+    auto xk_load = [&](int l, int t, int tid, half8 (&kf)[NKE][4]) {
+        const int c = t % nch, bh = t / nch, h = bh % H, b = bh / H;
+        const int j0 = c * CL, j1 = j0 + CL < T ? j0 + CL : T;
+        const int64_t cb = ((int64_t)l * a.Bt + a.b0 + (a.beam ? 0 : b)) * T * NS + h * 64;
+        const f16 *Kb = (const f16 *)a.ck + cb + (tid & 1) * 32;
+        const half8 z8 = {};
+#pragma unroll
+        for (int p = 0; p < NKE; ++p) {
+            int key = j0 + 128 * p + (tid >> 1);
+            key = key < j1 ? key : j1 - 1;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                kf[p][i] = 128 * p < CL ? sld((const half8 *)(Kb + (int64_t)key * NS + 8 * i)) : z8;
+        }
+    };
+    auto xv_load = [&](int l, int t, int tid, half8 (&vf)[NKE][4]) {
+        const int c = t % nch, bh = t / nch, h = bh % H, b = bh / H;
+        const int j0 = c * CL, j1 = j0 + CL < T ? j0 + CL : T;
+        const int64_t cb = ((int64_t)l * a.Bt + a.b0 + (a.beam ? 0 : b)) * T * NS + h * 64;
+        const int doct = tid & 7, jg = tid >> 3;
+        const f16 *Vb = (const f16 *)a.cv + cb + doct * 8;
+        const half8 z8 = {};
+#pragma unroll
+        for (int p = 0; p < NKE; ++p)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                int kv = j0 + 128 * p + jg * 4 + u;
+                kv = kv < j1 ? kv : j1 - 1;
+                vf[p][u] = 128 * p < CL ? sld((const half8 *)(Vb + (int64_t)kv * NS)) : z8;
+            }
     };
 
     int pos = a.st->pos;
@@ -1339,12 +1394,36 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
 
             PSTAMP(l * 32 + 1)
             // ---- C: Wo rows + residual -> x' ---------------------------
+            XOps<NS, NKE, EOP> XO;  // this workgroup's E task's operands, requested here (eop)
             {
                 PHASE_IDS
                 const uint32_t tag = ptag(pos, L, l, 2);
                 PSet<NS, BT, KC, 1, KS_N, Q5, false> S;
                 const bool act = rn0 < rn1;
                 S.load(lmat<Q5>(P.wo, P.wo5, NS * NS), P.bo, NS, rn0, rn1, slot, l16);
+                if constexpr (EOP) {
+                    // A workgroup without a self-attention task idles in this
+                    // poll for the length of phase B, and its E task's operands
+                    // (96 KB at base: one CU takes ~2 us to pull them from the
+                    // Infinity Cache) otherwise land in front of E's poll of x',
+                    // whose first round cannot retire before them (vmcnt
+                    // retires in order).  Requested here, behind C's own
+                    // weights, they arrive during the idle wait and E polls
+                    // with nothing queued.
+                    // (XO is left undefined where there is no task, against
+                    // the rule at phase B's arrays: zeros here are ~136 moves
+                    // in front of this poll on the self-attention workgroups,
+                    // the ones every other workgroup is waiting for — base
+                    // 14.72 vs 14.43 ms decode.  It costs registers instead,
+                    // 348 -> 388 at n = 512, none of them scratch.)
+                    if (eop && et0 < H * nch) {  // workgroup-uniform
+                        const int h = (et0 / nch) % H;
+                        xk_load(l, et0, tid, XO.kf);
+                        xv_load(l, et0, tid, XO.vf);
+                        wset_load(XO.S, wmat(P.wcq), P.bcq, NS, h * 64, h * 64 + 64, slot, l16);
+                        ln1_params<NS>(P.lnc_w, P.lnc_b, XO.l1, tid);
+                    }
+                }
                 PREFETCH_ISSUED
                 __syncthreads();
                 const bool ok = gpoll<PUX>(B * NS / 2, ptag(pos, L, l, 1), ptr_u64(xg + oO), (uint32_t *)xs, abortw, a.err,
@@ -1517,7 +1596,7 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
                     f16 *qh = (f16 *)scr;                 // [64] this task's cross q
                     float *st = (float *)(scr + XS_OFF);  // [NKE][128] p
                     const int ntask = B * H * nch;
-                    for (int t = wg; t < ntask; t += G) {
+                    for (int t = et0; t < ntask; t += G) {
                         const int c = t % nch, bh = t / nch, h = bh % H, b = bh / H;
                         const int j0 = c * CL, j1 = j0 + CL < T ? j0 + CL : T;
                         const int64_t cb = ((int64_t)l * a.Bt + a.b0 + (a.beam ? 0 : b)) * T * NS + h * 64;
@@ -1525,13 +1604,17 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
                         const f16 *Vb = (const f16 *)a.cv + cb + doct * 8;
                         half8 kf[NKE][4], vf[NKE][4];
                         const half8 z8 = {};
+                        // (eop: the task's operands were requested in phase C
+                        // — XO, by xk_load / xv_load, which restate these loads)
+                        if (!eop) {
 #pragma unroll
-                        for (int p = 0; p < NKE; ++p) {
-                            int key = j0 + 128 * p + (tid >> 1);
-                            key = key < j1 ? key : j1 - 1;
+                            for (int p = 0; p < NKE; ++p) {
+                                int key = j0 + 128 * p + (tid >> 1);
+                                key = key < j1 ? key : j1 - 1;
 #pragma unroll
-                            for (int i = 0; i < 4; ++i)
-                                kf[p][i] = 128 * p < CL ? sld((const half8 *)(Kb + (int64_t)key * NS + 8 * i)) : z8;
+                                for (int i = 0; i < 4; ++i)
+                                    kf[p][i] = 128 * p < CL ? sld((const half8 *)(Kb + (int64_t)key * NS + 8 * i)) : z8;
+                            }
                         }
                         auto v_load = [&] {
 #pragma unroll
@@ -1547,14 +1630,37 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
                         // computes its cross q — the q GEMV covers them — else
                         // behind the poll of q, which then waits for the key
                         // rows only: vmcnt retires in order)
-                        if constexpr (XQF) v_load();
+                        if constexpr (XQF) {
+                            if (!eop) v_load();
+                        }
+                        if constexpr (EOP) {
+                            if (eop) {
+#pragma unroll
+                                for (int p = 0; p < NKE; ++p)
+#pragma unroll
+                                    for (int i = 0; i < 4; ++i) {
+                                        kf[p][i] = XO.kf[p][i];
+                                        vf[p][i] = XO.vf[p][i];
+                                    }
+                            }
+                        }
                         if constexpr (XQF) {
                             // this head's cross q from x' directly: LNc(x'_b) and
                             // Wcq rows h*64 .. h*64+63, the D phase's arithmetic
                             WSet<KC, 4> S;
-                            wset_load(S, wmat(P.wcq), P.bcq, NS, h * 64, h * 64 + 64, slot, l16);
                             Ln1P<NS> l1;  // (the whole workgroup's LayerNorm of row b from the poll registers)
-                            ln1_params<NS>(P.lnc_w, P.lnc_b, l1, tid);
+                            bool req = true;
+                            if constexpr (EOP) {
+                                if (eop) {
+                                    S = XO.S;
+                                    l1 = XO.l1;
+                                    req = false;
+                                }
+                            }
+                            if (req) {
+                                wset_load(S, wmat(P.wcq), P.bcq, NS, h * 64, h * 64 + 64, slot, l16);
+                                ln1_params<NS>(P.lnc_w, P.lnc_b, l1, tid);
+                            }
                             PREFETCH_ISSUED
                             __syncthreads();
                             if (!poll_ln1<NS>(xg + oX2 + b * NS, ptag(pos, L, l, 2), l1, xf, xs, abortw, a.err, sh.redd,
@@ -2145,7 +2251,7 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
             }
         }
         PSTAMP(L * 32 + 0)
-        if (a.ptrace && threadIdx.x == 0 && (wg == 0 || wg == G / 2))  // shader clock (s_memtime) at the same point
+        if (a.ptrace && threadIdx.x == 0 && (wg == 0 || wg == PTWG))  // shader clock (s_memtime) at the same point
             a.ptrace[(((int64_t)step * (L + 1) + L) * 32 + 4) * 2 + (wg == 0 ? 0 : 1)] = __builtin_amdgcn_s_memtime();
     }
     // the last step's token: recorded by workgroup 0 and carried to the next launch
