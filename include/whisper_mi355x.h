@@ -474,6 +474,73 @@ int wmi_set_token_timestamps(wmi_context *ctx, const wmi_token_ts_params *params
 int wmi_token_times(wmi_context *ctx, const float *pcm, size_t n_samples, int64_t seek, int64_t t0, int64_t t1,
                     wmi_token_data *tokens, int n);
 
+/* ---- audio of any format: downmix, conversion, resampling on the device --- */
+
+/* A clip is N = n_frames frames of C = channels interleaved samples at R =
+ * sample_rate Hz, s16 or f32 (what wmi_read_wav returns for a file: its
+ * samples, n_samples / channels frames, rate and channels).  The raw samples go
+ * to the device once; these steps run there and leave y, 16 kHz mono f32, in
+ * the buffer the mel kernels read.  Each output is stated so that any
+ * summation order, tile shape or chunking gives the same bits.
+ *   1  Mono x_i, f32, i in [0, N).  s16: x_i = (float)((double)S_i / (32768.0
+ *      * C)), S_i the integer sum of the frame's channels (C = 1: exactly
+ *      wmi_pcm16_to_f32).  f32: C = 1 the sample unchanged, else x_i =
+ *      (float)((sum over c ascending of (double)s_ic) / (double)C).
+ *   2  Plan.  g = gcd(R, 16000), L = 16000 / g, M = R / g; Z = 64, K =
+ *      ceil(Z max(L, M) / L); a phase has 2K taps.  Accepted: 4000 <= R <=
+ *      384000 with L <= 640 (8000, 11025, 12000, 16000, 22050, 24000, 32000,
+ *      44100, 48000, 88200, 96000, 176400, 192000 among them; the largest
+ *      table, for 11025, has 81,920 entries); any other rate is
+ *      WMI_E_UNSUPPORTED.  R = 16000: L = M = 1, no filter, y = x.
+ *   3  Taps h[ph][j], ph in [0, L), j in [0, 2K), computed in double on the
+ *      host, stored f32: c = 0.95 min(1, L / M), d = (j - K + 1) - ph / L,
+ *      h = c sinc(c d) w(d / K); sinc(t) = sin(pi t) / (pi t), 1 at t = 0;
+ *      w(r) = I0(10 sqrt(1 - r^2)) / I0(10) for |r| < 1, else 0; I0(x) = the
+ *      sum over k of ((x / 2)^k / k!)^2, ascending until a term falls below
+ *      2^-60 of the sum.  Each phase row is divided by its own sum in double,
+ *      then rounded to f32.
+ *   4  Output.  N_out = floor((N L + M - 1) / M).  For n in [0, N_out): p =
+ *      n M (64-bit), i0 = p / L, ph = p mod L; s_r = the sum over j = r (mod
+ *      4), ascending, of (double)h[ph][j] * (double)x[i0 + j - K + 1], x = 0
+ *      outside [0, N); y_n = (float)((s_0 + s_1) + (s_2 + s_3)).  (An f32 x
+ *      f32 product is exact in double, so contraction changes no bit.)
+ * Each clip has its own format.  Times (segments, token timestamps, seek)
+ * are those of y, which is real time; wmi_set_token_timestamps works on y and
+ * its 2^26 bound applies to N_out; after wmi_transcribe_audio,
+ * wmi_token_times(pcm = NULL) uses that recording.  A clip of 16 kHz, mono,
+ * f32 takes exactly the upload of the float entry points (no kernel).
+ * WMI_E_INVALID_ARG: channels outside [1, 8], a sample type other than the
+ * two, data = NULL with frames, n_frames above 2^31 - 1; WMI_E_UNSUPPORTED: a
+ * rate outside the plan.  A failed call leaves the context's clips as they
+ * were.  Raw input passes through a bounded device staging buffer in chunks
+ * of at most 2^22 frames (WMI_AUDIO_CHUNK = frames overrides, read once per
+ * context) plus K-frame halos.  With WMI_CHECKSUMS=1 the samples checksum is
+ * taken over y, copied back. */
+enum wmi_sample_type { WMI_SAMPLE_F32 = 0, WMI_SAMPLE_S16 = 1 };
+typedef struct wmi_audio {
+    const void *data;
+    size_t n_frames;
+    int32_t sample_rate, channels, sample_type;
+} wmi_audio;
+/* wmi_pcm_to_mel_batch / wmi_stage_pcm / wmi_transcribe / wmi_transcribe_batch on y */
+int wmi_audio_to_mel_batch(wmi_context *ctx, int n_clips, const wmi_audio *clips);
+int wmi_stage_audio(wmi_context *ctx, int n_clips, const wmi_audio *clips);
+int wmi_transcribe_audio(wmi_context *ctx, const wmi_audio *clip, int max_tokens, int32_t *n_segments);
+int wmi_transcribe_audio_batch(wmi_context *ctx, int n_clips, const wmi_audio *clips, int max_tokens,
+                               int32_t *n_segments);
+/* The 16 kHz mono samples clip holds (whichever entry point loaded it); *n =
+ * their count; WMI_E_NO_SPACE if cap is below it (out may be NULL to ask). */
+int wmi_get_pcm(const wmi_context *ctx, int clip, float *out, size_t cap, size_t *n);
+/* Device time of the conversion in the last audio call (hipEvents) and the
+ * clips it ran a kernel for (0 for clips that are 16 kHz mono f32). */
+int wmi_get_audio_timing(const wmi_context *ctx, float *convert_ms, int32_t *n_converted);
+/* Host only, no context, no device: the plan (L, M, K), the table [L][2K]
+ * (*n = its entries; WMI_E_NO_SPACE if cap is below; h may be NULL to ask)
+ * and N_out.  Any of the out pointers may be NULL. */
+int wmi_resample_plan(int32_t sample_rate, int32_t *L, int32_t *M, int32_t *K);
+int wmi_resample_taps(int32_t sample_rate, float *h, size_t cap, size_t *n);
+int wmi_resampled_length(int32_t sample_rate, size_t n_frames, size_t *n_out);
+
 /* ---- device-resident benchmark path --------------------------------- */
 
 /* Upload n_clips PCM clips to HBM once (untimed). */

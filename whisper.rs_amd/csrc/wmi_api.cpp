@@ -210,6 +210,16 @@ struct wmi_context {
     size_t mel_cap = 0;
     int64_t mel_stride = 0, max_len = 0;
     std::vector<int64_t> n_len_host, n_samp_host;
+    // audio of any format (stage_audio): the taps uploaded per rate, rows au_stride(K) floats apart; raw input
+    // passes through au_raw a chunk of au_chunk frames (WMI_AUDIO_CHUNK) plus halos at a time, its mono in au_mono
+    std::map<int32_t, float *> au_taps;
+    void *au_raw = nullptr;
+    float *au_mono = nullptr;
+    size_t au_raw_cap = 0, au_mono_cap = 0;  // bytes, floats
+    long long au_chunk = AUDIO_CHUNK_MAX;
+    std::vector<hipEvent_t> au_ev;           // event pairs around the conversion launches of a call
+    float au_ms = 0.0f;                      // wmi_get_audio_timing
+    int au_converted = 0;
     int n_clips = 0;   // clips loaded by the last pcm_to_mel / stage
     int enc_T = 0;     // n_ctx of the last encode (0 = none)
     int enc_clips = 0;
@@ -865,6 +875,181 @@ int stage_pcm(wmi_context *ctx, int n_clips, const float *const *pcm, const size
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->n_clips = n_clips;
     ctx->enc_T = 0;
+    return WMI_OK;
+}
+
+// ---- audio of any format (the header's "audio of any format"; DESIGN.md "Audio front end") ----
+struct AudioPlan {
+    int32_t L = 1, M = 1, K = 0;
+    size_t n_out = 0;
+    bool plain = false;  // 16 kHz mono f32: the float path's upload, no kernel
+};
+
+// every clip's arguments and plan, before the context is touched
+int audio_check_clips(wmi_context *ctx, int n_clips, const wmi_audio *clips, std::vector<AudioPlan> &plans) {
+    if (n_clips < 1 || n_clips > ctx->max_clips || !clips)
+        return set_err(ctx, WMI_E_INVALID_ARG, "n_clips %d outside [1, max_clips=%d], or null clips", n_clips, ctx->max_clips);
+    plans.assign(n_clips, AudioPlan());
+    for (int c = 0; c < n_clips; ++c) {
+        const wmi_audio &a = clips[c];
+        if (a.channels < 1 || a.channels > AUDIO_CH_MAX)
+            return set_err(ctx, WMI_E_INVALID_ARG, "clip %d: %d channels outside [1, %d]", c, a.channels, AUDIO_CH_MAX);
+        if (a.sample_type != WMI_SAMPLE_F32 && a.sample_type != WMI_SAMPLE_S16)
+            return set_err(ctx, WMI_E_INVALID_ARG, "clip %d: sample type %d is neither f32 (0) nor s16 (1)", c, a.sample_type);
+        if (a.n_frames > (size_t)INT32_MAX)
+            return set_err(ctx, WMI_E_INVALID_ARG, "clip %d: %zu frames above 2^31 - 1", c, a.n_frames);
+        if (a.n_frames && !a.data) return set_err(ctx, WMI_E_INVALID_ARG, "clip %d: null data with %zu frames", c, a.n_frames);
+        AudioPlan &p = plans[c];
+        if (resample_plan(a.sample_rate, &p.L, &p.M, &p.K))
+            return set_err(ctx, WMI_E_UNSUPPORTED, "clip %d: sample rate %d outside the resampling plan (4000 to 384000 Hz "
+                           "with 16000 / gcd(rate, 16000) <= 640)", c, a.sample_rate);
+        (void)resampled_length(p.L, p.M, a.n_frames, &p.n_out);  // (at most 2^31 * 640)
+        p.plain = a.sample_rate == 16000 && a.channels == 1 && a.sample_type == WMI_SAMPLE_F32;
+    }
+    return WMI_OK;
+}
+
+// the taps of a rate on the device, uploaded once per context: [L][up4(2K)] f32
+int audio_taps(wmi_context *ctx, int32_t rate, const AudioPlan &p, const float **out, int *stride) {
+    *stride = (int)up(2 * p.K, 4);
+    auto it = ctx->au_taps.find(rate);
+    if (it == ctx->au_taps.end()) {
+        std::vector<float> h((size_t)p.L * *stride, 0.0f);
+        resample_taps(p.L, p.M, p.K, h.data(), (size_t)*stride);
+        float *d = nullptr;
+        HIPCHK(ctx, hipMalloc(&d, h.size() * 4));
+        it = ctx->au_taps.emplace(rate, d).first;
+        HIPCHK(ctx, hipMemcpyAsync(d, h.data(), h.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (h leaves scope)
+    }
+    *out = it->second;
+    return WMI_OK;
+}
+
+// Clip c's raw frames -> y in pcm_dev[c], a chunk of frames [c0, c1) at a time:
+// the chunk and K frames each side (inside the clip) are uploaded and made
+// mono, then the outputs whose first frame i0 lies in the chunk are computed
+// (n M >= c0 L up to n M < c1 L); at 16 kHz the mono goes straight into y.
+// Every chunk's launches lie between an event pair of their own (*n_ev counts the events).
+int audio_convert(wmi_context *ctx, int c, const wmi_audio &a, const AudioPlan &p, size_t *n_ev) {
+    const long long N = (long long)a.n_frames;
+    const bool s16 = a.sample_type == WMI_SAMPLE_S16, fir = a.sample_rate != 16000;
+    const size_t fb = (size_t)a.channels * (s16 ? 2 : 4);  // bytes a frame
+    const long long halo = fir ? p.K : 0;
+    // (16 kHz: a chunk starts on a 16-byte boundary of y)
+    const long long chunk = fir ? ctx->au_chunk : std::max(8ll, ctx->au_chunk & ~7ll);
+    const float *taps = nullptr;
+    int hs = 0;
+    if (fir) {
+        int rc = audio_taps(ctx, a.sample_rate, p, &taps, &hs);
+        if (rc) return rc;
+    }
+    const size_t frames_max = (size_t)(std::min(N, chunk) + 2 * halo);
+    if (frames_max * fb > ctx->au_raw_cap) {
+        if (ctx->au_raw) HIPCHK(ctx, hipFree(ctx->au_raw));
+        ctx->au_raw = nullptr; ctx->au_raw_cap = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->au_raw, frames_max * fb));
+        ctx->au_raw_cap = frames_max * fb;
+    }
+    if (fir && frames_max > ctx->au_mono_cap) {
+        if (ctx->au_mono) HIPCHK(ctx, hipFree(ctx->au_mono));
+        ctx->au_mono = nullptr; ctx->au_mono_cap = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->au_mono, frames_max * 4));
+        ctx->au_mono_cap = frames_max;
+    }
+    for (long long c0 = 0; c0 < N; c0 += chunk) {
+        const long long c1 = std::min(N, c0 + chunk);
+        const long long f0 = std::max(0ll, c0 - halo), f1 = std::min(N, c1 + halo);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->au_raw, (const char *)a.data + (size_t)f0 * fb, (size_t)(f1 - f0) * fb,
+                                   hipMemcpyHostToDevice, ctx->stream));
+        while (ctx->au_ev.size() < *n_ev + 2) {
+            hipEvent_t e;
+            HIPCHK(ctx, hipEventCreate(&e));
+            ctx->au_ev.push_back(e);
+        }
+        HIPCHK(ctx, hipEventRecord(ctx->au_ev[*n_ev], ctx->stream));
+        HIPCHK(ctx, launch_audio_mono(ctx->stream, ctx->au_raw, f1 - f0, a.channels, s16, fir ? ctx->au_mono : ctx->pcm_dev[c] + c0));
+        if (fir) {
+            // the outputs of the chunk: ceil(c0 L / M) <= n < ceil(c1 L / M) (the last chunk's end is N_out)
+            const long long n_lo = (c0 * p.L + p.M - 1) / p.M, n_hi = (c1 * p.L + p.M - 1) / p.M;
+            if (n_hi > n_lo) {
+                const FirArgs fa{ctx->au_mono, f0, f1 - f0, N, taps, p.L, p.M, p.K, hs, n_lo, n_hi, ctx->pcm_dev[c]};
+                HIPCHK(ctx, launch_audio_fir(ctx->stream, fa));
+            }
+        }
+        HIPCHK(ctx, hipEventRecord(ctx->au_ev[*n_ev + 1], ctx->stream));
+        *n_ev += 2;
+    }
+    return WMI_OK;
+}
+
+// stage_pcm for clips of any format: the same pcm_dev[c], n_samp_host and
+// n_len_host, filled with y.  Nothing of the context changes before every
+// clip's arguments have passed.
+int stage_audio(wmi_context *ctx, int n_clips, const wmi_audio *clips) {
+    std::vector<AudioPlan> plans;
+    int rc = audio_check_clips(ctx, n_clips, clips, plans);
+    if (rc) return rc;
+    ctx->pcm_dev.resize(ctx->max_clips, nullptr);
+    ctx->pcm_cap.resize(ctx->max_clips, 0);
+    std::vector<float *> ptrs(n_clips);
+    ctx->n_len_host.assign(n_clips, 0);
+    ctx->n_samp_host.assign(n_clips, 0);
+    ctx->n_clips = 0;  // (until the clips are whole again)
+    ctx->enc_T = 0;
+    ctx->au_ms = 0.0f;
+    ctx->au_converted = 0;
+    size_t n_ev = 0;
+    int64_t max_len = 0;
+    for (int c = 0; c < n_clips; ++c) {
+        const size_t ns = plans[c].n_out;
+        if (ns + 64 > ctx->pcm_cap[c]) {
+            if (ctx->pcm_dev[c]) HIPCHK(ctx, hipFree(ctx->pcm_dev[c]));
+            ctx->pcm_dev[c] = nullptr; ctx->pcm_cap[c] = 0;
+            HIPCHK(ctx, hipMalloc(&ctx->pcm_dev[c], (ns + 64) * 4));
+            ctx->pcm_cap[c] = ns + 64;
+        }
+        if (plans[c].plain) {
+            if (ns) HIPCHK(ctx, hipMemcpyAsync(ctx->pcm_dev[c], clips[c].data, ns * 4, hipMemcpyHostToDevice, ctx->stream));
+        } else if (ns) {
+            rc = audio_convert(ctx, c, clips[c], plans[c], &n_ev);
+            if (rc) return rc;
+            ++ctx->au_converted;
+        }
+        if (ctx->checksums && c == 0) {  // main.rs:1682-1686 over y, clip 0
+            std::vector<float> y(ns);
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            if (ns) HIPCHK(ctx, hipMemcpy(y.data(), ctx->pcm_dev[0], ns * 4, hipMemcpyDeviceToHost));
+            float x = 0.0f;
+            for (float v : y) x += v;
+            ctx->cks[1] = x;
+        }
+        ptrs[c] = ctx->pcm_dev[c];
+        ctx->n_samp_host[c] = (int64_t)ns;
+        ctx->n_len_host[c] = (int64_t)(ns / 160);  // main.rs:1575
+        if (ctx->n_len_host[c] > max_len) max_len = ctx->n_len_host[c];
+    }
+    const int64_t n_mel = ctx->hp.n_mels;
+    const size_t need = (size_t)n_clips * n_mel * (max_len > 0 ? max_len : 1);
+    if (need > ctx->mel_cap) {
+        if (ctx->d_mel) HIPCHK(ctx, hipFree(ctx->d_mel));
+        ctx->d_mel = nullptr; ctx->mel_cap = 0;
+        const size_t cap = (size_t)ctx->max_clips * n_mel * (max_len > 0 ? max_len : 1);
+        HIPCHK(ctx, hipMalloc(&ctx->d_mel, cap * 4));
+        ctx->mel_cap = cap;
+    }
+    ctx->mel_stride = n_mel * (max_len > 0 ? max_len : 1);
+    ctx->max_len = max_len;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_pcm_ptrs, ptrs.data(), n_clips * sizeof(float *), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_nsamp, ctx->n_samp_host.data(), n_clips * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_nlen, ctx->n_len_host.data(), n_clips * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n_ev; i += 2) {
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, ctx->au_ev[i], ctx->au_ev[i + 1]);
+        ctx->au_ms += ms;
+    }
+    ctx->n_clips = n_clips;
     return WMI_OK;
 }
 
@@ -2793,6 +2978,7 @@ static int wmi_init_from_file_impl(const char *path, int device, int max_clips, 
     if (const char *c = getenv("WMI_XSHARE")) ctx->use_xshare = atoi(c) != 0;
     if (const char *c = getenv("WMI_EARLY_OPERANDS")) ctx->early_ops = atoi(c) != 0;
     if (const char *c = getenv("WMI_SPLIT_ROWS")) ctx->split_rows = atoi(c);
+    if (const char *c = getenv("WMI_AUDIO_CHUNK")) ctx->au_chunk = std::max(1ll, std::min(atoll(c), AUDIO_CHUNK_MAX));
     ctx->dec_layers = ctx->hp.n_text_layer;
     if (const char *c = getenv("WMI_DEC_LAYERS")) ctx->dec_layers = std::max(1, std::min(atoi(c), ctx->hp.n_text_layer));
     ctx->enc_layers = ctx->hp.n_audio_layer;
@@ -2836,6 +3022,10 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
     ctx->clear_graphs();
     for (float *p : ctx->pcm_dev) if (p) (void)hipFree(p);
+    for (auto &kv : ctx->au_taps) if (kv.second) (void)hipFree(kv.second);
+    if (ctx->au_raw) (void)hipFree(ctx->au_raw);
+    if (ctx->au_mono) (void)hipFree(ctx->au_mono);
+    for (hipEvent_t e : ctx->au_ev) (void)hipEventDestroy(e);
     for (uint32_t *p : ctx->tt_E) if (p) (void)hipFree(p);
     for (unsigned long long *p : ctx->tt_P) if (p) (void)hipFree(p);
     if (ctx->tt_tsum) (void)hipFree(ctx->tt_tsum);
@@ -3496,6 +3686,116 @@ static int wmi_stage_pcm_impl(wmi_context *ctx, int n_clips, const float *const 
     if (!valid(ctx)) return WMI_E_INVALID_ARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return stage_pcm(ctx, n_clips, pcm, n_samples);
+}
+
+// ---- audio of any format: the float entry points' siblings --------------------
+static int wmi_stage_audio_impl(wmi_context *ctx, int n_clips, const wmi_audio *clips) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return stage_audio(ctx, n_clips, clips);
+}
+
+static int wmi_audio_to_mel_batch_impl(wmi_context *ctx, int n_clips, const wmi_audio *clips) {
+    int rc = wmi_stage_audio_impl(ctx, n_clips, clips);
+    if (rc) return rc;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    rc = run_mel(ctx);
+    if (rc) return rc;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
+    ctx->timings.mel_ms = ms;
+    return WMI_OK;
+}
+
+// the 2^26 bound of the token-level timestamps on every clip's N_out, before anything is uploaded
+static int audio_tt_check(wmi_context *ctx, int n_clips, const wmi_audio *clips) {
+    std::vector<AudioPlan> plans;
+    int rc = audio_check_clips(ctx, n_clips, clips, plans);
+    if (rc) return rc;
+    std::vector<size_t> n_out(n_clips);
+    for (int c = 0; c < n_clips; ++c) n_out[c] = plans[c].n_out;
+    return tt_check_samples(ctx, n_clips, n_out.data());
+}
+
+static int wmi_transcribe_audio_impl(wmi_context *ctx, const wmi_audio *clip, int max_tokens, int32_t *n_segments) {
+    if (!valid(ctx) || !clip || max_tokens < 1 || !n_segments)
+        return set_err(ctx, WMI_E_INVALID_ARG, "null context / clip / n_segments, or max_tokens %d below 1", max_tokens);
+    int rc = rules_beam_unsupported(ctx, ctx->beam_size);
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    rc = audio_tt_check(ctx, 1, clip);
+    if (rc) return rc;
+    rc = wmi_audio_to_mel_batch_impl(ctx, 1, clip);
+    if (rc) return rc;
+    rc = tt_energy_of_clips(ctx, 1);
+    if (rc) return rc;
+    rc = run_transcribe(ctx, max_tokens);
+    if (rc) return rc;
+    *n_segments = (int32_t)ctx->results[0].segments.size();
+    return WMI_OK;
+}
+
+static int wmi_transcribe_audio_batch_impl(wmi_context *ctx, int n_clips, const wmi_audio *clips, int max_tokens,
+                                           int32_t *n_segments) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (n_clips < 1 || n_clips > ctx->max_clips)
+        return set_err(ctx, WMI_E_INVALID_ARG, "n_clips %d outside [1, max_clips=%d]", n_clips, ctx->max_clips);
+    if (!clips || !n_segments) return set_err(ctx, WMI_E_INVALID_ARG, "null clips / n_segments");
+    if (max_tokens < 1) return set_err(ctx, WMI_E_INVALID_ARG, "max_tokens %d below 1", max_tokens);
+    if (ctx->beam_size > 1)  // (as wmi_transcribe_batch)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "wmi_transcribe_audio_batch decodes greedily only: beam size %d is set "
+                       "(wmi_set_beam_size(ctx, 1), or wmi_transcribe_audio per recording)", ctx->beam_size);
+    for (int c = 0; c < n_clips; ++c)
+        if (ctx->n_lang == 0 && (ctx->lang_set[c] != 0 || ctx->task != WMI_TASK_TRANSCRIBE))
+            return set_err(ctx, WMI_E_INVALID_ARG, "language %d / task %d on an English-only model (clip %d)",
+                           ctx->lang_set[c], ctx->task, c);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = audio_tt_check(ctx, n_clips, clips);
+    if (rc) return rc;
+    rc = wmi_audio_to_mel_batch_impl(ctx, n_clips, clips);
+    if (rc) return rc;
+    rc = tt_energy_of_clips(ctx, n_clips);
+    if (rc) return rc;
+    rc = run_transcribe_batch(ctx, max_tokens);
+    if (rc) return rc;
+    for (int c = 0; c < n_clips; ++c) n_segments[c] = (int32_t)ctx->results[c].segments.size();
+    return WMI_OK;
+}
+
+static int wmi_get_pcm_impl(const wmi_context *ctx, int clip, float *out, size_t cap, size_t *n) {
+    wmi_context *ec = const_cast<wmi_context *>(ctx);  // (last_error only)
+    if (!valid(ctx)) return set_err(ec, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (clip < 0 || clip >= ctx->n_clips) return set_err(ec, WMI_E_INVALID_ARG, "clip %d outside the %d loaded", clip, ctx->n_clips);
+    const size_t ns = (size_t)ctx->n_samp_host[clip];
+    if (n) *n = ns;
+    if (cap < ns || (!out && ns)) return WMI_E_NO_SPACE;
+    HIPCHK(ec, hipSetDevice(ctx->device));
+    if (ns) HIPCHK(ec, hipMemcpy(out, ctx->pcm_dev[clip], ns * 4, hipMemcpyDeviceToHost));
+    return WMI_OK;
+}
+
+int wmi_stage_audio(wmi_context *ctx, int n_clips, const wmi_audio *clips) {
+    return guarded(ctx, [&] { return wmi_stage_audio_impl(ctx, n_clips, clips); });
+}
+int wmi_audio_to_mel_batch(wmi_context *ctx, int n_clips, const wmi_audio *clips) {
+    return guarded(ctx, [&] { return wmi_audio_to_mel_batch_impl(ctx, n_clips, clips); });
+}
+int wmi_transcribe_audio(wmi_context *ctx, const wmi_audio *clip, int max_tokens, int32_t *n_segments) {
+    return guarded(ctx, [&] { return wmi_transcribe_audio_impl(ctx, clip, max_tokens, n_segments); });
+}
+int wmi_transcribe_audio_batch(wmi_context *ctx, int n_clips, const wmi_audio *clips, int max_tokens, int32_t *n_segments) {
+    return guarded(ctx, [&] { return wmi_transcribe_audio_batch_impl(ctx, n_clips, clips, max_tokens, n_segments); });
+}
+int wmi_get_pcm(const wmi_context *ctx, int clip, float *out, size_t cap, size_t *n) {
+    return guarded(const_cast<wmi_context *>(ctx), [&] { return wmi_get_pcm_impl(ctx, clip, out, cap, n); });
+}
+int wmi_get_audio_timing(const wmi_context *ctx, float *convert_ms, int32_t *n_converted) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    if (convert_ms) *convert_ms = ctx->au_ms;
+    if (n_converted) *n_converted = ctx->au_converted;
+    return WMI_OK;
 }
 
 int wmi_run_staged(wmi_context *ctx, int mel_offset, int n_decode) { return wmi_run_staged_beam(ctx, mel_offset, n_decode, 0); }

@@ -605,6 +605,61 @@ std::vector<TokPiece> split_segment(const std::vector<std::string> &vocab, int32
     return out;
 }
 
+// ---------------------------------------------------------------------------
+// audio of any rate: the polyphase plan and its Kaiser-windowed sinc taps
+// (the header's "audio of any format", steps 2 and 3; all in double)
+// ---------------------------------------------------------------------------
+int resample_plan(int32_t sample_rate, int32_t *L, int32_t *M, int32_t *K) {
+    if (sample_rate < 4000 || sample_rate > 384000) return WMI_E_UNSUPPORTED;
+    int64_t a = sample_rate, b = 16000;
+    while (b) { const int64_t t = a % b; a = b; b = t; }
+    const int64_t l = 16000 / a, m = sample_rate / a;
+    if (l > 640) return WMI_E_UNSUPPORTED;
+    const int64_t big = l > m ? l : m;
+    if (L) *L = (int32_t)l;
+    if (M) *M = (int32_t)m;
+    if (K) *K = (int32_t)((64 * big + l - 1) / l);
+    return WMI_OK;
+}
+
+// I0(x) = sum over k of ((x / 2)^k / k!)^2, ascending until a term falls below 2^-60 of the sum
+static double bessel_i0(double x) {
+    const double q = x / 2.0;
+    double t = 1.0, sum = 1.0;
+    for (int k = 1; k < 1000; ++k) {
+        t *= q / (double)k;
+        const double term = t * t;
+        sum += term;
+        if (term < sum * 0x1p-60) break;
+    }
+    return sum;
+}
+
+void resample_taps(int32_t L, int32_t M, int32_t K, float *h, size_t stride) {
+    const double PI = 3.14159265358979323846264338327950288;
+    const double c = 0.95 * (L < M ? (double)L / (double)M : 1.0), i0_10 = bessel_i0(10.0);
+    std::vector<double> row((size_t)2 * K);
+    for (int32_t ph = 0; ph < L; ++ph) {
+        double sum = 0.0;
+        for (int32_t j = 0; j < 2 * K; ++j) {
+            const double d = (double)(j - K + 1) - (double)ph / (double)L;
+            const double t = c * d, r = d / (double)K;
+            const double sinc = t == 0.0 ? 1.0 : sin(PI * t) / (PI * t);
+            const double w = fabs(r) < 1.0 ? bessel_i0(10.0 * sqrt(1.0 - r * r)) / i0_10 : 0.0;
+            row[(size_t)j] = c * sinc * w;
+            sum += row[(size_t)j];
+        }
+        for (int32_t j = 0; j < 2 * K; ++j) h[(size_t)ph * stride + (size_t)j] = (float)(row[(size_t)j] / sum);
+    }
+}
+
+bool resampled_length(int32_t L, int32_t M, size_t N, size_t *n_out) {
+    const unsigned __int128 v = ((unsigned __int128)N * (unsigned)L + (unsigned)(M - 1)) / (unsigned)M;
+    if (v > (unsigned __int128)SIZE_MAX) return false;
+    *n_out = (size_t)v;
+    return true;
+}
+
 }  // namespace wmi
 
 extern "C" {
@@ -634,6 +689,33 @@ const char *wmi_strerror(int status) {
 int wmi_pcm16_to_f32(const int16_t *s16, size_t n, float *out) {
     if ((!s16 || !out) && n) return WMI_E_INVALID_ARG;
     for (size_t i = 0; i < n; ++i) out[i] = (float)s16[i] / 32768.0f;
+    return WMI_OK;
+}
+
+int wmi_resample_plan(int32_t sample_rate, int32_t *L, int32_t *M, int32_t *K) {
+    return wmi::resample_plan(sample_rate, L, M, K);
+}
+
+int wmi_resample_taps(int32_t sample_rate, float *h, size_t cap, size_t *n) {
+    int32_t L, M, K;
+    if (int rc = wmi::resample_plan(sample_rate, &L, &M, &K)) return rc;
+    const size_t need = (size_t)L * 2 * (size_t)K;
+    if (n) *n = need;
+    if (!h || cap < need) return WMI_E_NO_SPACE;
+    try {
+        wmi::resample_taps(L, M, K, h, (size_t)2 * K);
+    } catch (...) {
+        return WMI_E_UNEXPECTED;
+    }
+    return WMI_OK;
+}
+
+int wmi_resampled_length(int32_t sample_rate, size_t n_frames, size_t *n_out) {
+    int32_t L, M;
+    if (int rc = wmi::resample_plan(sample_rate, &L, &M, nullptr)) return rc;
+    size_t v = 0;
+    if (!wmi::resampled_length(L, M, n_frames, &v)) return WMI_E_INVALID_ARG;
+    if (n_out) *n_out = v;
     return WMI_OK;
 }
 

@@ -92,4 +92,13 @@ struct TokPiece {
 std::vector<TokPiece> split_segment(const std::vector<std::string> &vocab, int32_t eot, const TokParams &p, int64_t T0,
                                     int64_t T1, const wmi_token_data *tok, int n);
 
+// ---- audio of any rate (DESIGN.md "Audio front end"; the header's "audio of
+// any format" states the plan and the taps) --------------------------------
+// L, M, K of a rate, or WMI_E_UNSUPPORTED outside the plan
+int resample_plan(int32_t sample_rate, int32_t *L, int32_t *M, int32_t *K);
+// h[ph][j], L rows of 2K taps, each row `stride` >= 2K floats apart (the rest of a row is left as it is)
+void resample_taps(int32_t L, int32_t M, int32_t K, float *h, size_t stride);
+// N_out of N frames; false if it does not fit a size_t
+bool resampled_length(int32_t L, int32_t M, size_t N, size_t *n_out);
+
 }  // namespace wmi

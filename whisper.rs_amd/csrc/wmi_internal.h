@@ -365,6 +365,20 @@ struct VadArgs {
     long long *t0, *t1;      // the spans after step B, in 10 ms units; moved in place
 };
 hipError_t launch_token_vad(hipStream_t s, const VadArgs &a, int n_segs);
+// ---- audio of any format (wmi_audio.hip; DESIGN.md "Audio front end") ----------
+constexpr int AUDIO_CH_MAX = 8;                 // channels of a clip
+constexpr long long AUDIO_CHUNK_MAX = 1ll << 22;  // frames of raw input on the device at a time (plus halos)
+// n frames of C interleaved samples (s16 != 0: int16, else f32) at raw (16-byte aligned) -> mono f32 at out (16-byte aligned)
+hipError_t launch_audio_mono(hipStream_t s, const void *raw, long long n, int C, int s16, float *out);
+struct FirArgs {
+    const float *x;          // mono frames [x0, x0 + xn) of the clip
+    long long x0, xn, N;     // N: the clip's frames; a frame outside [0, N) or outside x is 0 and never read
+    const float *h;          // taps [L][hs], a row's first 2K entries; hs a multiple of 4, h 16-byte aligned
+    int L, M, K, hs;
+    long long n_lo, n_hi;    // outputs [n_lo, n_hi) of the clip
+    float *y;                // the clip's outputs (y[n])
+};
+hipError_t launch_audio_fir(hipStream_t s, const FirArgs &a);
 struct NoSpeechArgs {        // a beam window's no-speech probability (row 0 of its first generated step)
     const float *logits;     // [V]
     int V, solm, feed_len;

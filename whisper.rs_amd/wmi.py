@@ -69,6 +69,8 @@ EXPORTS = (
     "wmi_set_fallback", "wmi_decode_timestamps_sampled", "wmi_get_window_count", "wmi_get_window_info",
     "wmi_set_decode_rules", "wmi_non_speech_tokens", "wmi_decode_timestamps_ruled", "wmi_set_initial_prompt",
     "wmi_is_non_speech_token", "wmi_set_token_timestamps", "wmi_token_times",
+    "wmi_audio_to_mel_batch", "wmi_stage_audio", "wmi_transcribe_audio", "wmi_transcribe_audio_batch", "wmi_get_pcm",
+    "wmi_get_audio_timing", "wmi_resample_plan", "wmi_resample_taps", "wmi_resampled_length",
     "wmi_pcm_to_mel", "wmi_pcm_to_mel_batch", "wmi_encode", "wmi_decode_greedy", "wmi_decode_logits",
     "wmi_decode_beam", "wmi_full", "wmi_stage_pcm", "wmi_run_staged", "wmi_run_staged_beam", "wmi_get_tokens", "wmi_get_timings", "wmi_sync",
     "wmi_get_mel", "wmi_get_checksums", "wmi_get_encoder_out", "wmi_get_cross_kv", "wmi_bench_kernel", "wmi_decode_alg_bytes",
@@ -127,6 +129,12 @@ class WindowInfo(C.Structure):
     _fields_ = [("seek", C.c_int64), ("n_attempts", C.c_int32), ("temperature", C.c_float),
                 ("avg_logprob", C.c_float), ("entropy", C.c_float), ("no_speech_prob", C.c_float),
                 ("flags", C.c_int32), ("first_segment", C.c_int32), ("n_segments", C.c_int32)]
+
+
+class Audio(C.Structure):
+    """wmi_audio: raw interleaved frames of one clip (sample_type 0 = f32, 1 = s16)."""
+    _fields_ = [("data", C.c_void_p), ("n_frames", C.c_size_t), ("sample_rate", C.c_int32), ("channels", C.c_int32),
+                ("sample_type", C.c_int32)]
 
 
 class Timings(C.Structure):
@@ -190,6 +198,16 @@ def lib():
         if hasattr(L, "wmi_set_token_timestamps"):  # (as above: an older build has no token-level timestamps)
             L.wmi_set_token_timestamps.argtypes = [vp, C.POINTER(TokenTsParams)]
             L.wmi_token_times.argtypes = [vp, vp, sz, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int]
+        if hasattr(L, "wmi_stage_audio"):  # (as above: an older build has no audio front end)
+            L.wmi_audio_to_mel_batch.argtypes = [vp, C.c_int, C.POINTER(Audio)]
+            L.wmi_stage_audio.argtypes = [vp, C.c_int, C.POINTER(Audio)]
+            L.wmi_transcribe_audio.argtypes = [vp, C.POINTER(Audio), C.c_int, C.POINTER(i32)]
+            L.wmi_transcribe_audio_batch.argtypes = [vp, C.c_int, C.POINTER(Audio), C.c_int, vp]
+            L.wmi_get_pcm.argtypes = [vp, C.c_int, vp, sz, C.POINTER(sz)]
+            L.wmi_get_audio_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(i32)]
+            L.wmi_resample_plan.argtypes = [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+            L.wmi_resample_taps.argtypes = [i32, vp, sz, C.POINTER(sz)]
+            L.wmi_resampled_length.argtypes = [i32, sz, C.POINTER(sz)]
         L.wmi_get_window_count.argtypes = [vp, C.c_int, C.POINTER(i32)]
         L.wmi_get_window_info.argtypes = [vp, C.c_int, C.c_int, C.POINTER(WindowInfo)]
         L.wmi_decode_timestamps_batch.argtypes =[vp, vp, C.c_int, C.c_int, vp, vp]
@@ -296,6 +314,50 @@ def pcm16_to_f32(s16) -> np.ndarray:
     out = np.zeros(s16.size, np.float32)
     _raise(lib().wmi_pcm16_to_f32(_ptr(s16), s16.size, _ptr(out)))
     return out
+
+
+def resample_plan(sample_rate: int):
+    """(L, M, K) of the resampler from sample_rate to 16 kHz (wmi_resample_plan:
+    host-only, no device).  Raises Unsupported for a rate outside the plan."""
+    l, m, k = C.c_int32(), C.c_int32(), C.c_int32()
+    _raise(lib().wmi_resample_plan(int(sample_rate), C.byref(l), C.byref(m), C.byref(k)))
+    return l.value, m.value, k.value
+
+
+def resample_taps(sample_rate: int) -> np.ndarray:
+    """The resampler's taps [L][2K] f32 (wmi_resample_taps: host-only, no device)."""
+    l, _, k = resample_plan(sample_rate)
+    h = np.zeros((l, 2 * k), np.float32)
+    n = C.c_size_t()
+    _raise(lib().wmi_resample_taps(int(sample_rate), _ptr(h), h.size, C.byref(n)))
+    return h
+
+
+def resampled_length(sample_rate: int, n_frames: int) -> int:
+    """16 kHz samples that n_frames frames at sample_rate give (wmi_resampled_length)."""
+    n = C.c_size_t()
+    _raise(lib().wmi_resampled_length(int(sample_rate), int(n_frames), C.byref(n)))
+    return n.value
+
+
+def _audio(clips):
+    """The wmi_audio array of clips, each (samples, rate): samples an ndarray
+    [frames] or [frames, channels] of int16 or float32, C-contiguous (or an
+    Audio already filled in); returns (array, the ndarrays kept alive)."""
+    arr = (Audio * max(1, len(clips)))()
+    keep = []
+    for i, clip in enumerate(clips):
+        if isinstance(clip, Audio):
+            arr[i] = clip
+            continue
+        a, rate = clip
+        if not isinstance(a, np.ndarray) or a.dtype not in (np.int16, np.float32) or a.ndim not in (1, 2) \
+                or not a.flags["C_CONTIGUOUS"]:
+            raise InvalidArgument("a clip is a C-contiguous int16 or float32 ndarray [frames] or [frames, channels]", 14)
+        keep.append(a)
+        arr[i] = Audio(a.ctypes.data, a.shape[0], int(rate), 1 if a.ndim == 1 else a.shape[1],
+                       1 if a.dtype == np.int16 else 0)
+    return arr, keep
 
 
 class WhisperContext:
@@ -616,6 +678,52 @@ class WhisperContext:
         ns = (C.c_size_t * len(clips))(*[c.size for c in clips])
         _raise(lib().wmi_pcm_to_mel_batch(self._h, len(clips), ptrs, ns), self._h)
         self.n_clips = len(clips)
+
+    # --- audio of any format (clips: see _audio) -----------------------------
+    def audio_to_mel_batch(self, clips) -> None:
+        """pcm_to_mel_batch() of clips of any rate, channel count and sample
+        type: downmix, conversion and resampling to 16 kHz run on the device."""
+        arr, keep = _audio(clips)
+        _raise(lib().wmi_audio_to_mel_batch(self._h, len(clips), arr), self._h)
+        self.n_clips = len(clips)
+
+    def stage_audio(self, clips) -> None:
+        """stage() of clips of any format."""
+        arr, keep = _audio(clips)
+        _raise(lib().wmi_stage_audio(self._h, len(clips), arr), self._h)
+        self.n_clips = len(clips)
+
+    def transcribe_audio(self, clip, max_tokens: int = 220):
+        """transcribe() of one clip of any format."""
+        arr, keep = _audio([clip])
+        ns = C.c_int32()
+        _raise(lib().wmi_transcribe_audio(self._h, arr, max_tokens, C.byref(ns)), self._h)
+        self.n_clips = 1
+        return self.segments_of(0, ns.value)
+
+    def transcribe_audio_batch(self, clips, max_tokens: int = 220):
+        """transcribe_batch() of clips of any format, each its own."""
+        arr, keep = _audio(clips)
+        nseg = np.zeros(max(1, len(clips)), np.int32)
+        _raise(lib().wmi_transcribe_audio_batch(self._h, len(clips), arr, max_tokens, _ptr(nseg)), self._h)
+        self.n_clips = len(clips)
+        return [self.segments_of(c, int(nseg[c])) for c in range(len(clips))]
+
+    def pcm(self, clip: int = 0) -> np.ndarray:
+        """The 16 kHz mono samples clip holds (wmi_get_pcm)."""
+        n = C.c_size_t()
+        rc = lib().wmi_get_pcm(self._h, clip, None, 0, C.byref(n))
+        if rc not in (WMI_OK, 3):
+            _raise(rc, self._h)
+        out = np.zeros(n.value, np.float32)
+        _raise(lib().wmi_get_pcm(self._h, clip, _ptr(out), out.size, C.byref(n)), self._h)
+        return out
+
+    def audio_timing(self) -> dict:
+        """Device time of the conversion in the last audio call and the clips it ran a kernel for."""
+        ms, n = C.c_float(), C.c_int32()
+        _raise(lib().wmi_get_audio_timing(self._h, C.byref(ms), C.byref(n)), self._h)
+        return {"convert_ms": ms.value, "n_converted": n.value}
 
     def encode(self, n_threads: int = 1, mel_offset: int = 0) -> None:
         _raise(lib().wmi_encode(self._h, n_threads, mel_offset), self._h)
