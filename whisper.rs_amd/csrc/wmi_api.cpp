@@ -268,6 +268,11 @@ struct wmi_context {
     // workgroups, their operands requested a phase early (PersistArgs::early_ops;
     // WMI_EARLY_OPERANDS=0: tasks from workgroup 0, operands requested in phase E)
     int early_ops = 1;
+    // one-row greedy launches (n <= PX_AOB_NMAX): the Wqkv rows of phase A on the
+    // workgroups past the H self-attention ones, which then enter phase B
+    // straight from the previous layer (PersistArgs::a_off_b; WMI_A_OFF_B=0:
+    // the rows over all workgroups)
+    int a_off_b = 1;
     // greedy blocks of at least split_rows clips decode as two concurrent
     // half-grid launches (rows [0, B/2) and [B/2, B), each on half the CUs, a
     // second stream): a workgroup's all-to-all gathers carry half the rows
@@ -1645,6 +1650,7 @@ PersistArgs persist_args(wmi_context *ctx, const DecRun &run, int G) {
     a.nres = ctx->persist_nres[B];
     a.vreg = ctx->persist_vreg ? 1 : 0;
     a.early_ops = ctx->early_ops;
+    a.a_off_b = ctx->a_off_b;
     a.stall_wg = -1;
     if (ctx->fault_inject == 1) {  // once per context: its first persistent launch
         a.stall_wg = G - 1;
@@ -2977,6 +2983,7 @@ static int wmi_init_from_file_impl(const char *path, int device, int max_clips, 
     if (const char *c = getenv("WMI_FAULT_INJECT")) ctx->fault_inject = atoi(c) ? 1 : 0;
     if (const char *c = getenv("WMI_XSHARE")) ctx->use_xshare = atoi(c) != 0;
     if (const char *c = getenv("WMI_EARLY_OPERANDS")) ctx->early_ops = atoi(c) != 0;
+    if (const char *c = getenv("WMI_A_OFF_B")) ctx->a_off_b = atoi(c) != 0;
     if (const char *c = getenv("WMI_SPLIT_ROWS")) ctx->split_rows = atoi(c);
     if (const char *c = getenv("WMI_AUDIO_CHUNK")) ctx->au_chunk = std::max(1ll, std::min(atoll(c), AUDIO_CHUNK_MAX));
     ctx->dec_layers = ctx->hp.n_text_layer;

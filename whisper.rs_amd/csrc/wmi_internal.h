@@ -545,7 +545,69 @@ struct PersistArgs {
     // their K / V rows, Wcq rows and LNc parameters in phase C, ahead of C's
     // poll (0: tasks on workgroups 0 .., operands requested in phase E)
     int early_ops;
+    // WMI_A_OFF_B (one-row greedy instances of n <= PX_AOB_NMAX): phase A's Wqkv
+    // rows lie on the workgroups from H on (px_a_off_b), and a workgroup that
+    // owns none skips phase A: the H self-attention workgroups enter phase B
+    // straight from the previous layer's phase I (0: the rows over all workgroups)
+    int a_off_b;
 };
+// rows per workgroup of an N-row GEMV over G workgroups, even (f16-pair outputs)
+__host__ __device__ constexpr int px_rows_even(int N, int G) { return (((N + G - 1) / G) + 1) & ~1; }
+// the largest divisor of kch with rows * ks <= 16 (one pass of 16 quarters)
+__host__ __device__ constexpr int split_of(int kch, int rows) {
+    int best = 1;
+    for (int k = 1; k <= kch; ++k)
+        if (kch % k == 0 && rows * k <= 16) best = k;
+    return best;
+}
+// One-row phase-A placement: the 3n Wqkv rows over the G - H workgroups from
+// H on, px_rows_even(3n, G - H) each, so that the H self-attention workgroups
+// own none.  Taken only where a row's sum stays bitwise what it was and the
+// GEMV takes no more passes: the split-K factor the kernel is compiled with
+// (split_of at the design grid GD's rows) still fits the rows in its one
+// pass, or, without split-K, the rows need no more 16-row passes than the
+// partition over all G workgroups.  Else (a small grid, n = 1280, knob off)
+// that partition stays.
+__host__ __device__ constexpr bool px_a_off_b(bool on, int n, int H, int G, int GD) {
+    if (!on || G <= H) return false;
+    const int N = 3 * n, old = px_rows_even(N, G), rpw = px_rows_even(N, G - H);
+    const int ks = split_of(n / 128, px_rows_even(N, GD));
+    return ks > 1 ? rpw * ks <= 16 : split_of(n / 128, rpw) == 1 && (rpw + 15) / 16 <= (old + 15) / 16;
+}
+__host__ __device__ constexpr int px_a_rpw(bool off_b, int n, int H, int G) {
+    return px_rows_even(3 * n, off_b ? G - H : G);
+}
+// workgroup wg's first Wqkv row (3n: it owns none)
+__host__ __device__ constexpr int px_a_row0(bool off_b, int wg, int n, int H, int G) {
+    const int s = off_b ? wg - H : wg, r = s * px_a_rpw(off_b, n, H, G);
+    return s >= 0 && r < 3 * n ? r : 3 * n;
+}
+// every row of [0, 3n) owned exactly once (the workgroups' ranges follow one
+// another), even starts, and with the placement taken none below workgroup H
+constexpr bool px_a_rows_once(bool want, int n, int G, int GD) {
+    const int H = n / 64, N = 3 * n;
+    const bool ob = px_a_off_b(true, n, H, G, GD);
+    if (ob != want) return false;
+    int next = 0;
+    for (int wg = 0; wg < G; ++wg) {
+        const int r0 = px_a_row0(ob, wg, n, H, G), r1 = r0 + px_a_rpw(ob, n, H, G) < N ? r0 + px_a_rpw(ob, n, H, G) : N;
+        if (r0 == N) continue;
+        if ((ob && wg < H) || r0 != next || (r0 & 1) || r1 <= r0) return false;
+        next = r1;
+    }
+    return next == N;
+}
+static_assert(px_a_rows_once(true, 128, 256, 256) && px_a_rows_once(true, 384, 256, 256) && px_a_rows_once(true, 512, 256, 256) &&
+                  px_a_rows_once(true, 768, 256, 256) && px_a_rows_once(true, 1024, 256, 256),
+              "Wqkv rows off the self-attention workgroups");
+static_assert(px_a_rpw(true, 128, 2, 256) == 2 && px_a_rpw(true, 384, 6, 256) == 6 && px_a_rpw(true, 512, 8, 256) == 8 &&
+                  px_a_rpw(true, 768, 12, 256) == 10 && px_a_rpw(true, 1024, 16, 256) == 14,
+              "rows per workgroup of the placement");
+static_assert(px_a_rows_once(false, 1280, 256, 256) && px_a_rows_once(false, 512, 192, 192) && px_a_rows_once(false, 512, 64, 256) &&
+                  !px_a_off_b(false, 512, 8, 256, 256),
+              "the partition over all workgroups where the rows would not fit, or the knob is off");
+// the one-row instances that carry the placement (n = 1280 never takes it)
+constexpr int PX_AOB_NMAX = 1024;
 // One-row cross-attention task placement: workgroup wg runs tasks first,
 // first + G, ... below ntask.  early (and room for it: H + ntask <= G): task t
 // on workgroup H + t, off the H workgroups whose self-attention task (phase B)

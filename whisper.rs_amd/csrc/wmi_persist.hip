@@ -425,14 +425,8 @@ struct WSplit {
 constexpr int PX_GDESIGN = WMI_GDESIGN;
 static_assert(PX_GDESIGN >= 32 && PX_GDESIGN <= PX_GMAX, "design grid");
 // rows per workgroup of an N-row GEMV at the design grid, even
-__host__ __device__ constexpr int rows_full(int N) { return (((N + PX_GDESIGN - 1) / PX_GDESIGN) + 1) & ~1; }
-// the largest divisor of kch with rows * ks <= 16 (one pass of 16 quarters)
-__host__ __device__ constexpr int split_of(int kch, int rows) {
-    int best = 1;
-    for (int k = 1; k <= kch; ++k)
-        if (kch % k == 0 && rows * k <= 16) best = k;
-    return best;
-}
+// (split_of, wmi_internal.h: the largest divisor of kch with rows * ks <= 16)
+__host__ __device__ constexpr int rows_full(int N) { return px_rows_even(N, PX_GDESIGN); }
 
 template <int KCH, int KS, bool Q5>
 __device__ __forceinline__ void wsplit_pre(WSplit<KCH, KS, Q5> &S, int l16) {
@@ -1042,7 +1036,17 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
     };
     int rn0, rn1, ra0, ra1, rh0, rh1, rv0, rv1;
     part(NS, true, rn0, rn1);      // Wo / Wcq / Wco / W1 rows = this WG's residual rows
-    part(3 * NS, true, ra0, ra1);  // Wqkv rows
+    // Wqkv rows: one row (greedy), off the H self-attention workgroups where
+    // they fit on the others (px_a_off_b, PersistArgs::a_off_b); a workgroup
+    // that owns none then has no phase A
+    constexpr bool AOB = BT == 1 && !BEAM && NS <= PX_AOB_NMAX;
+    const bool aob = AOB && px_a_off_b(a.a_off_b != 0, NS, H, G, PX_GDESIGN);
+    if constexpr (AOB) {
+        ra0 = px_a_row0(aob, wg, NS, H, G);
+        ra1 = ra0 + px_a_rpw(aob, NS, H, G) < 3 * NS ? ra0 + px_a_rpw(aob, NS, H, G) : 3 * NS;
+    } else {
+        part(3 * NS, true, ra0, ra1);
+    }
     part(4 * NS, true, rh0, rh1);  // W0 rows
     // the GEMV phases' partial sums: LDS scratch for the MFMA GEMVs, else the split-K buffer
     float *kpbuf = BT > 1 ? (float *)scr : sh.kpart;  // (an MSet phase's partials; sh.kpart for GSet's split-K)
@@ -1145,6 +1149,39 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
             uint16_t *vc = a.vcache + (size_t)l * DEC_ROWS * tctx * NS;
 
             // ---- A: LN1 + QKV rows ------------------------------------
+            if (AOB && aob && ra0 >= ra1) {  // workgroup-uniform
+                // No Wqkv row here (px_a_off_b: the H self-attention workgroups
+                // and those past the last row): no weight request, barrier,
+                // poll of x, LayerNorm or dot.  A self-attention workgroup goes
+                // from the previous layer's I straight into B, whose cache rows
+                // land while the others run A and whose poll of q / k / v then
+                // has nothing queued in front of it (vmcnt retires in order).
+                // What A left behind is not missed: sh.xres already holds this
+                // workgroup's residual rows (phase I's epilogue stored the very
+                // words it put into the x granules), and xf and xs are read
+                // again only behind a poll that refills them (xs: C's poll of o;
+                // xf: poll_ln1 of x' in D or E, of x'' in H, of x in the logits).
+                // Layer 0 keeps what yields the token, and takes the residual
+                // rows from the embeddings with A's expression.
+                if (l == 0) {
+                    PHASE_IDS
+                    __syncthreads();
+                    if (pos < a.feed_len) {
+                        if (tid < B) sh.tok[tid] = a.feed[tid * a.feed_stride + pos];
+                        __syncthreads();
+                    } else if (step == 0) {
+                        if (tid < B) sh.tok[tid] = a.cur_tok[tid];
+                        __syncthreads();
+                    } else {
+                        if (!argmax_gather(pos - 1)) return;
+                        if (wg == 0 && tid < B && pos - a.feed_len < a.out_stride)
+                            a.tokens_out[tid * a.out_stride + (pos - a.feed_len)] = sh.tok[tid];
+                    }
+                    for (int r = tid; r < rn; r += PT)
+                        sh.xres[0][r] = (float)((const f16 *)a.te)[(int64_t)sh.tok[0] * NS + rn0 + r] +
+                                        a.pe[(int64_t)pos * NS + rn0 + r];
+                }
+            } else
             {
                 PHASE_IDS
                 const uint32_t tag = ptag(pos, L, l, 0);
@@ -1233,7 +1270,20 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
                         // wave (its s_waitcnt vmcnt(0) on gfx9 also drains the
                         // store), so the row is in L2/memory before any granule
                         // that transitively signals it (documented,
-                        // no fence — an agent release costs ~1.7 us per phase)
+                        // no fence — an agent release costs ~1.7 us per phase).
+                        // With the rows off the self-attention workgroups
+                        // (aob) those issue B's loads of rows j < pos + 1 ahead
+                        // of the q/k/v poll: right behind phase I of layer
+                        // l - 1 (layer 0: behind the token) of step pos + 1.
+                        // The chain still holds, at the step boundary: every
+                        // wave here passes C's poll of o in this layer (the
+                        // store drained) before the workgroup writes any later
+                        // granule, its x of I(L - 1) of this step among them;
+                        // the loading workgroup has passed the logits' poll
+                        // of that x, all of it, before it begins step pos + 1
+                        // — and a launch's first step follows the previous
+                        // launch's end.  Row pos itself is never loaded early:
+                        // it comes from the granules
                         if (which > 0)
                             st32((uint32_t *)((which == 1 ? kc : vc) + ((int64_t)b * tctx + pos) * NS + c), pk);
                         gput(xg + gi, tag, pk);
