@@ -474,6 +474,86 @@ int wmi_set_token_timestamps(wmi_context *ctx, const wmi_token_ts_params *params
 int wmi_token_times(wmi_context *ctx, const float *pcm, size_t n_samples, int64_t seek, int64_t t0, int64_t t1,
                     wmi_token_data *tokens, int n);
 
+/* ---- token times from cross-attention alignment (DTW) --------------------- */
+
+/* What OpenAI's word_timestamps (find_alignment) and whisper.cpp's
+ * dtw_token_timestamps do: the text tokens of a finished window are
+ * teacher-forced through the decoder once more, the cross-attention of
+ * selected heads is turned into a cost matrix and dynamic time warping finds
+ * each token's first audio frame.  Inputs: an encoded clip of T encoder
+ * frames, a prompt P of p >= 1 ids, text ids x_0 .. x_{n-1} (n >= 1, p + n <=
+ * n_text_ctx), M frames of real audio (1 <= M <= T), A selected (layer, head)
+ * pairs (1 <= A <= 32) in the caller's order, an odd median width w in
+ * [1, 15], h = w / 2.
+ *   S1  Scores.  F = P ++ x is fed at positions 0 .. p+n-1; s[a][i][j], j < T,
+ *       is the f32 the cross-attention softmax of layer l_a, head h_a takes as
+ *       its input for key j at position i (all scaling applied), bit for bit.
+ *   S2  w32[a][i][j] = (float)(exp((double)s - m) / Z) for j < M, m the maximum
+ *       and Z the double sum over j < M.
+ *   S3  Per (a, j), over all i in [0, p+n), in double: mu = mean(w32), sd =
+ *       sqrt(mean((w32 - mu)^2)); z32 = (float)((w32 - mu) / sd), 0 where sd = 0.
+ *   S4  Median along j, width w, reflect padding without edge repeat (-k -> k,
+ *       M-1+k -> M-1-k): the h-th order statistic of the w values.  Applied
+ *       only if M > h, else z32 stays.
+ *   S5  Rows r = 0 .. n, row r = position p-1+r (it predicts x_r; row n what
+ *       follows the text): c = -(1/A) * the sum over a = 0 .. A-1, in that
+ *       order, in double, of the filtered value; Cq[r][j] = (int32) rint(c *
+ *       65536), clamped to +-2^30.
+ *   S6  DTW in int64, exact.  R = n+1 rows, M columns; D[0][0] = 0, the rest of
+ *       row 0 and column 0 +inf.  For i = 1..R, j = 1..M: c0 = D[i-1][j-1], c1 =
+ *       D[i-1][j], c2 = D[i][j-1]; t = 0 if c0 <= c1 and c0 <= c2, else 1 if
+ *       c1 <= c2, else 2; D[i][j] = Cq[i-1][j-1] + c_t.  Backtrace from (R, M):
+ *       0 -> (i-1, j-1), 1 -> (i-1, j), 2 -> (i, j-1), until (0, 0).  f[r] = the
+ *       smallest column of the path in row r (0-based).  A true minimum with
+ *       this tie order; OpenAI's dtw_cpu takes branch 2 on a c0 == c1 tie even
+ *       when c2 is larger, and that quirk is not restated here.
+ *   S7  Times in 10 ms units, W the window's start in mel frames: token x_k
+ *       gets t0 = W + 2 f[k], t1 = W + 2 f[k+1].
+ * Summation orders in S2, S3 are the kernels' own (a last-bit matter of the
+ * float front end); from Cq on every step is integer and exact.
+ *
+ * wmi_set_dtw: the head table is `heads` (n_heads (layer, head) pairs,
+ * copied), or with n_heads = 0 and n_top > 0 every head of the last n_top
+ * text layers in (layer, head) order (whisper.cpp's N_TOP_MOST); preset lists
+ * per released model are the caller's to pass.  enable != 0: every later
+ * wmi_transcribe / wmi_transcribe_audio and their _batch forms aligns each
+ * window's accepted result after it is committed, whatever beam size, fallback
+ * attempt, rules or prompt produced it: x = the window's text tokens (id < eot)
+ * over all its segments in order (none: no pass), P = [sot (, language, task)]
+ * ++ [not] (no <|prev|>, no earlier text, no initial prompt), M = max(1,
+ * (min(n_len - seek, 2T) + 1) / 2); one pass of p + n decoder steps on the
+ * kernel chain and one synchronisation a window.  enable 0 (default, also
+ * params = NULL: {0, 0, NULL, 0, 7}): every call runs exactly the kernels and
+ * code objects it ran before.  WMI_E_INVALID_ARG: a pair outside the model, a
+ * duplicate pair, more than 32 pairs (also through n_top), n_top above the
+ * text layers, an even width or one outside [1, 15], enable with an empty
+ * table.  Holds until changed. */
+typedef struct wmi_dtw_params {
+    int32_t enable;          /* 0 (default, also params = NULL) */
+    int32_t n_top;           /* used when n_heads == 0: every head of the last n_top text layers */
+    const int32_t *heads;    /* n_heads (layer, head) pairs, copied */
+    int32_t n_heads;
+    int32_t medfilt_width;   /* odd, 1..15; OpenAI: 7 */
+} wmi_dtw_params;
+typedef struct wmi_dtw_time { int64_t t0, t1; } wmi_dtw_time;
+int wmi_set_dtw(wmi_context *ctx, const wmi_dtw_params *params);
+/* S1 - S6 for encoded clip `clip` under the table and width set (enabled or
+ * not; an empty table: WMI_E_INVALID_ARG): frames[r] = f[r], r = 0 .. n_text.
+ * WMI_E_INVALID_ARG: n_prompt or n_text < 1, n_prompt + n_text > n_text_ctx,
+ * n_frames outside [1, T], an id outside the vocabulary, no encode yet.  The
+ * pass overwrites the decoder's self-attention cache and step state. */
+int wmi_align_tokens(wmi_context *ctx, int clip, const int32_t *prompt, int n_prompt, const int32_t *text, int n_text,
+                     int n_frames, int32_t *frames /* [n_text + 1] */);
+/* S6 alone, on the device and on the host (no context, no device): first[r] =
+ * f[r].  rows or cols < 1, rows > 513 or cols > 1500: WMI_E_INVALID_ARG. */
+int wmi_dtw_path(wmi_context *ctx, const int32_t *cost, int rows, int cols, int32_t *first /* [rows] */);
+int wmi_dtw_path_host(const int32_t *cost, int rows, int cols, int32_t *first);
+/* One entry per token of segment i of recording clip, parallel to
+ * wmi_get_segment_tokens_of (pieces under max_len carry their tokens' times):
+ * S7 for a text token, -1 / -1 for any other token and for every token while
+ * the feature is off.  *n = the count; WMI_E_NO_SPACE if cap is below it. */
+int wmi_get_segment_dtw_of(const wmi_context *ctx, int clip, int i, wmi_dtw_time *out, size_t cap, int32_t *n);
+
 /* ---- audio of any format: downmix, conversion, resampling on the device --- */
 
 /* A clip is N = n_frames frames of C = channels interleaved samples at R =
@@ -625,7 +705,12 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * wmi_transcribe_batch, then the recording [8] and the mel offset [8] of each
  * slot (int32 [17], host copy; 0 slots before the first round), 23 / 24 =
  * clip 0's energy envelope E (uint32 [N]) / its running sum P (uint64 [N + 1])
- * of the token-level timestamps (WMI_E_INVALID_ARG before one was computed). */
+ * of the token-level timestamps (WMI_E_INVALID_ARG before one was computed),
+ * 25 / 26 / 27 = the last aligned pass's scores s (f32 [A][p + n][T]) / its
+ * cost matrix Cq (int32 [n + 1][M]) / its path f (int32 [n + 1])
+ * (WMI_E_INVALID_ARG before a pass), 28 = with WMI_ALIGN_TIMING=1 the summed
+ * hipEvent ms of the passes' decoder steps, matrix kernels and DTW, and the
+ * passes counted (double [4], host). */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

@@ -173,7 +173,25 @@ struct wmi_context {
         std::vector<Segment> segments;  // result_all (main.rs:353)
         std::vector<TsRec> tokens;      // their tokens, in order
         std::vector<TokTime> times;     // and, under wmi_set_token_timestamps, each token's t0 / t1 / vlen (else empty)
+        std::vector<wmi_dtw_time> dtw;  // and, under wmi_set_dtw, each token's aligned t0 / t1 (else empty)
     };
+    // token times from cross-attention alignment (wmi_set_dtw; wmi_align.hip).  The buffers come with the
+    // first pass: al_s holds s [A][p + n][T] and behind it w [A][p + n][M] (al_cap floats each), al_small
+    // the pass's position count (int32, k_align_capture reads it) and f [AL_ROWS_MAX] behind it
+    bool al_on = false;
+    int al_width = 7;
+    std::vector<int32_t> al_heads;      // (layer, head) pairs in the caller's order
+    float *al_s = nullptr;
+    size_t al_cap = 0;
+    int32_t *al_cq = nullptr;
+    size_t al_cq_cap = 0;
+    uint8_t *al_trace = nullptr;
+    size_t al_trace_cap = 0;
+    int32_t *al_small = nullptr;
+    int32_t al_np_host = 0;             // the word uploaded to al_small[0]
+    int al_last[5] = {0, 0, 0, 0, 0};   // A, p + n, T, n, M of the last pass (debug reads 25 - 27)
+    hipEvent_t al_ev[4] = {};           // WMI_ALIGN_TIMING=1: around a pass's steps, matrix kernels and DTW
+    double al_ms[4] = {0, 0, 0, 0};     // their summed ms and the passes counted (debug read 28)
     // per recording of the last transcribe (one) / transcribe_batch
     std::vector<SegList> results = std::vector<SegList>(1);
     std::vector<int32_t> ts_prompt;     // prompt rows of the last timestamp window, [rows][np] (debug read 19)
@@ -1223,6 +1241,10 @@ struct DecRun {
     int sampled = 0;              // RUN_TS: the temperature sampler (k_ts_sample_t) with the rows' T and keys in d_samp_rows
     int ruled = 0;                // RUN_TS with sampled: that sampler under the decoding rules (k_ts_sample_r)
     int nosp = 0;                 // RUN_BEAM with ts_beam: the first generated step also yields the no-speech probability
+    // RUN_FORCED with B = 1, b0 = the clip's slot: an aligned pass (wmi_set_dtw).  It runs on the kernel chain
+    // whatever use_persist is (run_grid), and every selected layer's cross-attention launch is followed by
+    // k_align_capture
+    int align = 0;
 };
 
 // beam-step kernel arguments of a beam run
@@ -1383,6 +1405,19 @@ int enqueue_dec_step(wmi_context *ctx, const DecRun &run) {
             cur ^= 1;
         }
         HIPCHK(ctx, launch_dec_attn(s, at));
+        if (run.align) {  // (dS is the next layer's self-attention scratch: the copy sits directly behind the launch)
+            AlCapArgs ca{};
+            ca.S = ctx->dS; ca.s_stride = ctx->s_stride; ca.T = T; ca.st = ctx->dstate; ca.np = ctx->al_small;
+            ca.s = ctx->al_s;
+            const size_t A = ctx->al_heads.size() / 2;
+            ca.np_max = (int)std::min<size_t>(ctx->al_cap / (A * (size_t)T), (size_t)hp.n_text_ctx);
+            for (size_t k = 0; k < A; ++k)
+                if (ctx->al_heads[2 * k] == l) {
+                    ca.head[ca.n] = (int16_t)ctx->al_heads[2 * k + 1];
+                    ca.slot[ca.n++] = (int16_t)k;
+                }
+            if (ca.n) HIPCHK(ctx, launch_align_capture(s, ca));
+        }
         g = DecGemvArgs{};
         g.parts = ctx->dopart; g.n_parts = c_cross; g.W = d.wco; g.bias = d.bco; g.N = n; g.K = n; g.B = B;
         g.Wq5 = q5 ? d.wco5 : nullptr;
@@ -1496,10 +1531,11 @@ int run_dec_steps(wmi_context *ctx, const DecRun &run0, int pos0, int steps) {
             if (reps < 1 || (reps > 1 && n < reps)) continue;
             char key[192];
             // (a forced step enqueues what a greedy step does: they share graphs)
-            snprintf(key, sizeof key, "%d/%d/%d/%d/%d/%d/%d/%d/%p/%p/%d/%d/%d/%d/%d", run.b0, run.B, run.feed_len,
+            // (... but an aligned one also captures scores: a field of its own)
+            snprintf(key, sizeof key, "%d/%d/%d/%d/%d/%d/%d/%d/%p/%p/%d/%d/%d/%d/%d/%d", run.b0, run.B, run.feed_len,
                      run.feed_stride, run.suppress_eot, run.out_stride, ctx->enc_T, ctx->enc_clips, (void *)ctx->dfeed,
                      (void *)ctx->dtokens, run.K, run.max_tokens, mk,
-                     run.kind == RUN_TS ? (run.ruled ? 5 : run.sampled ? 3 : 1) : run.ts_beam ? (run.nosp ? 4 : 2) : 0, reps);
+                     run.kind == RUN_TS ? (run.ruled ? 5 : run.sampled ? 3 : 1) : run.ts_beam ? (run.nosp ? 4 : 2) : 0, reps, run.align);
             auto it = ctx->graphs.find(key);
             if (it == ctx->graphs.end()) {
                 if (ctx->graphs.size() >= 32) ctx->clear_graphs();
@@ -1725,6 +1761,7 @@ int reset_run(wmi_context *ctx, bool first, int G, int Gh, bool err_cleared, con
 // greedy block of at least split_rows rows the half grids Gh (0: one launch)
 struct RunGrid { int G, Gh; };
 RunGrid run_grid(wmi_context *ctx, const DecRun &run) {
+    if (run.align) return {0, 0};  // (the capture sits in the kernel chain)
     const int G = persist_grid_for(ctx, run.B);
     const bool split = run.kind == RUN_GREEDY && G > 0 && ctx->split_rows > 1 && run.B >= ctx->split_rows;
     return {G, split ? persist_split_grid(ctx->hp.n_text_state, G) : 0};
@@ -2356,6 +2393,112 @@ int tt_energy_of_clips(wmi_context *ctx, int n_clips) {
     return WMI_OK;
 }
 
+// ---- token times from cross-attention alignment (wmi_set_dtw) --------------------
+// the cost matrix, the trace and the small words of a DTW over R x M
+int al_ensure_dtw(wmi_context *ctx, int R, int M) {
+    const size_t cells = (size_t)R * (size_t)M, tb = dtw_trace_bytes(R, M);
+    if (cells > ctx->al_cq_cap) {
+        if (ctx->al_cq) HIPCHK(ctx, hipFree(ctx->al_cq));
+        ctx->al_cq = nullptr; ctx->al_cq_cap = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->al_cq, 2 * cells * 4));
+        ctx->al_cq_cap = 2 * cells;
+    }
+    if (tb > ctx->al_trace_cap) {
+        if (ctx->al_trace) HIPCHK(ctx, hipFree(ctx->al_trace));
+        ctx->al_trace = nullptr; ctx->al_trace_cap = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->al_trace, 2 * tb));
+        ctx->al_trace_cap = 2 * tb;
+    }
+    // (every word is written before it is read: the position count with each pass, f by each k_dtw)
+    if (!ctx->al_small) HIPCHK(ctx, hipMalloc(&ctx->al_small, (size_t)(4 + AL_ROWS_MAX) * 4));
+    return WMI_OK;
+}
+
+// S1 - S6 for the clip in encoder slot `slot`: F = P ++ x (p + n ids) teacher-
+// forced on the kernel chain with the capture behind every selected layer's
+// cross-attention, the matrix kernels, the DTW; frames[0 .. n] = f.  One
+// synchronisation, at the end.  The pass leaves the self-attention cache, the
+// step state and the feed as a forced run of F does.
+int al_pass(wmi_context *ctx, int slot, const std::vector<int32_t> &F, int p, int M, int32_t *frames) {
+    const int A = (int)ctx->al_heads.size() / 2, Np = (int)F.size(), n = Np - p, T = ctx->enc_T, R = n + 1;
+    if (A < 1) return set_err(ctx, WMI_E_INVALID_ARG, "no (layer, head) pairs set (wmi_set_dtw)");
+    if (T > AL_COLS_MAX || R > AL_ROWS_MAX)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "alignment takes at most %d frames and %d text tokens (%d, %d)", AL_COLS_MAX,
+                       AL_ROWS_MAX - 1, T, n);
+    const size_t need = (size_t)A * (size_t)Np * (size_t)T;
+    if (need > ctx->al_cap) {  // (the captured steps hold the buffer's address)
+        if (ctx->al_s) HIPCHK(ctx, hipFree(ctx->al_s));
+        ctx->al_s = nullptr; ctx->al_cap = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->al_s, 2 * need * 2 * 4));
+        ctx->al_cap = 2 * need;
+        ctx->clear_graphs();
+    }
+    int rc = al_ensure_dtw(ctx, R, M);
+    if (rc) return rc;
+    rc = ensure_decode_buffers(ctx, Np, 1);
+    if (rc) return rc;
+    const bool timed = ctx->al_ev[0] != nullptr;
+    DecRun run{RUN_FORCED, slot, 1, Np, Np};
+    run.align = 1;
+    ctx->al_np_host = Np;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->al_small, &ctx->al_np_host, 4, hipMemcpyHostToDevice, ctx->stream));
+    rc = reset_run(ctx, true, 0, 0, false, F.data(), Np);
+    if (rc) return rc;
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->al_ev[0], ctx->stream));
+    rc = run_dec_steps(ctx, run, 0, Np);
+    if (rc) return rc;
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->al_ev[1], ctx->stream));
+    AlMatArgs ma{};
+    ma.s = ctx->al_s; ma.w = ctx->al_s + ctx->al_cap; ma.cq = ctx->al_cq;
+    ma.A = A; ma.Np = Np; ma.T = T; ma.M = M; ma.p = p; ma.n = n; ma.width = ctx->al_width;
+    HIPCHK(ctx, launch_align_cost(ctx->stream, ma));
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->al_ev[2], ctx->stream));
+    HIPCHK(ctx, launch_dtw(ctx->stream, ctx->al_cq, R, M, ctx->al_trace, ctx->al_small + 4));
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->al_ev[3], ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(frames, ctx->al_small + 4, (size_t)R * 4, hipMemcpyDeviceToHost, ctx->stream));
+    rc = finish_run(ctx);
+    if (rc) return rc == RERUN_ON_CHAIN ? set_err(ctx, WMI_E_HIP, "internal: an aligned pass ran off the kernel chain") : rc;
+    const int last[5] = {A, Np, T, n, M};
+    memcpy(ctx->al_last, last, sizeof last);
+    if (timed) {
+        for (int k = 0; k < 3; ++k) {
+            float ms = 0.0f;
+            (void)hipEventElapsedTime(&ms, ctx->al_ev[k], ctx->al_ev[k + 1]);
+            ctx->al_ms[k] += (double)ms;
+        }
+        ctx->al_ms[3] += 1.0;
+    }
+    return WMI_OK;
+}
+
+std::vector<int32_t> ts_init_prompt(const wmi_context *ctx, int lang);
+
+// A committed window's tokens res.tokens[tok_first ..) of the window at frame
+// W, decoded from encoder slot `slot` of a recording of n_len frames: one pass
+// over its text tokens, S7 into res.dtw (any other token -1 / -1).
+int al_window(wmi_context *ctx, int slot, int lang, wmi_context::SegList &res, size_t tok_first, int64_t W, int64_t n_len) {
+    res.dtw.resize(res.tokens.size(), wmi_dtw_time{-1, -1});
+    std::vector<int32_t> F = ts_init_prompt(ctx, lang);
+    F.push_back(ctx->sp.not_);
+    const int p = (int)F.size();
+    std::vector<size_t> at;
+    for (size_t i = tok_first; i < res.tokens.size(); ++i)
+        if (res.tokens[i].id < ctx->sp.eot) {
+            F.push_back(res.tokens[i].id);
+            at.push_back(i);
+        }
+    if (at.empty()) return WMI_OK;
+    if ((int)F.size() > ctx->hp.n_text_ctx)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "a window of %zu text tokens does not fit an aligned pass", at.size());
+    const int T = ctx->enc_T;
+    const int M = (int)std::max<int64_t>(1, (std::min<int64_t>(n_len - W, 2 * (int64_t)T) + 1) / 2);
+    std::vector<int32_t> f(at.size() + 1);
+    int rc = al_pass(ctx, slot, F, p, M, f.data());
+    if (rc) return rc;
+    for (size_t k = 0; k < at.size(); ++k) res.dtw[at[k]] = wmi_dtw_time{W + 2 * (int64_t)f[k], W + 2 * (int64_t)f[k + 1]};
+    return WMI_OK;
+}
+
 // ---- temperature fallback (wmi_set_fallback) ---------------------------------
 // the temperatures of a window's attempts: T_j = temperature + j * inc while <= 1 + 1e-6
 std::vector<float> fb_temperatures(const wmi_fallback_params &fb) {
@@ -2546,15 +2689,21 @@ int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows,
 // silence its segments; a result of T > 0.5 clears the text context.
 // *done: whether the window is done (seek has then moved).  Under
 // wmi_set_token_timestamps a committed window's segments get their token
-// times, and are split, before they are counted (tt_window).
-int tr_settle(wmi_context *ctx, const TrRun &tr, TrRec &rec, TrAttempt a, bool *done) {
+// times, and are split, before they are counted (tt_window).  Under
+// wmi_set_dtw a committed window's text tokens are aligned first (al_window:
+// one more pass over encoder slot `slot`, which still holds the window).
+int tr_settle(wmi_context *ctx, const TrRun &tr, TrRec &rec, int slot, TrAttempt a, bool *done) {
     wmi_context::SegList &res = ctx->results[rec.clip];
     std::vector<int32_t> *past = rec.carry ? &rec.past : nullptr;
-    const size_t seg_first = res.segments.size();
+    const size_t seg_first = res.segments.size(), tok_first = res.tokens.size();
     *done = true;
     if (tr.temps.empty()) {
         const TsWindowClass wc = classify_ts_window(ctx, a.toks, rec.seek, rec.n_len, tr.window);
         const int64_t delta = commit_ts_window(ctx, std::move(a.toks), wc, rec.seek, res, past);
+        if (ctx->al_on) {
+            int rc = al_window(ctx, slot, rec.lang, res, tok_first, rec.seek, rec.n_len);
+            if (rc) return rc;
+        }
         if (ctx->tt_on) {
             int rc = tt_window(ctx, rec.clip, res, seg_first, rec.seek);
             if (rc) return rc;
@@ -2583,6 +2732,10 @@ int tr_settle(wmi_context *ctx, const TrRun &tr, TrRec &rec, TrAttempt a, bool *
         if (a.T > 0.5f) {
             wi.flags |= WIN_RESET;
             rec.past.clear();
+        }
+        if (ctx->al_on) {
+            int rc = al_window(ctx, slot, rec.lang, res, tok_first, rec.seek, rec.n_len);
+            if (rc) return rc;
         }
         if (ctx->tt_on) {
             int rc = tt_window(ctx, rec.clip, res, seg_first, rec.seek);
@@ -2621,7 +2774,7 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
             if (rc) return rc;
             ctx->tr_count[1] += ctx->last_run_steps;
             if (ctx->fb_on) ++ctx->tr_count[2];
-            rc = tr_settle(ctx, tr, rec, std::move(att[0]), &done);
+            rc = tr_settle(ctx, tr, rec, 0, std::move(att[0]), &done);
             if (rc) return rc;
         }
         ++ctx->tr_count[0];
@@ -2684,7 +2837,7 @@ int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
         if (rc) return rc;
         for (int b = 0; b < B; ++b) {
             bool done;
-            rc = tr_settle(ctx, tr, tr.recs[rows[b]], std::move(att[b]), &done);
+            rc = tr_settle(ctx, tr, tr.recs[rows[b]], b, std::move(att[b]), &done);
             if (rc) return rc;
         }
     }
@@ -2996,6 +3149,8 @@ static int wmi_init_from_file_impl(const char *path, int device, int max_clips, 
         HIPCHK(ctx.get(), hipMalloc(&ctx->d_lgall, nb));
         HIPCHK(ctx.get(), hipMemset(ctx->d_lgall, 0, nb));
     }
+    if (const char *c = getenv("WMI_ALIGN_TIMING"); c && atoi(c))
+        for (hipEvent_t &e : ctx->al_ev) HIPCHK(ctx.get(), hipEventCreate(&e));
     if (getenv("WMI_PTRACE")) {
         const size_t nb = (size_t)hp_ptrace_slots(ctx->hp) * 8;
         HIPCHK(ctx.get(), hipMalloc(&ctx->d_ptrace, nb));
@@ -3038,6 +3193,11 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->tt_tsum) (void)hipFree(ctx->tt_tsum);
     if (ctx->tt_pcm) (void)hipFree(ctx->tt_pcm);
     if (ctx->tt_spans) (void)hipFree(ctx->tt_spans);
+    if (ctx->al_s) (void)hipFree(ctx->al_s);
+    if (ctx->al_cq) (void)hipFree(ctx->al_cq);
+    if (ctx->al_trace) (void)hipFree(ctx->al_trace);
+    if (ctx->al_small) (void)hipFree(ctx->al_small);
+    for (hipEvent_t e : ctx->al_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->d_mel) (void)hipFree(ctx->d_mel);
     if (ctx->dfeed) (void)hipFree(ctx->dfeed);
     if (ctx->dtokens) (void)hipFree(ctx->dtokens);
@@ -3466,6 +3626,89 @@ static int wmi_token_times_impl(wmi_context *ctx, const float *pcm, size_t n_sam
 int wmi_token_times(wmi_context *ctx, const float *pcm, size_t n_samples, int64_t seek, int64_t t0, int64_t t1,
                     wmi_token_data *tokens, int n) {
     return guarded(ctx, [&] { return wmi_token_times_impl(ctx, pcm, n_samples, seek, t0, t1, tokens, n); });
+}
+
+int wmi_set_dtw(wmi_context *ctx, const wmi_dtw_params *params) {
+    return guarded(ctx, [&] {
+        if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+        const wmi_dtw_params def{0, 0, nullptr, 0, 7};
+        const wmi_dtw_params p = params ? *params : def;
+        std::vector<int32_t> pairs;
+        std::string err;
+        if (int rc = dtw_head_table(ctx->hp, p, pairs, err)) return set_err(ctx, rc, "%s", err.c_str());
+        if (pairs != ctx->al_heads) {  // (captured aligned steps hold the table)
+            HIPCHK(ctx, hipSetDevice(ctx->device));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            ctx->clear_graphs();
+        }
+        ctx->al_heads = std::move(pairs);
+        ctx->al_width = p.medfilt_width;
+        ctx->al_on = p.enable != 0;
+        return (int)WMI_OK;
+    });
+}
+
+static int wmi_align_tokens_impl(wmi_context *ctx, int clip, const int32_t *prompt, int n_prompt, const int32_t *text, int n_text,
+                                 int n_frames, int32_t *frames) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (!prompt || !text || !frames || n_prompt < 1 || n_text < 1)
+        return set_err(ctx, WMI_E_INVALID_ARG, "null pointer, or %d prompt / %d text ids", n_prompt, n_text);
+    if (ctx->enc_T <= 0) return set_err(ctx, WMI_E_INVALID_ARG, "align before encode");
+    if (clip < 0 || clip >= ctx->enc_clips) return set_err(ctx, WMI_E_INVALID_ARG, "clip %d", clip);
+    if ((int64_t)n_prompt + n_text > ctx->hp.n_text_ctx)
+        return set_err(ctx, WMI_E_INVALID_ARG, "%d + %d ids above n_text_ctx %d", n_prompt, n_text, ctx->hp.n_text_ctx);
+    if (n_frames < 1 || n_frames > ctx->enc_T)
+        return set_err(ctx, WMI_E_INVALID_ARG, "%d frames outside [1, %d]", n_frames, ctx->enc_T);
+    std::vector<int32_t> F(prompt, prompt + n_prompt);
+    F.insert(F.end(), text, text + n_text);
+    for (int32_t id : F)
+        if (id < 0 || id >= ctx->hp.n_vocab) return set_err(ctx, WMI_E_INVALID_ARG, "token id %d", id);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return al_pass(ctx, clip, F, n_prompt, n_frames, frames);
+}
+
+int wmi_align_tokens(wmi_context *ctx, int clip, const int32_t *prompt, int n_prompt, const int32_t *text, int n_text,
+                     int n_frames, int32_t *frames) {
+    return guarded(ctx, [&] { return wmi_align_tokens_impl(ctx, clip, prompt, n_prompt, text, n_text, n_frames, frames); });
+}
+
+static int wmi_dtw_path_impl(wmi_context *ctx, const int32_t *cost, int rows, int cols, int32_t *first) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (!cost || !first || rows < 1 || rows > AL_ROWS_MAX || cols < 1 || cols > AL_COLS_MAX)
+        return set_err(ctx, WMI_E_INVALID_ARG, "null pointer, or %d x %d outside [1, %d] x [1, %d]", rows, cols, AL_ROWS_MAX,
+                       AL_COLS_MAX);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = al_ensure_dtw(ctx, rows, cols);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->al_cq, cost, (size_t)rows * cols * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, launch_dtw(ctx->stream, ctx->al_cq, rows, cols, ctx->al_trace, ctx->al_small + 4));
+    HIPCHK(ctx, hipMemcpyAsync(first, ctx->al_small + 4, (size_t)rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return WMI_OK;
+}
+
+int wmi_dtw_path(wmi_context *ctx, const int32_t *cost, int rows, int cols, int32_t *first) {
+    return guarded(ctx, [&] { return wmi_dtw_path_impl(ctx, cost, rows, cols, first); });
+}
+
+int wmi_get_segment_dtw_of(const wmi_context *ctx, int clip, int i, wmi_dtw_time *out, size_t cap, int32_t *n) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    wmi_context *ec = const_cast<wmi_context *>(ctx);
+    if (clip < 0 || clip >= (int)ctx->results.size())
+        return set_err(ec, WMI_E_INVALID_ARG, "clip %d outside the %d recordings of the last transcribe", clip,
+                       (int)ctx->results.size());
+    if (i < 0 || i >= (int)ctx->results[clip].segments.size() || !n)
+        return set_err(ec, WMI_E_INVALID_ARG, "segment %d outside clip %d's %d segments, or null n", i, clip,
+                       (int)ctx->results[clip].segments.size());
+    const auto &res = ctx->results[clip];
+    const auto &sg = res.segments[i];
+    *n = sg.count;
+    if (!out || cap < (size_t)sg.count) return WMI_E_NO_SPACE;
+    for (int k = 0; k < sg.count; ++k) {
+        const size_t t = (size_t)(sg.first + k);
+        out[k] = t < res.dtw.size() ? res.dtw[t] : wmi_dtw_time{-1, -1};
+    }
+    return WMI_OK;
 }
 
 int wmi_set_fallback(wmi_context *ctx, const wmi_fallback_params *params) {
@@ -4082,6 +4325,18 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
             if (which == 23) { src = ctx->tt_E[0]; have = (size_t)ctx->tt_n[0] * 4; }
             else { src = ctx->tt_P[0]; have = ((size_t)ctx->tt_n[0] + 1) * 8; }
             break;
+        case 25:  // the last aligned pass's scores s, f32 [A][p + n][T]
+        case 26:  // ... its cost matrix Cq, int32 [n + 1][M]
+        case 27:  // ... and its path f, int32 [n + 1]
+            if (!ctx->al_last[0]) return WMI_E_INVALID_ARG;
+            if (which == 25) { src = ctx->al_s; have = (size_t)ctx->al_last[0] * ctx->al_last[1] * ctx->al_last[2] * 4; }
+            else if (which == 26) { src = ctx->al_cq; have = ((size_t)ctx->al_last[3] + 1) * ctx->al_last[4] * 4; }
+            else { src = ctx->al_small + 4; have = ((size_t)ctx->al_last[3] + 1) * 4; }
+            break;
+        case 28: {  // host: WMI_ALIGN_TIMING's summed ms of the passes' steps, matrix kernels and DTW, and the passes, double [4]
+            memcpy(out, ctx->al_ms, std::min(sizeof ctx->al_ms, bytes));
+            return WMI_OK;
+        }
         case 11: {  // host: decodes re-run on the kernel chain after a persistent exchange timeout
             const int32_t v = ctx->n_fallbacks;
             memcpy(out, &v, std::min(sizeof v, bytes));

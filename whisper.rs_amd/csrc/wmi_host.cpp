@@ -660,9 +660,77 @@ bool resampled_length(int32_t L, int32_t M, size_t N, size_t *n_out) {
     return true;
 }
 
+int dtw_head_table(const wmi_hparams &hp, const wmi_dtw_params &p, std::vector<int32_t> &pairs, std::string &err) {
+    char b[160];
+    auto bad = [&](const char *why, long a0, long a1) {
+        snprintf(b, sizeof b, why, a0, a1);
+        err = b;
+        pairs.clear();
+        return (int)WMI_E_INVALID_ARG;
+    };
+    pairs.clear();
+    if (p.medfilt_width < 1 || p.medfilt_width > 15 || !(p.medfilt_width & 1))
+        return bad("median width %ld is not an odd number in [1, %ld]", p.medfilt_width, 15);
+    if (p.n_heads < 0 || p.n_top < 0 || (p.n_heads > 0 && !p.heads)) return bad("n_heads %ld, n_top %ld, or null heads", p.n_heads, p.n_top);
+    if (p.n_heads > 32) return bad("%ld (layer, head) pairs, at most %ld", p.n_heads, 32);
+    if (p.n_heads > 0) {
+        for (int i = 0; i < p.n_heads; ++i) {
+            const int32_t l = p.heads[2 * i], h = p.heads[2 * i + 1];
+            if (l < 0 || l >= hp.n_text_layer || h < 0 || h >= hp.n_text_head) return bad("pair (%ld, %ld) outside the model", l, h);
+            for (int k = 0; k < i; ++k)
+                if (pairs[2 * k] == l && pairs[2 * k + 1] == h) return bad("pair (%ld, %ld) twice", l, h);
+            pairs.push_back(l);
+            pairs.push_back(h);
+        }
+    } else if (p.n_top > 0) {
+        if (p.n_top > hp.n_text_layer) return bad("n_top %ld above the %ld text layers", p.n_top, hp.n_text_layer);
+        if ((int64_t)p.n_top * hp.n_text_head > 32) return bad("n_top %ld selects more than %ld heads", p.n_top, 32);
+        for (int32_t l = hp.n_text_layer - p.n_top; l < hp.n_text_layer; ++l)
+            for (int32_t h = 0; h < hp.n_text_head; ++h) {
+                pairs.push_back(l);
+                pairs.push_back(h);
+            }
+    } else if (p.enable) {
+        return bad("enabled with neither heads nor n_top (%ld, %ld)", 0, 0);
+    }
+    return WMI_OK;
+}
+
 }  // namespace wmi
 
 extern "C" {
+
+// S6 of the header on the host: D row by row in int64, a trace byte a cell
+int wmi_dtw_path_host(const int32_t *cost, int rows, int cols, int32_t *first) {
+    if (!cost || !first || rows < 1 || rows > 513 || cols < 1 || cols > 1500) return WMI_E_INVALID_ARG;
+    try {
+        const int64_t INF = (int64_t)1 << 62;
+        const size_t R = (size_t)rows, M = (size_t)cols;
+        std::vector<uint8_t> trace(R * M);
+        std::vector<int64_t> prev(M + 1, INF), cur(M + 1, INF);
+        prev[0] = 0;
+        for (size_t i = 1; i <= R; ++i) {
+            cur[0] = INF;
+            for (size_t j = 1; j <= M; ++j) {
+                const int64_t c0 = prev[j - 1], c1 = prev[j], c2 = cur[j - 1];
+                const int t = (c0 <= c1 && c0 <= c2) ? 0 : (c1 <= c2 ? 1 : 2);
+                cur[j] = (int64_t)cost[(i - 1) * M + (j - 1)] + (t == 0 ? c0 : t == 1 ? c1 : c2);
+                trace[(i - 1) * M + (j - 1)] = (uint8_t)t;
+            }
+            prev.swap(cur);
+        }
+        int i = rows, j = cols;
+        for (int k = 0; k < rows + cols && i >= 1 && j >= 1; ++k) {
+            first[i - 1] = j - 1;
+            const int t = trace[(size_t)(i - 1) * M + (size_t)(j - 1)];
+            if (t != 2) --i;
+            if (t != 1) --j;
+        }
+    } catch (...) {
+        return WMI_E_UNEXPECTED;
+    }
+    return WMI_OK;
+}
 
 const char *wmi_strerror(int status) {
     switch (status) {

@@ -92,6 +92,13 @@ struct TokPiece {
 std::vector<TokPiece> split_segment(const std::vector<std::string> &vocab, int32_t eot, const TokParams &p, int64_t T0,
                                     int64_t T1, const wmi_token_data *tok, int n);
 
+// ---- token times from cross-attention alignment: the host side (DESIGN.md
+// "Token times from cross-attention alignment") -------------------------------
+// wmi_set_dtw's checks and the head table, (layer, head) pairs in order: from
+// p.heads, or every head of the last p.n_top text layers; WMI_E_INVALID_ARG
+// with the reason in err
+int dtw_head_table(const wmi_hparams &hp, const wmi_dtw_params &p, std::vector<int32_t> &pairs, std::string &err);
+
 // ---- audio of any rate (DESIGN.md "Audio front end"; the header's "audio of
 // any format" states the plan and the taps) --------------------------------
 // L, M, K of a rate, or WMI_E_UNSUPPORTED outside the plan

@@ -365,6 +365,37 @@ struct VadArgs {
     long long *t0, *t1;      // the spans after step B, in 10 ms units; moved in place
 };
 hipError_t launch_token_vad(hipStream_t s, const VadArgs &a, int n_segs);
+// ---- token times from cross-attention alignment (wmi_align.hip; DESIGN.md
+// "Token times from cross-attention alignment"; S1 - S7 in the public header) ----
+constexpr int AL_HEADS_MAX = 32, AL_WIDTH_MAX = 15;
+constexpr int AL_ROWS_MAX = 513, AL_COLS_MAX = 1500;  // rows (text tokens + 1) and columns (frames) of a cost matrix
+constexpr int AL_DTW_WG = 576;                        // k_dtw's workgroup: a thread a row
+// bytes of k_dtw's trace: a byte a cell, diagonal by diagonal, R bytes a diagonal
+constexpr size_t dtw_trace_bytes(int R, int M) { return (size_t)(R + M - 1) * (size_t)R; }
+// S1 behind a layer's cross-attention launch of an aligned step (one decoder
+// row): workgroup g copies head[g]'s T scores to s[slot[g]][pos][0 .. T),
+// s being [A][*np][T]; nothing is written unless pos < *np <= np_max
+struct AlCapArgs {
+    const float *S;          // the launch's scores [H][s_stride]
+    int s_stride, T;
+    const DecState *st;
+    const int32_t *np;       // device: positions of this pass
+    int np_max;              // positions the buffer holds
+    float *s;
+    int n;                   // selected heads of this layer
+    int16_t head[AL_HEADS_MAX], slot[AL_HEADS_MAX];
+};
+hipError_t launch_align_capture(hipStream_t s, const AlCapArgs &a);
+// S2 - S5: s [A][Np][T] -> w [A][Np][M] (softmax, then z-score in place) -> cq [n + 1][M]; three launches
+struct AlMatArgs {
+    const float *s;
+    float *w;
+    int32_t *cq;
+    int A, Np, T, M, p, n, width;
+};
+hipError_t launch_align_cost(hipStream_t s, const AlMatArgs &a);
+// S6: first[r] = the smallest column of the path in row r; trace holds dtw_trace_bytes(R, M)
+hipError_t launch_dtw(hipStream_t s, const int32_t *cq, int R, int M, uint8_t *trace, int32_t *first);
 // ---- audio of any format (wmi_audio.hip; DESIGN.md "Audio front end") ----------
 constexpr int AUDIO_CH_MAX = 8;                 // channels of a clip
 constexpr long long AUDIO_CHUNK_MAX = 1ll << 22;  // frames of raw input on the device at a time (plus halos)

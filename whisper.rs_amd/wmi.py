@@ -69,6 +69,7 @@ EXPORTS = (
     "wmi_set_fallback", "wmi_decode_timestamps_sampled", "wmi_get_window_count", "wmi_get_window_info",
     "wmi_set_decode_rules", "wmi_non_speech_tokens", "wmi_decode_timestamps_ruled", "wmi_set_initial_prompt",
     "wmi_is_non_speech_token", "wmi_set_token_timestamps", "wmi_token_times",
+    "wmi_set_dtw", "wmi_align_tokens", "wmi_dtw_path", "wmi_dtw_path_host", "wmi_get_segment_dtw_of",
     "wmi_audio_to_mel_batch", "wmi_stage_audio", "wmi_transcribe_audio", "wmi_transcribe_audio_batch", "wmi_get_pcm",
     "wmi_get_audio_timing", "wmi_resample_plan", "wmi_resample_taps", "wmi_resampled_length",
     "wmi_pcm_to_mel", "wmi_pcm_to_mel_batch", "wmi_encode", "wmi_decode_greedy", "wmi_decode_logits",
@@ -122,6 +123,17 @@ class TokenTsParams(C.Structure):
     """wmi_token_ts_params."""
     _fields_ = [("enable", C.c_int32), ("thold_pt", C.c_float), ("thold_ptsum", C.c_float), ("max_len", C.c_int32),
                 ("split_on_word", C.c_int32)]
+
+
+class DtwParams(C.Structure):
+    """wmi_dtw_params."""
+    _fields_ = [("enable", C.c_int32), ("n_top", C.c_int32), ("heads", C.c_void_p), ("n_heads", C.c_int32),
+                ("medfilt_width", C.c_int32)]
+
+
+class DtwTime(C.Structure):
+    """wmi_dtw_time."""
+    _fields_ = [("t0", C.c_int64), ("t1", C.c_int64)]
 
 
 class WindowInfo(C.Structure):
@@ -208,6 +220,12 @@ def lib():
             L.wmi_resample_plan.argtypes = [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
             L.wmi_resample_taps.argtypes = [i32, vp, sz, C.POINTER(sz)]
             L.wmi_resampled_length.argtypes = [i32, sz, C.POINTER(sz)]
+        if hasattr(L, "wmi_set_dtw"):  # (as above: an older build has no alignment)
+            L.wmi_set_dtw.argtypes = [vp, C.POINTER(DtwParams)]
+            L.wmi_align_tokens.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp]
+            L.wmi_dtw_path.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+            L.wmi_dtw_path_host.argtypes = [vp, C.c_int, C.c_int, vp]
+            L.wmi_get_segment_dtw_of.argtypes = [vp, C.c_int, C.c_int, vp, sz, C.POINTER(i32)]
         L.wmi_get_window_count.argtypes = [vp, C.c_int, C.POINTER(i32)]
         L.wmi_get_window_info.argtypes = [vp, C.c_int, C.c_int, C.POINTER(WindowInfo)]
         L.wmi_decode_timestamps_batch.argtypes =[vp, vp, C.c_int, C.c_int, vp, vp]
@@ -651,6 +669,60 @@ class WhisperContext:
         _raise(lib().wmi_token_times(self._h, ptr, ns, int(seek), int(t0), int(t1), arr, len(tokens)), self._h)
         return [arr[i].as_dict() for i in range(len(tokens))]
 
+    # --- token times from cross-attention alignment (DTW) ---------------------
+    def set_dtw(self, enable: bool = True, heads=(), n_top: int = 0, medfilt_width: int = 7,
+                default: bool = False) -> None:
+        """Token times from cross-attention alignment for transcribe() /
+        transcribe_batch() (wmi_set_dtw): heads as (layer, head) pairs, or
+        every head of the last n_top text layers; enable=False keeps the table
+        for align_tokens() only; default=True (a NULL parameter block)
+        switches it off and clears the table."""
+        if default:
+            _raise(lib().wmi_set_dtw(self._h, None), self._h)
+            return
+        hd = np.ascontiguousarray(heads, dtype=np.int32).reshape(-1)
+        p = DtwParams(int(bool(enable)), int(n_top), hd.ctypes.data if hd.size else None, hd.size // 2,
+                      int(medfilt_width))
+        _raise(lib().wmi_set_dtw(self._h, C.byref(p)), self._h)
+
+    def align_tokens(self, prompt, text, n_frames: int, clip: int = 0):
+        """The first frame of every text token, and of what follows the text,
+        on encoded clip `clip` (wmi_align_tokens): int32 [len(text) + 1]."""
+        prompt = np.ascontiguousarray(prompt, dtype=np.int32)
+        text = np.ascontiguousarray(text, dtype=np.int32)
+        out = np.full(text.size + 1, -1, np.int32)
+        _raise(lib().wmi_align_tokens(self._h, clip, _ptr(prompt) if prompt.size else None, prompt.size,
+                                      _ptr(text) if text.size else None, text.size, int(n_frames), _ptr(out)), self._h)
+        return out
+
+    def dtw_path(self, cost):
+        """S6 on the device (wmi_dtw_path): cost int32 [rows][cols] -> the
+        smallest column of the path in every row, int32 [rows]."""
+        cost = np.ascontiguousarray(cost, dtype=np.int32)
+        rows, cols = cost.shape
+        out = np.full(max(1, rows), -1, np.int32)
+        _raise(lib().wmi_dtw_path(self._h, _ptr(cost) if cost.size else _ptr(out), rows, cols, _ptr(out)), self._h)
+        return out[:rows]
+
+    def segment_dtw_of(self, clip: int, i: int):
+        """(t0, t1) of every token of segment i of recording `clip`, parallel to
+        its tokens (wmi_get_segment_dtw_of); (-1, -1): no text token, or off."""
+        n = C.c_int32()
+        rc = lib().wmi_get_segment_dtw_of(self._h, clip, i, None, 0, C.byref(n))
+        if rc not in (0, NotEnoughSpace.code):
+            _raise(rc, self._h)
+        out = (DtwTime * max(1, n.value))()
+        _raise(lib().wmi_get_segment_dtw_of(self._h, clip, i, out, n.value, C.byref(n)), self._h)
+        return [(out[k].t0, out[k].t1) for k in range(n.value)]
+
+    def align_debug(self, A: int, n_pos: int, T: int, n: int, M: int):
+        """The last aligned pass's scores s float32 [A][n_pos][T], cost matrix
+        int32 [n + 1][M] and path int32 [n + 1] (debug reads 25, 26, 27)."""
+        s = np.frombuffer(self.debug_read(25, 4 * A * n_pos * T), np.float32).reshape(A, n_pos, T)
+        cq = np.frombuffer(self.debug_read(26, 4 * (n + 1) * M), np.int32).reshape(n + 1, M)
+        f = np.frombuffer(self.debug_read(27, 4 * (n + 1)), np.int32)
+        return s, cq, f
+
     def energy(self, n: int):
         """Clip 0's energy envelope of the token-level timestamps: (E uint32
         [n], P uint64 [n + 1]) of the last recording given, of n samples (debug
@@ -897,3 +969,14 @@ def whisper_pcm_to_mel(ctx: WhisperContext, samples) -> None:
 def whisper_encode(ctx: WhisperContext, n_threads: int, mel_offset: int) -> None:
     """main.rs:1799-2063 (n_threads accepted and ignored, as in the reference)."""
     ctx.encode(n_threads, mel_offset)
+
+
+def dtw_path_host(cost):
+    """S6 on the host, no context (wmi_dtw_path_host)."""
+    cost = np.ascontiguousarray(cost, dtype=np.int32)
+    rows, cols = cost.shape
+    out = np.full(max(1, rows), -1, np.int32)
+    rc = lib().wmi_dtw_path_host(_ptr(cost) if cost.size else _ptr(out), rows, cols, _ptr(out))
+    if rc:
+        _raise(rc, None)
+    return out[:rows]
