@@ -376,8 +376,8 @@ int wmi_get_window_info(const wmi_context *ctx, int clip, int i, wmi_window_info
  * interface (the same kernels).  A suppress id outside [0, eot):
  * WMI_E_INVALID_ARG; the vocabulary conditions of wmi_set_fallback:
  * WMI_E_UNSUPPORTED.  With rules enabled a beam size above 1 is
- * WMI_E_UNSUPPORTED in wmi_transcribe and wmi_decode_timestamps_beam (the
- * mask would have to follow each hypothesis through the parent selection).
+ * WMI_E_UNSUPPORTED in wmi_transcribe and wmi_decode_timestamps_beam unless
+ * the context has opted into the ruled beam window (wmi_set_rules_beam below).
  * Holds until changed. */
 typedef struct wmi_decode_rules {
     int32_t enable;               /* 0 (default, also params = NULL): the sampler as before */
@@ -402,6 +402,39 @@ int wmi_is_non_speech_token(const char *bytes, size_t len);
 int wmi_decode_timestamps_ruled(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens,
                                 float temperature, uint64_t seed, int n, wmi_token_data *out, int32_t *n_out,
                                 float *plog, float *p_nosp);
+/* ---- the decoding rules in the beam window -------------------------------- */
+
+/* wmi_decode_timestamps_beam under the rules set: K = beam_size (1..8)
+ * hypotheses, each active row b with a history s_b, the ids of its own
+ * hypothesis in this window.  A' of the row: the masks M0 - M2 above, M1 from
+ * s_b.  Over A': sum_ts = P(timestamps), p_tx = the largest P of an id below
+ * beg (EOT included; 0 if none); the row's set A = the timestamps of A' if
+ * sum_ts > p_tx, else A'.  The row contributes its top K + 1 ids of A by logit
+ * (ties: lower id; fewer if A holds fewer), each scored score_b + (l_i -
+ * lse_A) in float64.  Ranking, walk, finished list, stop and the final choice
+ * are wmi_decode_timestamps_beam's.  A new slot's history is its parent's
+ * followed by the id it took.  Records as wmi_decode_timestamps_ruled's (tid,
+ * p, pt, ptsum under the softmax over A'), from the row that produced each
+ * token; *score = the chosen hypothesis' summed log-probability under its
+ * rows' sets A.  At beam_size 1 the ids and tids are
+ * wmi_decode_timestamps_ruled's at temperature 0.  score and p_nosp (P(solm)
+ * under the unmasked softmax of the first generated step) may be NULL.  No
+ * rules enabled, or beam_size outside [1, 8]: WMI_E_INVALID_ARG. */
+int wmi_decode_timestamps_ruled_beam(wmi_context *ctx, int beam_size, const int32_t *prompt, int n_prompt,
+                                     int max_tokens, wmi_token_data *out, int32_t *n_out, double *score,
+                                     float *p_nosp);
+/* enable 1: with rules and a beam size above 1, a temperature-0 window of
+ * wmi_transcribe / wmi_transcribe_audio is the ruled beam window, and
+ * wmi_decode_timestamps_beam under rules is wmi_decode_timestamps_ruled_beam.
+ * Under wmi_set_fallback attempt 0 is that window, judged as the beam window
+ * is (its score as the summed log-probability, the no-speech probability of
+ * its first generated step); attempts at T > 0 draw one hypothesis under the
+ * rules, as at beam size 1.  enable 0 (the default): rules with a beam size
+ * above 1 stay WMI_E_UNSUPPORTED, and every call runs the kernels it ran
+ * before this interface.  wmi_transcribe_batch with a beam size stays
+ * WMI_E_UNSUPPORTED either way.  Neither 0 nor 1: WMI_E_INVALID_ARG.  Holds
+ * until changed. */
+int wmi_set_rules_beam(wmi_context *ctx, int enable);
 /* Text ids (below eot, else WMI_E_INVALID_ARG) in front of the text context
  * of wmi_transcribe: window 0 decodes from [prev] + ids + [sot ..], later
  * windows see the tail of ids + text (at most n_text_ctx / 2 ids, of which
@@ -640,7 +673,11 @@ int wmi_sync(wmi_context *ctx);
  * which: 14 = the persistent greedy decoder over the staged clips (one launch
  * per 8-row block, as run_staged makes it; algorithmic bytes summed per step),
  * 0 = the kernel chain's logits GEMV + argmax, 1 = encoder MLP-up GEMM of
- * layer 0 (MFMA), 2 = encoder attention of layer 0, 3 = cross-K/V GEMM. */
+ * layer 0 (MFMA), 2 = encoder attention of layer 0, 3 = cross-K/V GEMM,
+ * 15 / 16 = the beam step under the timestamp rule / under the decoding rules
+ * (both kernels of either; K = wmi_set_beam_size, at generated token 1 over
+ * the logits rows of the last ruled beam window, which must have run with at
+ * least that many hypotheses: WMI_E_INVALID_ARG before one). */
 typedef struct wmi_kernel_bench {
     float avg_us;          /* mean launch duration */
     double alg_bytes;      /* algorithmic HBM bytes per launch */
@@ -696,7 +733,10 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * window), 20 = the windows and the decoder steps of the last wmi_transcribe
  * (int64 [2], host; every attempt's steps under wmi_set_fallback, and a third
  * int64: the attempts).  13 to 15 also hold the last wmi_decode_timestamps_beam
- * window; 13 also the last sampled or ruled window
+ * or ruled beam window (19 its prompt rows), and 29 = the last ruled beam
+ * window's slot histories after every step, int32 [steps][8][3] = {last id was
+ * a timestamp, the one before was, the last timestamp + 1 (0: none)}
+ * (WMI_E_INVALID_ARG before one ran); 13 also the last sampled or ruled window
  * (wmi_decode_timestamps_sampled, wmi_decode_timestamps_ruled, a window of
  * wmi_transcribe under wmi_set_fallback or wmi_set_decode_rules; row b in
  * row b).  21 = the conv-1 input of the last encode, [slots][2 * n_ctx + 2]

@@ -153,6 +153,13 @@ struct wmi_context {
     uint32_t *d_rule_m0 = nullptr;      // [ceil(n_vocab / 32)] bit i: id i is masked always
     RuleHist *d_rule_hist = nullptr;    // [8] the rows' history (same allocation, behind dts_done)
     std::vector<int32_t> init_prompt;   // text ids in front of the first window's context
+    // the rules in the beam window (wmi_set_rules_beam; wmi_rbeam.hip).  One allocation, made with the first
+    // such window: the slots' histories [8], the per-step history table [n_text_ctx][8][3], the parts [8][16]
+    bool rules_beam = false;
+    RuleHist *d_rb_hist = nullptr;
+    int32_t *d_rb_tab = nullptr;
+    RBeamPart *d_rb_parts = nullptr;
+    int rb_steps = 0;                   // steps of the last ruled beam window (0: none has run; debug read 29)
     // token-level timestamps (wmi_set_token_timestamps): per clip the energy envelope E [N] and its running
     // sum P [N + 1] of the last recording uploaded with the feature on (tt_n: its samples, -1: none)
     bool tt_on = false;
@@ -1223,7 +1230,8 @@ int run_encode(wmi_context *ctx, int mel_offset, int slots = 0, const int32_t *s
 //   RUN_GREEDY  rows are consecutive clips; the argmax of a step feeds the next
 //               and is recorded in dtokens ([.][out_stride])
 //   RUN_BEAM    rows are the K hypotheses of clip b0; k_beam_step follows a step,
-//               or with ts_beam the step under the timestamp rule (k_tsbeam_*)
+//               or with ts_beam the step under the timestamp rule (k_tsbeam_*),
+//               with ts_beam and ruled the step under the decoding rules (k_rbeam_*)
 //   RUN_TS      rows are consecutive clips, as greedy; the timestamp sampler
 //               (k_ts_sample) follows a step and picks each row's next token,
 //               or with `sampled` the temperature sampler (k_ts_sample_t)
@@ -1239,7 +1247,8 @@ struct DecRun {
     int mk = 512;                 // key capacity of the self-attention launch being enqueued (run_dec_steps)
     int ts_beam = 0;              // RUN_BEAM: the hypotheses follow the timestamp rule and keep token records
     int sampled = 0;              // RUN_TS: the temperature sampler (k_ts_sample_t) with the rows' T and keys in d_samp_rows
-    int ruled = 0;                // RUN_TS with sampled: that sampler under the decoding rules (k_ts_sample_r)
+    int ruled = 0;                // RUN_TS with sampled: that sampler under the decoding rules (k_ts_sample_r);
+                                  // RUN_BEAM with ts_beam: the beam step under them (k_rbeam_*)
     int nosp = 0;                 // RUN_BEAM with ts_beam: the first generated step also yields the no-speech probability
     // RUN_FORCED with B = 1, b0 = the clip's slot: an aligned pass (wmi_set_dtw).  It runs on the kernel chain
     // whatever use_persist is (run_grid), and every selected layer's cross-attention launch is followed by
@@ -1267,6 +1276,18 @@ TsBeamArgs tsbeam_args(wmi_context *ctx, const DecRun &run) {
     ta.tparts = ctx->d_tsb_parts; ta.hist_rec = ctx->d_tsb_rec;
     ta.fin_rec = ctx->d_tsb_rec + (size_t)ctx->hp.n_text_ctx * BEAM_MAX;
     return ta;
+}
+
+// ... and of one under the decoding rules
+RBeamArgs rbeam_args(wmi_context *ctx, const DecRun &run) {
+    RBeamArgs ra{};
+    ra.b = beam_args(ctx, run);
+    ra.b.parts = nullptr;
+    ra.beg = ctx->sp.beg; ra.max_initial_ts = ctx->max_initial_ts; ra.m0 = ctx->d_rule_m0;
+    ra.hist = ctx->d_rb_hist; ra.rparts = ctx->d_rb_parts; ra.hist_tab = ctx->d_rb_tab;
+    ra.hist_rec = ctx->d_tsb_rec;
+    ra.fin_rec = ctx->d_tsb_rec + (size_t)ctx->hp.n_text_ctx * BEAM_MAX;
+    return ra;
 }
 
 // timestamp-sampler arguments of a timestamp run
@@ -1302,7 +1323,8 @@ int enqueue_step_tail(wmi_context *ctx, const DecRun &run) {
         HIPCHK(ctx, launch_no_speech(ctx->stream, na));
     }
     if (run.kind == RUN_TS) HIPCHK(ctx, launch_ts_sample(ctx->stream, ts_args(ctx, run)));
-    if (run.kind == RUN_BEAM && run.ts_beam) HIPCHK(ctx, launch_tsbeam_step(ctx->stream, tsbeam_args(ctx, run)));
+    if (run.kind == RUN_BEAM && run.ts_beam && run.ruled) HIPCHK(ctx, launch_rbeam_step(ctx->stream, rbeam_args(ctx, run)));
+    else if (run.kind == RUN_BEAM && run.ts_beam) HIPCHK(ctx, launch_tsbeam_step(ctx->stream, tsbeam_args(ctx, run)));
     else if (run.kind == RUN_BEAM) HIPCHK(ctx, launch_beam_step(ctx->stream, beam_args(ctx, run)));
     return WMI_OK;
 }
@@ -1535,7 +1557,8 @@ int run_dec_steps(wmi_context *ctx, const DecRun &run0, int pos0, int steps) {
             snprintf(key, sizeof key, "%d/%d/%d/%d/%d/%d/%d/%d/%p/%p/%d/%d/%d/%d/%d/%d", run.b0, run.B, run.feed_len,
                      run.feed_stride, run.suppress_eot, run.out_stride, ctx->enc_T, ctx->enc_clips, (void *)ctx->dfeed,
                      (void *)ctx->dtokens, run.K, run.max_tokens, mk,
-                     run.kind == RUN_TS ? (run.ruled ? 5 : run.sampled ? 3 : 1) : run.ts_beam ? (run.nosp ? 4 : 2) : 0, reps, run.align);
+                     run.kind == RUN_TS ? (run.ruled ? 5 : run.sampled ? 3 : 1) : run.ts_beam ? (run.ruled ? (run.nosp ? 7 : 6) : run.nosp ? 4 : 2) : 0,
+                     reps, run.align);
             auto it = ctx->graphs.find(key);
             if (it == ctx->graphs.end()) {
                 if (ctx->graphs.size() >= 32) ctx->clear_graphs();
@@ -2552,7 +2575,7 @@ std::vector<int32_t> ts_init_prompt(const wmi_context *ctx, int lang) {
 }
 
 int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, int K, int max_tokens,
-                       std::vector<TsRec> *out, double *score, float *p_nosp = nullptr);
+                       std::vector<TsRec> *out, double *score, float *p_nosp = nullptr, bool ruled = false);
 
 // after attempt 0: probably silence (OpenAI's no_speech_threshold rule)
 bool fb_silence(const wmi_context *ctx, float p_nosp, const FbAttempt &att) {
@@ -2645,10 +2668,12 @@ struct TrAttempt {
 // The recordings `rows` sit in the encoded rows 0..B-1 and row b is fed the np
 // tokens feed[b * np ..): each row's attempt at its recording's temperature.
 // Fallback off: the plain sampler (k_ts_sample), or with a beam size the beam
-// window, neither with quality figures.  Decoding rules on (never with a beam
-// size): k_ts_sample_r in the place of either sampler.  Fallback on: every row through the
+// window, neither with quality figures.  Decoding rules on, no beam size:
+// k_ts_sample_r in the place of either sampler.  Fallback on: every row through the
 // temperature sampler (at T = 0 too) with its own stream key; with a beam
-// size a T = 0 attempt is the beam window with k_no_speech behind it.
+// size a T = 0 attempt is the beam window with k_no_speech behind it.  Rules
+// and a beam size (wmi_set_rules_beam): a T = 0 attempt is the ruled beam
+// window, one at T > 0 goes through k_ts_sample_r as at beam size 1.
 int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows, const std::vector<int32_t> &feed, int np,
                       std::vector<TrAttempt> *out) {
     const int B = (int)rows.size();
@@ -2658,8 +2683,9 @@ int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows,
     if (ctx->beam_size > 1 && (*out)[0].T == 0.0f) {
         if (B != 1) return set_err(ctx, WMI_E_UNSUPPORTED, "a beam window decodes one recording (%d rows)", B);
         TrAttempt &a = (*out)[0];
+        // (rules on: the caller has checked wmi_set_rules_beam, and the window is the ruled beam window)
         return run_ts_beam_window(ctx, 0, feed, ctx->beam_size, tr.n_max, &a.toks, fb ? &a.logprob_sum : nullptr,
-                                  fb ? &a.p_nosp : nullptr);
+                                  fb ? &a.p_nosp : nullptr, ctx->rules_on);
     }
     TsSampled sp;
     for (int b = 0; b < B && fb; ++b) {
@@ -2977,9 +3003,12 @@ int run_beam(wmi_context *ctx, int K, int n_gen, int suppress_eot, bool early_st
 // after `prompt` (every row is fed the same prompt), each step followed by the
 // beam step under the timestamp rule (k_tsbeam_part / k_tsbeam_select).  The
 // hypothesis is chosen as run_beam chooses it; out = its tokens' records, the
-// EOT of a finished one included, *score its summed log-probability.
+// EOT of a finished one included, *score its summed log-probability.  With
+// `ruled` the step is the one under the decoding rules (k_rbeam_part /
+// k_rbeam_select): the slots' histories start empty at every (re)start of the
+// run, and the step keeps their table for debug read 29.
 int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, int K, int max_tokens,
-                       std::vector<TsRec> *out, double *score, float *p_nosp) {
+                       std::vector<TsRec> *out, double *score, float *p_nosp, bool ruled) {
     const wmi_hparams &hp = ctx->hp;
     const int np = (int)prompt.size();
     if (ctx->enc_T <= 0 || ctx->enc_clips < 1) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
@@ -2994,6 +3023,16 @@ int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &p
         HIPCHK(ctx, hipMalloc(&ctx->d_tsb_parts, (size_t)BEAM_MAX * BEAM_NS * sizeof(TsBeamPart)));
         HIPCHK(ctx, hipMalloc(&ctx->d_tsb_rec, n_rec * sizeof(TsRec)));
     }
+    const size_t rb_zero = BEAM_MAX * sizeof(RuleHist) + (size_t)hp.n_text_ctx * BEAM_MAX * 3 * 4;  // histories and table
+    if (ruled && !ctx->d_rb_hist) {
+        if (!ctx->rules_on || !ctx->d_rule_m0) return set_err(ctx, WMI_E_INVALID_ARG, "no decoding rules are enabled");
+        char *p = nullptr;
+        HIPCHK(ctx, hipMalloc(&p, rb_zero + (size_t)BEAM_MAX * BEAM_NS * sizeof(RBeamPart)));
+        ctx->d_rb_hist = (RuleHist *)p;
+        ctx->d_rb_tab = (int32_t *)(p + BEAM_MAX * sizeof(RuleHist));
+        ctx->d_rb_parts = (RBeamPart *)(p + rb_zero);
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_rb_parts, 0, (size_t)BEAM_MAX * BEAM_NS * sizeof(RBeamPart), ctx->stream));
+    }
     // (a window's prompt holds up to n_text_ctx / 2 earlier tokens: K rows of
     // it are more than the 64 words of the reset launch, so reset_run copies them)
     int rc = ensure_decode_buffers(ctx, K * np, 1);
@@ -3004,6 +3043,8 @@ int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &p
     ctx->ts_prompt = feed;
     DecRun run{RUN_BEAM, clip, K, np, np, 0, 1, K, max_tokens};
     run.ts_beam = 1;
+    run.ruled = ruled ? 1 : 0;
+    if (ruled) ctx->rb_steps = 0;
     if (p_nosp) {  // (the fallback's attempt 0: k_no_speech behind the first generated step)
         rc = ensure_samp_buffers(ctx);
         if (rc) return rc;
@@ -3017,6 +3058,8 @@ int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &p
         if (rc) return rc;
         rc = start_beam_run(ctx);
         if (rc) return rc;
+        // (no hypothesis has sampled anything: also where the run starts again on the kernel chain)
+        if (ruled) HIPCHK(ctx, hipMemsetAsync(ctx->d_rb_hist, 0, rb_zero, ctx->stream));
         for (int done = 0; done < total;) {
             // (the prompt in one chunk, then 16 steps between looks at BeamState::done)
             const int chunk = std::min(done < np - 1 ? np - 1 - done + 16 : 16, total - done);
@@ -3037,6 +3080,7 @@ int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &p
     if (rc) return rc;
     const int ns = bs.n_steps;
     if (ns < 1 || ns > max_tokens) return set_err(ctx, WMI_E_HIP, "beam search produced %d steps", ns);
+    if (ruled) ctx->rb_steps = ns;
     std::vector<int32_t> hpar((size_t)ns * BEAM_MAX);
     std::vector<TsRec> hrec((size_t)ns * BEAM_MAX), frec(BEAM_MAX);
     HIPCHK(ctx, hipMemcpy(hpar.data(), ctx->dhist_par, hpar.size() * 4, hipMemcpyDeviceToHost));
@@ -3218,6 +3262,7 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->d_win) (void)hipFree(ctx->d_win);
     if (ctx->d_samp_rows) (void)hipFree(ctx->d_samp_rows);
     if (ctx->d_rule_m0) (void)hipFree(ctx->d_rule_m0);
+    if (ctx->d_rb_hist) (void)hipFree(ctx->d_rb_hist);
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -3387,10 +3432,12 @@ static int wmi_decode_timestamps_sampled_impl(wmi_context *ctx, const int32_t *p
 }
 
 // A history-dependent mask needs per-hypothesis state that follows the beam
-// step's parent selection (the follow-up work); no silent fall-back to the
-// old rule, as for a beam size in wmi_transcribe_batch.
+// step's parent selection: the ruled beam window (wmi_rbeam.hip), which a
+// context takes only after wmi_set_rules_beam(ctx, 1).  Without it the
+// combination is refused as it always was; no silent fall-back to the old
+// rule, as for a beam size in wmi_transcribe_batch.
 static int rules_beam_unsupported(wmi_context *ctx, int beam_size) {
-    if (ctx->rules_on && beam_size > 1)
+    if (ctx->rules_on && beam_size > 1 && !ctx->rules_beam)
         return set_err(ctx, WMI_E_UNSUPPORTED, "the decoding rules are not built into the beam window: beam size %d is set "
                        "(wmi_set_beam_size(ctx, 1), or wmi_set_decode_rules(ctx, NULL))", beam_size);
     return WMI_OK;
@@ -3427,7 +3474,27 @@ static int wmi_decode_timestamps_beam_impl(wmi_context *ctx, int beam_size, cons
     if (rc) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::vector<TsRec> rec;
-    rc = run_ts_beam_window(ctx, 0, std::vector<int32_t>(prompt, prompt + n_prompt), beam_size, max_tokens, &rec, score);
+    // (under wmi_set_rules_beam and rules this is wmi_decode_timestamps_ruled_beam)
+    rc = run_ts_beam_window(ctx, 0, std::vector<int32_t>(prompt, prompt + n_prompt), beam_size, max_tokens, &rec, score,
+                            nullptr, ctx->rules_on && ctx->rules_beam);
+    if (rc) return rc;
+    copy_out_tokens(rec, out, n_out);
+    return WMI_OK;
+}
+
+// wmi_decode_timestamps_beam under the context's decoding rules, whatever wmi_set_rules_beam says
+static int wmi_decode_timestamps_ruled_beam_impl(wmi_context *ctx, int beam_size, const int32_t *prompt, int n_prompt,
+                                                 int max_tokens, wmi_token_data *out, int32_t *n_out, double *score,
+                                                 float *p_nosp) {
+    int rc = check_ts_args(ctx, prompt, n_prompt, max_tokens, out, n_out);
+    if (rc) return rc;
+    if (!ctx->rules_on) return set_err(ctx, WMI_E_INVALID_ARG, "no decoding rules are enabled (wmi_set_decode_rules)");
+    if (beam_size < 1 || beam_size > BEAM_MAX)
+        return set_err(ctx, WMI_E_INVALID_ARG, "beam size %d outside [1, %d]", beam_size, BEAM_MAX);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<TsRec> rec;
+    rc = run_ts_beam_window(ctx, 0, std::vector<int32_t>(prompt, prompt + n_prompt), beam_size, max_tokens, &rec, score,
+                            p_nosp, true);
     if (rc) return rc;
     copy_out_tokens(rec, out, n_out);
     return WMI_OK;
@@ -4161,6 +4228,24 @@ int wmi_bench_kernel(wmi_context *ctx, int which, int iters, wmi_kernel_bench *o
     const int n = hp.n_audio_state, T = ctx->enc_T, B = ctx->enc_clips, M = B * T;
     memset(out, 0, sizeof(*out));
     hipStream_t s = ctx->stream;
+    // 15 / 16: the beam step under the timestamp rule / under the decoding rules (both kernels of either), K =
+    // the context's beam size, over the logits rows the last ruled beam window left, every launch at t = 1 with
+    // K active hypotheses (the select kernel keeps K of them; an EOT among a row's best would finish one, so the
+    // state is read back below and a changed one is an error rather than a wrong figure)
+    DecRun brun{RUN_BEAM, 0, ctx->beam_size, 1, 1, 0, 1, ctx->beam_size, hp.n_text_ctx};
+    if (which == 15 || which == 16) {
+        if (!ctx->rules_on || !ctx->d_rb_hist || !ctx->d_tsb_parts || ctx->rb_steps < 2)
+            return set_err(ctx, WMI_E_INVALID_ARG, "bench_kernel %d needs a ruled beam window first", which);
+        BeamState init{};
+        init.n_active = ctx->beam_size;
+        const DecState st{2, {0, 0, 0}};
+        int rcb = start_beam_run(ctx);
+        if (rcb) return rcb;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->dbstate, &init, sizeof init, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->dstate, &st, sizeof st, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_rb_hist, 0, BEAM_MAX * sizeof(RuleHist), s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+    }
     auto launch = [&]() -> int {
         if (which == 0) {
             DecGemvArgs g{}; g.tune = &ctx->tune;
@@ -4200,6 +4285,10 @@ int wmi_bench_kernel(wmi_context *ctx, int which, int iters, wmi_kernel_bench *o
                 return set_err(ctx, WMI_E_INVALID_ARG, "persistent decoder not in use for this run");
             const int r = run_greedy(ctx, ctx->staged_n_decode, 1, false, nullptr, nullptr);
             if (r) return r;
+        } else if (which == 15) {
+            HIPCHK(ctx, launch_tsbeam_step(s, tsbeam_args(ctx, brun)));
+        } else if (which == 16) {
+            HIPCHK(ctx, launch_rbeam_step(s, rbeam_args(ctx, brun)));
         } else {
             return set_err(ctx, WMI_E_INVALID_ARG, "unknown kernel %d", which);
         }
@@ -4233,6 +4322,15 @@ int wmi_bench_kernel(wmi_context *ctx, int which, int iters, wmi_kernel_bench *o
         out->alg_bytes = 4.0 * (double)M * n * 2;
         const int nw = attn_enc_nw(T, hp.n_audio_head, B, ctx->tune.enc_attn_nw);  // as launch_attn_enc picks it
         snprintf(out->name, sizeof out->name, "k_attn_enc4<%d,%d>", nw, attn_enc_kq(T, hp.n_audio_head));
+    } else if (which == 15 || which == 16) {
+        BeamState bs{};
+        HIPCHK(ctx, hipMemcpy(&bs, ctx->dbstate, sizeof bs, hipMemcpyDeviceToHost));
+        if (bs.done || bs.n_fin || bs.n_active != ctx->beam_size)
+            return set_err(ctx, WMI_E_UNEXPECTED, "bench_kernel %d: the beam state moved (%d active, %d finished)", which,
+                           bs.n_active, bs.n_fin);
+        out->alg_bytes = (double)ctx->beam_size * V * 4;  // (the rows' logits, read once)
+        snprintf(out->name, sizeof out->name, which == 15 ? "k_tsbeam_part + _select (K %d)" : "k_rbeam_part + _select (K %d)",
+                 ctx->beam_size);
     } else if (which == 14) {
         int32_t prompt[8];
         const int np = prompt_tokens(ctx, prompt), steps = np + ctx->staged_n_decode - 1;
@@ -4337,6 +4435,9 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
             memcpy(out, ctx->al_ms, std::min(sizeof ctx->al_ms, bytes));
             return WMI_OK;
         }
+        case 29:  // the last ruled beam window's slot histories after every step, int32 [steps][BEAM_MAX][3] = {last, pen, lts1}
+            if (!ctx->d_rb_tab || ctx->rb_steps < 1) return WMI_E_INVALID_ARG;
+            src = ctx->d_rb_tab; have = (size_t)ctx->rb_steps * BEAM_MAX * 3 * 4; break;
         case 11: {  // host: decodes re-run on the kernel chain after a persistent exchange timeout
             const int32_t v = ctx->n_fallbacks;
             memcpy(out, &v, std::min(sizeof v, bytes));
@@ -4499,6 +4600,20 @@ int wmi_decode_timestamps_ruled(wmi_context *ctx, const int32_t *prompt, int n_p
         return wmi_decode_timestamps_ruled_impl(ctx, prompt, n_prompt, max_tokens, temperature, seed, n, out, n_out, plog,
                                                 p_nosp);
     });
+}
+
+int wmi_decode_timestamps_ruled_beam(wmi_context *ctx, int beam_size, const int32_t *prompt, int n_prompt, int max_tokens,
+                                     wmi_token_data *out, int32_t *n_out, double *score, float *p_nosp) {
+    return guarded(ctx, [&] {
+        return wmi_decode_timestamps_ruled_beam_impl(ctx, beam_size, prompt, n_prompt, max_tokens, out, n_out, score, p_nosp);
+    });
+}
+
+int wmi_set_rules_beam(wmi_context *ctx, int enable) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    if (enable != 0 && enable != 1) return set_err(ctx, WMI_E_INVALID_ARG, "enable %d is neither 0 nor 1", enable);
+    ctx->rules_beam = enable != 0;
+    return WMI_OK;
 }
 
 int wmi_decode_timestamps_beam(wmi_context *ctx, int beam_size, const int32_t *prompt, int n_prompt, int max_tokens,

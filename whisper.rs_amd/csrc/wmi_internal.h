@@ -349,6 +349,33 @@ struct TsRuleArgs {
     int max_initial_ts;      // first timestamp <= beg + this (< 0: no cap)
 };
 hipError_t launch_ts_sample_r(hipStream_t s, const TsRuleArgs &a);
+// ---- beam search under the decoding rules (wmi_rbeam.hip; DESIGN.md "Decoding
+// rules in the beam window"): k_ts_sample_r's masks per hypothesis row, each
+// row's history following the beam step's parent selection; the ranking, walk
+// and records of k_tsbeam_select ------------------------------------------------
+struct RBeamPart {           // one vocabulary split of one row
+    float m_tx;              // max over the split's text ids (< beg) of A' (-inf: none)
+    int32_t pad;
+    unsigned long long k_all;  // argmax key over all its ids >= beg, masked or not (0: none)
+    double sum_ap;           // sum exp(l - ap_val[0]) over the split's ids of A'
+    double sum_ts;           // sum exp(l - ts_val[0]) over its timestamps of A'
+    float ap_val[BEAM_TK];   // top-(K+1) of A' (id -1: no such rank)
+    int32_t ap_id[BEAM_TK];
+    float ts_val[BEAM_TK];   // top-(K+1) of the timestamps of A'
+    int32_t ts_id[BEAM_TK];
+};
+struct RBeamArgs {
+    BeamArgs b;              // (parts unused; suppress_id -1)
+    int beg;
+    int max_initial_ts;      // first timestamp <= beg + this (< 0: no cap)
+    const uint32_t *m0;      // [ceil(V / 32)] bit i set: id i is masked always (M0)
+    RuleHist *hist;          // [BEAM_MAX] history of the hypothesis in slot s
+    RBeamPart *rparts;       // [K][BEAM_NS]
+    TsRec *hist_rec;         // [tctx][BEAM_MAX] record of the token slot s took at step t
+    TsRec *fin_rec;          // [BEAM_MAX] record of finished hypothesis f's EOT
+    int32_t *hist_tab;       // [tctx][BEAM_MAX][3] {last, pen, lts1} of slot s after step t (debug read 29)
+};
+hipError_t launch_rbeam_step(hipStream_t s, const RBeamArgs &a);
 // ---- token-level timestamps (wmi_toktime.hip; DESIGN.md "Token-level
 // timestamps"): a recording's energy envelope E [N] and its running sum
 // P [N + 1], and the voice-activity pass over each segment's text tokens ------

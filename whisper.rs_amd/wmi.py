@@ -68,6 +68,7 @@ EXPORTS = (
     "wmi_get_segment_tokens_of", "wmi_decode_timestamps_beam", "wmi_set_beam_size",
     "wmi_set_fallback", "wmi_decode_timestamps_sampled", "wmi_get_window_count", "wmi_get_window_info",
     "wmi_set_decode_rules", "wmi_non_speech_tokens", "wmi_decode_timestamps_ruled", "wmi_set_initial_prompt",
+    "wmi_set_rules_beam", "wmi_decode_timestamps_ruled_beam",
     "wmi_is_non_speech_token", "wmi_set_token_timestamps", "wmi_token_times",
     "wmi_set_dtw", "wmi_align_tokens", "wmi_dtw_path", "wmi_dtw_path_host", "wmi_get_segment_dtw_of",
     "wmi_audio_to_mel_batch", "wmi_stage_audio", "wmi_transcribe_audio", "wmi_transcribe_audio_batch", "wmi_get_pcm",
@@ -207,6 +208,10 @@ def lib():
             L.wmi_decode_timestamps_ruled.argtypes = L.wmi_decode_timestamps_sampled.argtypes
             L.wmi_set_initial_prompt.argtypes = [vp, vp, C.c_int]
             L.wmi_is_non_speech_token.argtypes = [C.c_char_p, sz]
+        if hasattr(L, "wmi_set_rules_beam"):  # (as above: an older build has no ruled beam window)
+            L.wmi_set_rules_beam.argtypes = [vp, C.c_int]
+            L.wmi_decode_timestamps_ruled_beam.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.POINTER(i32),
+                                                           C.POINTER(C.c_double), C.POINTER(C.c_float)]
         if hasattr(L, "wmi_set_token_timestamps"):  # (as above: an older build has no token-level timestamps)
             L.wmi_set_token_timestamps.argtypes = [vp, C.POINTER(TokenTsParams)]
             L.wmi_token_times.argtypes = [vp, vp, sz, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int]
@@ -632,6 +637,30 @@ class WhisperContext:
                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, n, out, C.byref(cnt), _ptr(plog),
                                                  C.byref(pn)), self._h)
         return [out[i].as_dict() for i in range(cnt.value)], plog[:cnt.value].copy(), pn.value
+
+    def set_rules_beam(self, on: bool = True) -> None:
+        """With rules and a beam size above 1, transcribe() windows and
+        decode_timestamps_beam() take the ruled beam window
+        (wmi_set_rules_beam); off, the default, they stay Unsupported."""
+        _raise(lib().wmi_set_rules_beam(self._h, int(on)), self._h)
+
+    def decode_timestamps_ruled_beam(self, beam_size: int, prompt, max_tokens: int):
+        """decode_timestamps_beam() under the rules set: ([WhisperTokenData
+        dict] of the chosen hypothesis, its summed log-probability, p_nosp)."""
+        prompt = np.ascontiguousarray(prompt, dtype=np.int32)
+        out = (TokenData * max(1, max_tokens))()
+        n = C.c_int32()
+        sc = C.c_double()
+        pn = C.c_float()
+        _raise(lib().wmi_decode_timestamps_ruled_beam(self._h, beam_size, _ptr(prompt), prompt.size, max_tokens, out,
+                                                      C.byref(n), C.byref(sc), C.byref(pn)), self._h)
+        return [out[i].as_dict() for i in range(n.value)], sc.value, pn.value
+
+    def rule_history(self, n_steps: int) -> np.ndarray:
+        """The last ruled beam window's slot histories (debug read 29), int32
+        [n_steps][8][3]: after generation step t slot s has {last id was a
+        timestamp, the one before was, the last timestamp + 1 (0: none)}."""
+        return np.frombuffer(self.debug_read(29, n_steps * 8 * 3 * 4), np.int32).reshape(n_steps, 8, 3).copy()
 
     def set_initial_prompt(self, ids=()) -> None:
         """Text ids in front of the first window's context (wmi_set_initial_prompt); () clears."""
