@@ -277,11 +277,12 @@ int wmi_decode_timestamps_batch(wmi_context *ctx, const int32_t *prompt, int n_p
  * unequal lengths, up to 8 of them per decoder step: per round every active
  * recording's next window is encoded at its own seek and the windows are
  * decoded in lockstep; a recording that reached its end frees its row for a
- * waiting one.  The rows of a step share the decoder position, so windows
- * always decode without earlier text (as with wmi_set_no_context(1), whatever
- * that setting is).  Recording c yields the segments wmi_transcribe gives for
- * it alone with no-context on and the same language and task, whichever other
- * recordings share the batch.  Language of clip c: wmi_set_language(c, ..);
+ * waiting one.  By default windows decode without earlier text (as with
+ * wmi_set_no_context(1), whatever that setting is): recording c yields the
+ * segments wmi_transcribe gives for it alone with no-context on and the same
+ * language and task, whichever other recordings share the batch.  Under
+ * wmi_set_batch_context(1) every recording carries its own text context
+ * instead.  Language of clip c: wmi_set_language(c, ..);
  * WMI_LANG_AUTO is detected on that recording's first window and kept
  * (wmi_get_language(c)).  n_segments[n_clips]; read the segments with the
  * _of getters below. */
@@ -293,6 +294,30 @@ int wmi_transcribe_batch(wmi_context *ctx, int n_clips, const float *const *pcm,
 int wmi_get_segment_of(const wmi_context *ctx, int clip, int i, int64_t *t0, int64_t *t1, char *text, size_t cap,
                        size_t *len);
 int wmi_get_segment_tokens_of(const wmi_context *ctx, int clip, int i, wmi_token_data *out, size_t cap, int32_t *n);
+/* enable 1: wmi_transcribe_batch / wmi_transcribe_audio_batch give every
+ * recording its own text context, as wmi_transcribe does: recording c yields
+ * the segments wmi_transcribe gives for it alone under the same settings
+ * (no_context as set — with wmi_set_no_context(1) the batch stays without
+ * context —, language, task, fallback, rules, initial prompt, token times,
+ * DTW).  Rows of a round then hold prompts of unequal length.  The decoder
+ * keeps its one step position and right-aligns the rows: a row whose prompt is
+ * shorter than the round's longest starts that many steps later, so that
+ * every row samples its first token at the same step.  Such a row takes its
+ * position embedding relative to its own start and its self-attention never
+ * looks at keys before it, so from its start on it computes what it computes
+ * alone, up to the order of the key sums.  A round costs the steps of its
+ * longest prompt.  enable 0 (default): every call runs exactly the kernels it
+ * ran before.  Neither 0 nor 1: WMI_E_INVALID_ARG.  Holds until changed.  A
+ * beam size above 1 in the batch stays WMI_E_UNSUPPORTED. */
+int wmi_set_batch_context(wmi_context *ctx, int enable);
+/* wmi_decode_timestamps_batch with a prompt per row: row b (encoded clip b)
+ * decodes after prompts[b * prompt_stride .. + n_prompt[b]); out is
+ * [n_clips][max_tokens], n_out as there.  Rows of unequal length are
+ * right-aligned as under wmi_set_batch_context.  Equal lengths: exactly
+ * wmi_decode_timestamps_batch.  n_prompt[b] < 1, > prompt_stride, or
+ * max n_prompt + max_tokens > n_text_ctx: WMI_E_INVALID_ARG. */
+int wmi_decode_timestamps_rows(wmi_context *ctx, const int32_t *prompts, const int32_t *n_prompt, int prompt_stride,
+                               int max_tokens, wmi_token_data *out, int32_t *n_out);
 
 /* ---- temperature fallback, quality thresholds, no-speech ---------------- */
 
@@ -439,10 +464,12 @@ int wmi_set_rules_beam(wmi_context *ctx, int enable);
  * of wmi_transcribe: window 0 decodes from [prev] + ids + [sot ..], later
  * windows see the tail of ids + text (at most n_text_ctx / 2 ids, of which
  * the last are kept here too); a fallback result of T > 0.5 clears them with
- * the rest.  With wmi_set_no_context(1) and in wmi_transcribe_batch (one
- * prompt for all recordings) every window decodes from [prev] + ids +
- * [sot ..] — OpenAI prompts the first window only; this keeps the rows of a
- * batch at one decoder position.  n = 0 clears.  Independent of the rules. */
+ * the rest.  With wmi_set_no_context(1), and in wmi_transcribe_batch without
+ * wmi_set_batch_context(1) (one prompt for all recordings), every window
+ * decodes from [prev] + ids + [sot ..] — OpenAI prompts the first window
+ * only; this keeps the rows of such a batch at one distance into their
+ * prompts.  Under wmi_set_batch_context(1) the ids seed every recording's own
+ * context, as in wmi_transcribe.  n = 0 clears.  Independent of the rules. */
 int wmi_set_initial_prompt(wmi_context *ctx, const int32_t *ids, int n);
 
 /* ---- token-level timestamps, max_len / split_on_word -------------------- */
@@ -750,7 +777,18 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * cost matrix Cq (int32 [n + 1][M]) / its path f (int32 [n + 1])
  * (WMI_E_INVALID_ARG before a pass), 28 = with WMI_ALIGN_TIMING=1 the summed
  * hipEvent ms of the passes' decoder steps, matrix kernels and DTW, and the
- * passes counted (double [4], host). */
+ * passes counted (double [4], host).  30 = the last timestamp run of rows
+ * (wmi_decode_timestamps*, a window of wmi_transcribe / a round of
+ * wmi_transcribe_batch without a beam): its rows B, its feed steps Pmax and
+ * each row's start lo[8] = Pmax - its prompt length (int32 [10], host copy;
+ * all 0: rows of equal length).  31 = the last wmi_transcribe_batch (int64
+ * [7], host): its rounds, how many of them held rows of unequal prompt
+ * length, and summed over the rounds the feed steps Pmax, the rows' prompt
+ * lengths, the rows, the decoder steps and rows x Pmax (the last four give a
+ * batch's mean prompt length and the share of its feed steps spent in
+ * padding: scripts/transcribe_batch_bench.py).  In a run with rows of unequal
+ * length row b's position p sits at step p + lo[b]: 13 holds its logits in slab p + lo[b], and 19 is [rows][Pmax] with -1 in the
+ * lo[b] entries in front of row b's prompt. */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

@@ -147,6 +147,14 @@ struct wmi_context {
     int32_t win_host[2 * DEC_ROWS] = {};  // host copy of the last d_win upload (debug read 22)
     int win_slots = 0;                    // and its slot count (0: no batched round yet)
     bool no_context = false;    // wmi_set_no_context: windows of wmi_transcribe take no earlier text
+    // text context in the batch (wmi_set_batch_context): rows of a round hold prompts of unequal length,
+    // right-aligned under the one step position (run_ts_rows)
+    bool batch_context = false;
+    int32_t *d_lo = nullptr;    // [8] step at which each row's prompt starts (same allocation, behind d_rule_hist)
+    int32_t ts_lo[2 + DEC_ROWS] = {};   // the last RUN_TS run's {B, Pmax, lo[8]} (debug read 30)
+    // the last wmi_transcribe_batch (debug read 31): rounds, the ragged ones among them, then summed over the rounds
+    // the feed steps (Pmax), the rows' prompt lengths, the rows, the decoder steps and rows x feed steps
+    int64_t trb_count[7] = {0, 0, 0, 0, 0, 0, 0};
     // OpenAI decoding rules (wmi_set_decode_rules) and the initial prompt (wmi_set_initial_prompt)
     bool rules_on = false;
     int max_initial_ts = -1;
@@ -201,7 +209,8 @@ struct wmi_context {
     double al_ms[4] = {0, 0, 0, 0};     // their summed ms and the passes counted (debug read 28)
     // per recording of the last transcribe (one) / transcribe_batch
     std::vector<SegList> results = std::vector<SegList>(1);
-    std::vector<int32_t> ts_prompt;     // prompt rows of the last timestamp window, [rows][np] (debug read 19)
+    std::vector<int32_t> ts_prompt;     // prompt rows of the last timestamp window, [rows][np] (debug read 19; ragged rows:
+                                        // [rows][Pmax], row b's prompt behind lo[b] entries of -1)
     // language and task (wmi_set_language / wmi_set_task).  While every clip
     // is language 0 and the task transcribe (lang_default), the decode
     // entries enqueue what they always did; otherwise the block's prompt rows
@@ -1254,6 +1263,8 @@ struct DecRun {
     // whatever use_persist is (run_grid), and every selected layer's cross-attention launch is followed by
     // k_align_capture
     int align = 0;
+    // RUN_TS of several rows whose prompts differ in length: row b's starts at step d_lo[b] (run_ts_rows)
+    int ragged = 0;
 };
 
 // beam-step kernel arguments of a beam run
@@ -1370,6 +1381,7 @@ int enqueue_dec_step(wmi_context *ctx, const DecRun &run) {
             if (f32) { g.te32 = W32(ctx->te); g.te = nullptr; }
             g.amax = ctx->damax; g.tokens_out = ctx->dtokens + (size_t)b0 * run.out_stride; g.out_stride = run.out_stride;
             g.x_out = X[cur];
+            if (run.ragged) g.lo = ctx->d_lo;
             if (beam) {
                 g.tokens_out = nullptr;
                 g.beam_tok = ctx->dbstate->tok;
@@ -1387,6 +1399,7 @@ int enqueue_dec_step(wmi_context *ctx, const DecRun &run) {
         at.H = H; at.n = n; at.B = B;
         at.reset_amax = (l == 0 && !beam) ? ctx->damax : nullptr;
         at.clip_div = 1;
+        if (run.ragged) at.lo = ctx->d_lo;
         if (beam) {
             at.kv_src = ctx->dkvsrc;
             at.kv_src_stride = hp.n_text_ctx;
@@ -1554,11 +1567,11 @@ int run_dec_steps(wmi_context *ctx, const DecRun &run0, int pos0, int steps) {
             char key[192];
             // (a forced step enqueues what a greedy step does: they share graphs)
             // (... but an aligned one also captures scores: a field of its own)
-            snprintf(key, sizeof key, "%d/%d/%d/%d/%d/%d/%d/%d/%p/%p/%d/%d/%d/%d/%d/%d", run.b0, run.B, run.feed_len,
+            snprintf(key, sizeof key, "%d/%d/%d/%d/%d/%d/%d/%d/%p/%p/%d/%d/%d/%d/%d/%d/%d", run.b0, run.B, run.feed_len,
                      run.feed_stride, run.suppress_eot, run.out_stride, ctx->enc_T, ctx->enc_clips, (void *)ctx->dfeed,
                      (void *)ctx->dtokens, run.K, run.max_tokens, mk,
                      run.kind == RUN_TS ? (run.ruled ? 5 : run.sampled ? 3 : 1) : run.ts_beam ? (run.ruled ? (run.nosp ? 7 : 6) : run.nosp ? 4 : 2) : 0,
-                     reps, run.align);
+                     reps, run.align, run.ragged);
             auto it = ctx->graphs.find(key);
             if (it == ctx->graphs.end()) {
                 if (ctx->graphs.size() >= 32) ctx->clear_graphs();
@@ -1740,6 +1753,7 @@ PersistArgs persist_args(wmi_context *ctx, const DecRun &run, int G) {
         a.out_stride = 0;  // (record no token: dtokens holds decode results)
         // the timestamp sampler picks the next token into dts_tok, which the next launch feeds
         if (run.kind == RUN_TS) a.cur_tok = ctx->dts_tok;
+        if (run.ragged) a.lo = ctx->d_lo;
     }
     return a;
 }
@@ -2121,9 +2135,50 @@ int ensure_samp_buffers(wmi_context *ctx) {
     return WMI_OK;
 }
 
-int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &feed, int np, int max_tokens,
-                std::vector<std::vector<TsRec>> *out, TsSampled *samp = nullptr, bool ruled = false) {
+// Rows [b0, b0 + B) of the encoded batch, row b after the np tokens feed[b * np ..).
+// With `lens` the rows' prompts differ in length: feed holds them one behind
+// the other, row b's lens[b] tokens, and np is ignored.  The run then takes
+// Pmax = max lens feed steps and row b is right-aligned in them: its first
+// token repeated lo[b] = Pmax - lens[b] times, then its prompt, so every row's
+// first sampled token falls on step Pmax.  The kernels count row b's position
+// from lo[b] and mask its keys below it (DecRun::ragged).  Equal lengths are
+// the plain run.
+int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &feed_in, int np, int max_tokens,
+                std::vector<std::vector<TsRec>> *out, TsSampled *samp = nullptr, bool ruled = false,
+                const std::vector<int> *lens = nullptr) {
     const wmi_hparams &hp = ctx->hp;
+    std::vector<int32_t> aligned, shown;
+    int32_t lo[DEC_ROWS] = {};
+    bool ragged = false;
+    if (lens) {
+        if ((int)lens->size() != B || B < 1 || B > DEC_ROWS)
+            return set_err(ctx, WMI_E_INVALID_ARG, "%d prompt lengths for %d rows", (int)lens->size(), B);
+        np = 0;
+        size_t total_len = 0;
+        for (int v : *lens) {
+            if (v < 1) return set_err(ctx, WMI_E_INVALID_ARG, "a prompt of %d tokens", v);
+            np = std::max(np, v);
+            total_len += (size_t)v;
+        }
+        if (total_len != feed_in.size())
+            return set_err(ctx, WMI_E_INVALID_ARG, "internal: %zu prompt tokens for lengths summing to %zu", feed_in.size(),
+                           total_len);
+        for (int b = 0; b < B; ++b) {
+            lo[b] = np - (*lens)[b];
+            ragged = ragged || lo[b] > 0;
+        }
+        if (ragged) {
+            size_t at = 0;
+            for (int b = 0; b < B; ++b) {
+                aligned.insert(aligned.end(), (size_t)lo[b], feed_in[at]);
+                shown.insert(shown.end(), (size_t)lo[b], -1);
+                aligned.insert(aligned.end(), feed_in.begin() + at, feed_in.begin() + at + (*lens)[b]);
+                shown.insert(shown.end(), feed_in.begin() + at, feed_in.begin() + at + (*lens)[b]);
+                at += (size_t)(*lens)[b];
+            }
+        }
+    }
+    const std::vector<int32_t> &feed = ragged ? aligned : feed_in;
     if (ctx->enc_T <= 0) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
     if (B < 1 || B > DEC_ROWS || b0 < 0 || b0 + B > ctx->enc_clips)
         return set_err(ctx, WMI_E_INVALID_ARG, "rows [%d, %d) outside the %d encoded clips", b0, b0 + B, ctx->enc_clips);
@@ -2131,18 +2186,23 @@ int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &fee
         return set_err(ctx, WMI_E_INVALID_ARG, "prompt %d + max_tokens %d exceed n_text_ctx %d", np, max_tokens,
                        hp.n_text_ctx);
     if (!ctx->dts_tok) {
-        const size_t nb = 2 * DEC_ROWS * 4 + DEC_ROWS * sizeof(RuleHist);
+        const size_t nb = 2 * DEC_ROWS * 4 + DEC_ROWS * sizeof(RuleHist) + DEC_ROWS * 4;
         HIPCHK(ctx, hipMalloc(&ctx->dts_tok, nb));
         HIPCHK(ctx, hipMemset(ctx->dts_tok, 0, nb));
         ctx->dts_done = ctx->dts_tok + DEC_ROWS;
         ctx->d_rule_hist = (RuleHist *)(ctx->dts_done + DEC_ROWS);
+        ctx->d_lo = (int32_t *)(ctx->d_rule_hist + DEC_ROWS);
         HIPCHK(ctx, hipMalloc(&ctx->dts_rec, (size_t)DEC_ROWS * hp.n_text_ctx * sizeof(TsRec)));
         ctx->clear_graphs();
     }
     int rc = ensure_decode_buffers(ctx, DEC_ROWS * np, 1);
     if (rc) return rc;
-    ctx->ts_prompt = feed;
+    ctx->ts_prompt = ragged ? shown : feed;
+    ctx->ts_lo[0] = B;
+    ctx->ts_lo[1] = np;
+    memcpy(ctx->ts_lo + 2, lo, sizeof lo);
     DecRun run{RUN_TS, b0, B, np, np};
+    run.ragged = ragged ? 1 : 0;
     SampRow srows[DEC_ROWS] = {};
     if (samp) {
         rc = ensure_samp_buffers(ctx);
@@ -2158,6 +2218,7 @@ int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &fee
         rc = reset_run(ctx, true, gr.G, gr.Gh, false, feed.data(), B * np, true, run.ruled != 0);
         if (rc) return rc;
         if (samp) HIPCHK(ctx, hipMemcpyAsync(ctx->d_samp_rows, srows, sizeof srows, hipMemcpyHostToDevice, ctx->stream));
+        if (ragged) HIPCHK(ctx, hipMemcpyAsync(ctx->d_lo, ctx->ts_lo + 2, sizeof lo, hipMemcpyHostToDevice, ctx->stream));
         have = 0;
         for (int done = 0; done < total;) {
             const int chunk = std::min(16, total - done);
@@ -2674,8 +2735,10 @@ struct TrAttempt {
 // size a T = 0 attempt is the beam window with k_no_speech behind it.  Rules
 // and a beam size (wmi_set_rules_beam): a T = 0 attempt is the ruled beam
 // window, one at T > 0 goes through k_ts_sample_r as at beam size 1.
+// With `lens` (text context in the batch) row b is fed its own lens[b] tokens,
+// one row behind the other in feed, and np is ignored (run_ts_rows).
 int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows, const std::vector<int32_t> &feed, int np,
-                      std::vector<TrAttempt> *out) {
+                      std::vector<TrAttempt> *out, const std::vector<int> *lens = nullptr) {
     const int B = (int)rows.size();
     const bool fb = !tr.temps.empty();
     out->assign((size_t)B, {});
@@ -2695,7 +2758,7 @@ int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows,
     // (under the decoding rules every row goes through k_ts_sample_r: fallback off at T = 0, no figures kept)
     const bool ruled = ctx->rules_on;
     std::vector<std::vector<TsRec>> toks;
-    int rc = run_ts_rows(ctx, 0, B, feed, np, tr.n_max, &toks, fb || ruled ? &sp : nullptr, ruled);
+    int rc = run_ts_rows(ctx, 0, B, feed, np, tr.n_max, &toks, fb || ruled ? &sp : nullptr, ruled, lens);
     if (rc) return rc;
     for (int b = 0; b < B; ++b) {
         TrAttempt &a = (*out)[b];
@@ -2808,14 +2871,17 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
     return WMI_OK;
 }
 
-// wmi_transcribe_batch: every loaded recording through whisper_full's loop
-// without text context, up to DEC_ROWS of them per decoder step.  All mels
+// wmi_transcribe_batch: every loaded recording through whisper_full's loop,
+// up to DEC_ROWS of them per decoder step; without text context, or under
+// wmi_set_batch_context each with its own (TrRec::past).  All mels
 // stay resident; a recording holds host state (TrRec) and its own segment
 // list.  Per round the active recordings sit compacted in rows 0..B-1: one
 // encode of the B slots, each at its recording's seek (k_mel_window's per-slot
-// source and offset), one lockstep timestamp window of B rows — every prompt
-// is [sot (, language, task)], after [prev] + the one initial prompt if there
-// is one, so the rows share the decoder's one position —
+// source and offset), one lockstep timestamp window of B rows — without
+// context every prompt is [sot (, language, task)], after [prev] + the one
+// initial prompt if there is one, and the rows sit at one distance into their
+// prompts; with it each row has its own tr_prompt and run_ts_rows right-aligns
+// the rows under the decoder's one step position —
 // then each row's tr_settle.  A recording that reached its end leaves its
 // row; a waiting one takes a free row at the next round; under the fallback a
 // rejected recording stays at its seek and takes its next temperature in the
@@ -2823,7 +2889,8 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
 int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
     const int R = ctx->n_clips;
     if (!ctx->d_win) HIPCHK(ctx, hipMalloc(&ctx->d_win, 2 * DEC_ROWS * 4));
-    TrRun tr = tr_begin(ctx, R, max_tokens, false);
+    TrRun tr = tr_begin(ctx, R, max_tokens, ctx->batch_context && !ctx->no_context);
+    memset(ctx->trb_count, 0, sizeof ctx->trb_count);
     for (int r = 0; r < R; ++r) {
         ctx->lang_used[r] = tr.recs[r].lang;  // (AUTO: until the recording's first window detects it)
         ctx->lang_p[r] = -1.0f;
@@ -2852,15 +2919,25 @@ int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
         rc = tr_resolve_languages(ctx, tr, rows);
         if (rc) return rc;
         std::vector<int32_t> feed;
+        std::vector<int> lens;
         int np = 0;
         for (int r : rows) {
             const std::vector<int32_t> prompt = tr_prompt(ctx, tr.recs[r]);
             np = (int)prompt.size();
+            lens.push_back(np);
             feed.insert(feed.end(), prompt.begin(), prompt.end());
         }
         std::vector<TrAttempt> att;
-        rc = tr_decode_attempt(ctx, tr, rows, feed, np, &att);
+        rc = tr_decode_attempt(ctx, tr, rows, feed, np, &att, &lens);
         if (rc) return rc;
+        ++ctx->trb_count[0];
+        for (int b = 0; b < B; ++b)
+            if (ctx->ts_lo[2 + b] > 0) { ++ctx->trb_count[1]; break; }
+        ctx->trb_count[2] += ctx->ts_lo[1];
+        for (int v : lens) ctx->trb_count[3] += v;
+        ctx->trb_count[4] += B;
+        ctx->trb_count[5] += ctx->last_run_steps;
+        ctx->trb_count[6] += (int64_t)B * ctx->ts_lo[1];
         for (int b = 0; b < B; ++b) {
             bool done;
             rc = tr_settle(ctx, tr, tr.recs[rows[b]], b, std::move(att[b]), &done);
@@ -3538,6 +3615,45 @@ static int wmi_decode_timestamps_batch_impl(wmi_context *ctx, const int32_t *pro
     return WMI_OK;
 }
 
+// wmi_decode_timestamps_batch with a prompt per row: per block of up to DEC_ROWS
+// clips one run_ts_rows with the rows' lengths (a block of equal lengths is the
+// plain run)
+static int wmi_decode_timestamps_rows_impl(wmi_context *ctx, const int32_t *prompts, const int32_t *n_prompt, int prompt_stride,
+                                           int max_tokens, wmi_token_data *out, int32_t *n_out) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (!prompts || !n_prompt || prompt_stride < 1 || max_tokens < 1 || !out || !n_out)
+        return set_err(ctx, WMI_E_INVALID_ARG, "null prompts / n_prompt / out / n_out, or prompt_stride %d / max_tokens %d below 1",
+                       prompt_stride, max_tokens);
+    if (ctx->enc_T <= 0 || ctx->enc_clips < 1) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
+    const int Bt = ctx->enc_clips;
+    int pmax = 0;
+    for (int b = 0; b < Bt; ++b) {
+        if (n_prompt[b] < 1 || n_prompt[b] > prompt_stride)
+            return set_err(ctx, WMI_E_INVALID_ARG, "n_prompt[%d] = %d outside [1, prompt_stride=%d]", b, n_prompt[b], prompt_stride);
+        pmax = std::max(pmax, n_prompt[b]);
+        int rc = check_ts_args(ctx, prompts + (size_t)b * prompt_stride, n_prompt[b], max_tokens, out, n_out);
+        if (rc) return rc;
+    }
+    if (pmax + max_tokens > ctx->hp.n_text_ctx)
+        return set_err(ctx, WMI_E_INVALID_ARG, "prompt %d + max_tokens %d exceed n_text_ctx %d", pmax, max_tokens, ctx->hp.n_text_ctx);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    for (int b0 = 0; b0 < Bt; b0 += DEC_ROWS) {
+        const int B = std::min(DEC_ROWS, Bt - b0);
+        std::vector<int32_t> feed;
+        std::vector<int> lens;
+        for (int b = 0; b < B; ++b) {
+            const int32_t *p = prompts + (size_t)(b0 + b) * prompt_stride;
+            feed.insert(feed.end(), p, p + n_prompt[b0 + b]);
+            lens.push_back(n_prompt[b0 + b]);
+        }
+        std::vector<std::vector<TsRec>> rec;
+        int rc = run_ts_rows(ctx, b0, B, feed, 0, max_tokens, &rec, nullptr, false, &lens);
+        if (rc) return rc;
+        for (int b = 0; b < B; ++b) copy_out_tokens(rec[b], out + (size_t)(b0 + b) * max_tokens, n_out + b0 + b);
+    }
+    return WMI_OK;
+}
+
 static int wmi_transcribe_batch_impl(wmi_context *ctx, int n_clips, const float *const *pcm, const size_t *n_samples,
                                      int max_tokens, int32_t *n_segments) {
     if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
@@ -3569,6 +3685,13 @@ int wmi_set_no_context(wmi_context *ctx, int no_context) {
     if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
     if (no_context != 0 && no_context != 1) return set_err(ctx, WMI_E_INVALID_ARG, "no_context %d is neither 0 nor 1", no_context);
     ctx->no_context = no_context != 0;
+    return WMI_OK;
+}
+
+int wmi_set_batch_context(wmi_context *ctx, int enable) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    if (enable != 0 && enable != 1) return set_err(ctx, WMI_E_INVALID_ARG, "enable %d is neither 0 nor 1", enable);
+    ctx->batch_context = enable != 0;
     return WMI_OK;
 }
 
@@ -4400,6 +4523,15 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
             memcpy(out, ctx->ts_prompt.data(), std::min(have19, bytes));
             return WMI_OK;
         }
+        case 30: {  // host: the last timestamp run's rows, feed steps and each row's start, int32 {B, Pmax, lo[8]}
+            memcpy(out, ctx->ts_lo, std::min(sizeof ctx->ts_lo, bytes));
+            return WMI_OK;
+        }
+        case 31: {  // host, int64 [7]: rounds of the last wmi_transcribe_batch, those whose rows held prompts of unequal length,
+                    // then summed over the rounds the feed steps, the rows' prompt lengths, rows, decoder steps, rows x feed steps
+            memcpy(out, ctx->trb_count, std::min(sizeof ctx->trb_count, bytes));
+            return WMI_OK;
+        }
         case 20: {  // host: windows, decoder steps (every attempt's) and fallback attempts of the last wmi_transcribe, int64 [3]
             memcpy(out, ctx->tr_count, std::min(sizeof ctx->tr_count, bytes));
             return WMI_OK;
@@ -4630,6 +4762,13 @@ int wmi_transcribe(wmi_context *ctx, const float *pcm, size_t n_samples, int max
 int wmi_decode_timestamps_batch(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens, wmi_token_data *out,
                                 int32_t *n_out) {
     return guarded(ctx, [&] { return wmi_decode_timestamps_batch_impl(ctx, prompt, n_prompt, max_tokens, out, n_out); });
+}
+
+int wmi_decode_timestamps_rows(wmi_context *ctx, const int32_t *prompts, const int32_t *n_prompt, int prompt_stride,
+                               int max_tokens, wmi_token_data *out, int32_t *n_out) {
+    return guarded(ctx, [&] {
+        return wmi_decode_timestamps_rows_impl(ctx, prompts, n_prompt, prompt_stride, max_tokens, out, n_out);
+    });
 }
 
 int wmi_transcribe_batch(wmi_context *ctx, int n_clips, const float *const *pcm, const size_t *n_samples, int max_tokens,

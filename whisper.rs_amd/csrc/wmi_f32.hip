@@ -241,12 +241,13 @@ __global__ __launch_bounds__(256) void k_dec_gemv32(DecGemvArgs a) {
         const int pos = IN == 3 ? a.st->pos : 0;
         for (int rb = w; rb < B; rb += 4) {
             float *xr = xs + rb * K;
-            if (IN == 3) {  // x = te[tok] + pe[pos] (get_rows f32, add)
+            if (IN == 3) {  // x = te[tok] + pe[pos] (get_rows f32, add); a ragged row counts from its own start
+                const int ppos = a.lo ? max(pos - a.lo[rb], 0) : pos;
                 const bool fed = pos < a.feed_len;
                 const int32_t tok = fed ? a.feed[rb * a.feed_stride + pos]
                                         : (a.beam_tok ? a.beam_tok[rb] : shard_token32(a.amax + rb * AMAX_SHARDS, lane));
                 for (int k = lane; k < K; k += 64) {
-                    const float v = a.te32[(int64_t)tok * K + k] + a.pe[(int64_t)pos * K + k];
+                    const float v = a.te32[(int64_t)tok * K + k] + a.pe[(int64_t)ppos * K + k];
                     xr[k] = v;
                     if (blockIdx.x == 0) a.x_out[(int64_t)rb * K + k] = v;
                 }

@@ -194,6 +194,9 @@ struct DecGemvArgs {
     // f32 models: W32 = f32 weights [N][K] (W / Wq5 unused), te32 = f32 token
     // embedding for IN = 3; activations stay f32 into the dot (wmi_f32.hip)
     const float *W32, *te32;
+    // ragged rows (DESIGN.md "Text context in the batch"): row b's prompt starts
+    // at step lo[b], its position embedding is pe[max(pos - lo[b], 0)] (null: 0)
+    const int32_t *lo;
 };
 constexpr int AMAX_SHARDS = 64;
 constexpr int DEC_ROWS = 8;  // decoder rows per step: clips (greedy) or beam hypotheses
@@ -240,6 +243,9 @@ struct DecAttnArgs {
     // then LN(x_out); block (0, 0, b) stores x_out[b] (x_out != x: ping-pong)
     const float *res_parts, *res_bias;
     float *x_out;
+    // self-attention of ragged rows: row b attends to keys [min(lo[b], pos), pos]
+    // only (k_dec_self_attn<MK, true>; null: every key, the plain instances)
+    const int32_t *lo;
 };
 // exchange words of one (layer, clip, head) for the cooperative kernel
 struct XSync {
@@ -608,6 +614,10 @@ struct PersistArgs {
     // owns none skips phase A: the H self-attention workgroups enter phase B
     // straight from the previous layer's phase I (0: the rows over all workgroups)
     int a_off_b;
+    // ragged rows (multi-row instances without beam search): row b's prompt
+    // starts at step lo[b]; its layer-0 position embedding is pe[max(pos -
+    // lo[b], 0)] and phase B masks its keys below min(lo[b], pos) (null: 0)
+    const int32_t *lo;
 };
 // rows per workgroup of an N-row GEMV over G workgroups, even (f16-pair outputs)
 __host__ __device__ constexpr int px_rows_even(int N, int G) { return (((N + G - 1) / G) + 1) & ~1; }

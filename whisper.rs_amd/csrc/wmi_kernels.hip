@@ -1830,12 +1830,13 @@ __global__ __launch_bounds__(64 * NW) void k_dec_gemv(DecGemvArgs a) {
                 if (IN == 0) {
                     ln_load_row(a.x + (int64_t)rb * K, K, lane, xv);
                 } else {
-                    // x = te[tok] + pe[pos] (get_rows f16 -> f32, add)
+                    // x = te[tok] + pe[pos] (get_rows f16 -> f32, add); a ragged
+                    // row's position counts from its own start (DecGemvArgs::lo)
                     const bool fed = pos < a.feed_len;
                     const int32_t tok = fed ? a.feed[rb * a.feed_stride + pos]
                                             : (a.beam_tok ? a.beam_tok[rb] : shard_token(a.amax + rb * AMAX_SHARDS, lane));
                     const f16 *ter = (const f16 *)a.te + (int64_t)tok * K;
-                    const float *per = a.pe + (int64_t)pos * K;
+                    const float *per = a.pe + (int64_t)(a.lo ? max(pos - a.lo[rb], 0) : pos) * K;
                     half4 tv[LNV];
                     float4 pv[LNV];
 #pragma unroll
@@ -2345,12 +2346,18 @@ __global__ __launch_bounds__(256) void k_dec_attn_pv(DecAttnArgs a) {
 // self-attention over the KV cache (M = pos + 1 <= 512 keys): one workgroup
 // per (clip, head), every K and V load issued up front.  Output goes to
 // opart[b][0][n] (n_parts = 1 for the consumer).
-template <int MK>  // keys covered: M = pos + 1 <= MK (64, 128, 256 or 512)
+// RAG (DecAttnArgs::lo): row b attends to keys [lo, M) only, lo = min(lo[b],
+// pos) — a row that has not started attends to itself.  A key below lo takes
+// no part in the maximum or the sum, its P entry is 0, and its value row is
+// not loaded (zero registers), so its P.V term is 0 * 0 whatever the cache
+// holds there.
+template <int MK, bool RAG = false>  // keys covered: M = pos + 1 <= MK (64, 128, 256 or 512)
 __global__ __launch_bounds__(256) void k_dec_self_attn(DecAttnArgs a) {
     constexpr int RK = MK > 256 ? 2 : 1, NVI = MK / 32;
     const int h = blockIdx.x, b = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int M = a.st->pos + 1;
+    const int lo = RAG ? min(a.lo[b], M - 1) : 0;
     const int n = a.n;
     __shared__ float redf[4];
     __shared__ double redd[4];
@@ -2396,8 +2403,11 @@ __global__ __launch_bounds__(256) void k_dec_self_attn(DecAttnArgs a) {
     }
     half8 vv[NVI];
 #pragma unroll
-    for (int i = 0; i < NVI; ++i)
-        vv[i] = *(const half8 *)((const f16 *)a.V + sv[i] * a.clip_stride + (int64_t)jv[i] * n + h * 64 + doct * 8);
+    for (int i = 0; i < NVI; ++i) {
+        const half8 *vp = (const half8 *)((const f16 *)a.V + sv[i] * a.clip_stride + (int64_t)jv[i] * n + h * 64 + doct * 8);
+        if constexpr (RAG) vv[i] = jg + 32 * i >= lo ? *vp : half8{};
+        else vv[i] = *vp;
+    }
     half8 qv[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) qv[i] = *(const half8 *)(qr + 8 * i);
@@ -2430,7 +2440,7 @@ __global__ __launch_bounds__(256) void k_dec_self_attn(DecAttnArgs a) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) s = dot8(kv[r][i], qv[i], s);
         sc[r] = s;
-        if (tid + 256 * r < M) mx = fmaxf(mx, s);
+        if (tid + 256 * r < M && tid + 256 * r >= lo) mx = fmaxf(mx, s);
     }
     mx = wave_max(mx);
     if (lane == 0) redf[w] = mx;
@@ -2441,7 +2451,7 @@ __global__ __launch_bounds__(256) void k_dec_self_attn(DecAttnArgs a) {
 #pragma unroll
     for (int r = 0; r < RK; ++r) {
         p[r] = 0.0f;
-        if (tid + 256 * r < M) {
+        if (tid + 256 * r < M && tid + 256 * r >= lo) {
             p[r] = exp_f16_exact(sc[r] - mx);
             sum += (double)p[r];
         }
@@ -2452,7 +2462,7 @@ __global__ __launch_bounds__(256) void k_dec_self_attn(DecAttnArgs a) {
     const float inv = (float)(1.0 / (((redd[0] + redd[1]) + redd[2]) + redd[3]));
 #pragma unroll
     for (int r = 0; r < RK; ++r)
-        if (tid + 256 * r < MK) P[tid + 256 * r] = f2h_bits(tid + 256 * r < M ? p[r] * inv : 0.0f);
+        if (tid + 256 * r < MK) P[tid + 256 * r] = f2h_bits(tid + 256 * r < M && tid + 256 * r >= lo ? p[r] * inv : 0.0f);
     __syncthreads();
     float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -2544,6 +2554,17 @@ hipError_t launch_dec_attn(hipStream_t s, const DecAttnArgs &a) {
         // fused output projection split over n / 128 workgroups per head
         const int S = (a.Wo && a.n % 128 == 0) ? a.n / 128 : 1;
         const dim3 grid(a.H, a.B, S);
+        if (a.lo) {  // ragged rows: no beam table (the rows are clips)
+            if (a.kv_src) return hipErrorInvalidValue;
+            switch (a.mk) {
+                case 64: hipLaunchKernelGGL((k_dec_self_attn<64, true>), grid, dim3(256), 0, s, a); break;
+                case 128: hipLaunchKernelGGL((k_dec_self_attn<128, true>), grid, dim3(256), 0, s, a); break;
+                case 256: hipLaunchKernelGGL((k_dec_self_attn<256, true>), grid, dim3(256), 0, s, a); break;
+                case 512: hipLaunchKernelGGL((k_dec_self_attn<512, true>), grid, dim3(256), 0, s, a); break;
+                default: return hipErrorInvalidValue;
+            }
+            return hipGetLastError();
+        }
         switch (a.mk) {
             case 64: hipLaunchKernelGGL(k_dec_self_attn<64>, grid, dim3(256), 0, s, a); break;
             case 128: hipLaunchKernelGGL(k_dec_self_attn<128>, grid, dim3(256), 0, s, a); break;

@@ -1039,6 +1039,8 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
     // Wqkv rows: one row (greedy), off the H self-attention workgroups where
     // they fit on the others (px_a_off_b, PersistArgs::a_off_b); a workgroup
     // that owns none then has no phase A
+    // ragged rows (PersistArgs::lo): the multi-row instances without beam search
+    constexpr bool RAG = BT >= 2 && !BEAM;
     constexpr bool AOB = BT == 1 && !BEAM && NS <= PX_AOB_NMAX;
     const bool aob = AOB && px_a_off_b(a.a_off_b != 0, NS, H, G, PX_GDESIGN);
     if constexpr (AOB) {
@@ -1216,11 +1218,14 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
                             a.tokens_out[tid * a.out_stride + (pos - a.feed_len)] = sh.tok[tid];
                     }
                     S.pre(l16);  // (no poll to hide it behind in layer 0)
-                    // x = te[tok] + pe[pos]  (get_rows f16 -> f32, add)
+                    // x = te[tok] + pe[pos]  (get_rows f16 -> f32, add); a ragged
+                    // row's position counts from its own start (PersistArgs::lo)
                     for (int i = tid; i < B * NS / 4; i += PT) {
                         const int b = (i * 4) / NS, e = i * 4 - b * NS;
                         const half4 tv = *(const half4 *)((const f16 *)a.te + (int64_t)sh.tok[b] * NS + e);
-                        const float4 pv = *(const float4 *)(a.pe + (int64_t)pos * NS + e);
+                        int pb = pos;
+                        if constexpr (RAG) pb = a.lo ? max(pos - a.lo[b], 0) : pos;
+                        const float4 pv = *(const float4 *)(a.pe + (int64_t)pb * NS + e);
                         *(float4 *)(xf + b * NS + e) = make_float4((float)tv[0] + pv.x, (float)tv[1] + pv.y,
                                                                    (float)tv[2] + pv.z, (float)tv[3] + pv.w);
                     }
@@ -1303,6 +1308,18 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
                 for (int t = wg; t < B * H; t += G) {
                     const int b = t / H, h = t - b * H;
                     const int doct = tid & 7, jg = tid >> 3;
+                    // ragged rows: keys [lo, pos] only, lo = min(lo[b], pos) — a
+                    // row that has not started attends to itself; a key below
+                    // lo is not loaded (zero registers), stays out of the
+                    // maximum and the sum, and has P16 = 0 and weight 0 in P.V.
+                    // The one-row and beam instances have no such test: started()
+                    // is the constant true there and their code stays as it was.
+                    int lo = 0;
+                    if constexpr (RAG) lo = a.lo ? min(a.lo[b], pos) : 0;
+                    auto started = [&](int j) {
+                        if constexpr (RAG) return j >= lo;
+                        else return true;
+                    };
                     // cache rows j < pos (this step's row comes from the granules)
                     half8 kv[2][8];
                     // (every register array is defined on every path — a
@@ -1334,14 +1351,14 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
                         const int j = tid + 256 * r;
                         const uint32_t off = (uint32_t)((((int64_t)srk[r] * tctx + j) * NS + h * 64) * 2);
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) kv[r][i] = j < pos ? bload_sc1(rk, off + 16 * i) : z8;
+                        for (int i = 0; i < 8; ++i) kv[r][i] = j < pos && started(j) ? bload_sc1(rk, off + 16 * i) : z8;
                     }
                     // value rows j < pos, in flight across the poll as well
                     half8 vv[16];
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         const int j = jg + 32 * i;
-                        vv[i] = j < pos ? bload_sc1(rv, (uint32_t)((((int64_t)srv[i] * tctx + j) * NS + h * 64 + doct * 8) * 2)) : z8;
+                        vv[i] = j < pos && started(j) ? bload_sc1(rv, (uint32_t)((((int64_t)srv[i] * tctx + j) * NS + h * 64 + doct * 8) * 2)) : z8;
                     }
                     PREFETCH_ISSUED
                     __syncthreads();
@@ -1375,7 +1392,7 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
                             for (int i = 0; i < 8; ++i) s = dot8(kv[r][i], q8[i], s);
                         s = j < pos ? s : j == pos ? snew : 0.0f;
                         sc[r] = s;
-                        if (j < M) mx = fmaxf(mx, s);
+                        if (j < M && started(j)) mx = fmaxf(mx, s);
                     }
                     mx = wave_max(mx);
                     if (lane == 0) sh.redf[w] = mx;
@@ -1390,10 +1407,12 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
                     double sum = 0.0;
 #pragma unroll
                     for (int r = 0; r < 2; ++r) {
-                        if (tid + 256 * r < M) {
+                        if (tid + 256 * r < M && started(tid + 256 * r)) {
                             const float pr = exp_f16_hash(sc[r] - mx, sh.expfb, fbk);
                             sum += (double)pr;
                             P16[tid + 256 * r] = f2h_bits(pr);
+                        } else if constexpr (RAG) {
+                            if (tid + 256 * r < lo) P16[tid + 256 * r] = 0;
                         }
                     }
                     sum = wave_sum(sum);
@@ -1415,7 +1434,7 @@ __global__ __launch_bounds__(PT, 1) void k_dec_persist(PersistArgs a) {
                     for (int i = 0; i < 16; ++i) {
                         if (32 * i >= pos) break;  // workgroup-uniform: the rest add zeros
                         const int j = jg + 32 * i;
-                        const float pj = j < pos ? pv[i] : 0.0f;
+                        const float pj = j < pos && started(j) ? pv[i] : 0.0f;
 #pragma unroll
                         for (int e = 0; e < 8; ++e) o[e] = o[e] + pj * (float)vv[i][e];
                     }
@@ -2480,7 +2499,8 @@ hipError_t launch_dec_persist(hipStream_t s, const PersistArgs &a, int G) {
         a.cl > 128 * NKP || (int64_t)a.nch * a.cl < a.T || (int64_t)a.B * (a.n / 64) * a.nch > PX_TASKS ||
         a.tctx > 512 || a.cl % 128 || (a.beam && a.n_steps != 1) || (a.kv_src && a.kv_src_stride < a.tctx) ||
         (!a.beam && a.B == 1 && a.cl > 256) ||  // (the one-row instance: two sub-chunks per task)
-        (a.xshare && (!a.beam || a.n <= 768 || a.cl != 128)))
+        (a.xshare && (!a.beam || a.n <= 768 || a.cl != 128)) ||
+        (a.lo && (a.beam || a.B < 2)))  // (ragged rows: the multi-row instances without beam search)
         return hipErrorInvalidValue;
     switch (a.n) {
         case 128: return launch_ns<128>(s, a, G);

@@ -65,7 +65,8 @@ EXPORTS = (
     "wmi_get_language",
     "wmi_decode_timestamps", "wmi_transcribe", "wmi_get_segment", "wmi_get_segment_tokens",
     "wmi_set_no_context", "wmi_decode_timestamps_batch", "wmi_transcribe_batch", "wmi_get_segment_of",
-    "wmi_get_segment_tokens_of", "wmi_decode_timestamps_beam", "wmi_set_beam_size",
+    "wmi_get_segment_tokens_of", "wmi_set_batch_context", "wmi_decode_timestamps_rows",
+    "wmi_decode_timestamps_beam", "wmi_set_beam_size",
     "wmi_set_fallback", "wmi_decode_timestamps_sampled", "wmi_get_window_count", "wmi_get_window_info",
     "wmi_set_decode_rules", "wmi_non_speech_tokens", "wmi_decode_timestamps_ruled", "wmi_set_initial_prompt",
     "wmi_set_rules_beam", "wmi_decode_timestamps_ruled_beam",
@@ -194,6 +195,9 @@ def lib():
                                       C.POINTER(sz)]
         L.wmi_get_segment_tokens.argtypes = [vp, C.c_int, vp, sz, C.POINTER(i32)]
         L.wmi_set_no_context.argtypes = [vp, C.c_int]
+        if hasattr(L, "wmi_set_batch_context"):  # (as below: an older build has no text context in the batch)
+            L.wmi_set_batch_context.argtypes = [vp, C.c_int]
+            L.wmi_decode_timestamps_rows.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
         L.wmi_decode_timestamps_beam.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.POINTER(i32),
                                                  C.POINTER(C.c_double)]
         L.wmi_set_beam_size.argtypes = [vp, C.c_int]
@@ -515,7 +519,8 @@ class WhisperContext:
 
     def set_no_context(self, on: bool = True) -> None:
         """Windows of transcribe() decode without the earlier windows' text
-        (whisper.cpp no_context); transcribe_batch() always does."""
+        (whisper.cpp no_context); transcribe_batch() does so unless
+        set_batch_context(1) is on, and then follows this setting."""
         _raise(lib().wmi_set_no_context(self._h, int(bool(on))), self._h)
 
     def decode_timestamps_beam(self, beam_size: int, prompt, max_tokens: int):
@@ -545,6 +550,30 @@ class WhisperContext:
                self._h)
         return [[out[c * max_tokens + i].as_dict() for i in range(n[c])] for c in range(self.n_clips)]
 
+    def set_batch_context(self, enable=1) -> None:
+        """1: transcribe_batch() gives every recording its own text context, as
+        transcribe() does (rows of unequal prompt length are right-aligned
+        under the decoder's one step position); 0, the default: every window
+        without earlier text.  Neither: InvalidArgument."""
+        _raise(lib().wmi_set_batch_context(self._h, int(enable)), self._h)
+
+    def decode_timestamps_rows(self, prompts, max_tokens: int):
+        """decode_timestamps_batch() with a prompt per encoded clip (a list of
+        id sequences of any lengths): per clip [WhisperTokenData dict]."""
+        rows = [np.ascontiguousarray(p, dtype=np.int32).ravel() for p in prompts]
+        lens = np.array([r.size for r in rows], np.int32)
+        stride = max(1, int(lens.max()) if len(rows) else 1)
+        flat = np.zeros((max(1, len(rows)), stride), np.int32)
+        for b, r in enumerate(rows):
+            flat[b, :r.size] = r
+        out = (TokenData * (max(1, self.n_clips) * max_tokens))()
+        n = np.zeros(max(1, self.n_clips), np.int32)
+        if len(rows) != self.n_clips:
+            raise ValueError(f"{len(rows)} prompts for {self.n_clips} clips")
+        _raise(lib().wmi_decode_timestamps_rows(self._h, _ptr(flat), _ptr(lens), stride, max_tokens, out, _ptr(n)),
+               self._h)
+        return [[out[c * max_tokens + i].as_dict() for i in range(n[c])] for c in range(self.n_clips)]
+
     def segments_of(self, clip: int, n_segments: int):
         """Segments of recording `clip` of the last transcribe_batch."""
         segs = []
@@ -565,7 +594,8 @@ class WhisperContext:
     def transcribe_batch(self, clips, max_tokens: int = 220):
         """transcribe() of several recordings (any lengths, at most max_clips)
         with up to 8 of them per decoder step, every window without earlier
-        text: per recording the list transcribe() returns."""
+        text (or, under set_batch_context(1), each recording with its own):
+        per recording the list transcribe() returns."""
         clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
         ptrs = (C.c_void_p * max(1, len(clips)))(*[c.ctypes.data for c in clips])
         ns = (C.c_size_t * max(1, len(clips)))(*[c.size for c in clips])
