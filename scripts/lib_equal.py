@@ -1,9 +1,11 @@
 """Bitwise comparison of two builds of the library (scripts/build_variant.sh)
 on the encoder output and the persistent decoder: greedy ids and last-step
 logits of base (1 clip and 8 clips), micro and small; then micro's beam
-search, timestamp window, teacher-forced logits and language detection, so
-every kind of decode run is compared; a 2-clip encode at a mel offset and
-wmi_transcribe over several windows.  Usage: lib_equal.py LIB_A LIB_B (needs the GPU)."""
+search, timestamp window, teacher-forced logits and language detection, the
+timestamped beam, the sampled and the ruled window at T = 0 and T > 0, the
+ruled beam and an 8-beam search, so every kind of decode run is compared; a
+2-clip encode at a mel offset and wmi_transcribe over several windows,
+without and with a temperature fallback.  Usage: lib_equal.py LIB_A LIB_B (needs the GPU)."""
 import os
 import subprocess
 import sys
@@ -54,6 +56,33 @@ def run_one(out):
     res["ts_ids"] = np.array([[t["id"], t["tid"]] for t in ts])
     res["ts_p"] = np.array([[t["p"], t["pt"], t["ptsum"]] for t in ts], np.float32)
     res["forced_lg"] = ctx.decode_logits((prompt + [sp["not"], 11, 23, 37, 41, 53])[:6], 1)
+    # the windows of the other pick kernels (csrc/wmi_pick.h), a few tokens
+    # each: the timestamped beam, the temperature sampler and the ruled
+    # sampler at T = 0 and at T = 0.8 under a fixed seed, the ruled beam with
+    # its slot histories, and an 8-beam search that may finish hypotheses
+    def recs(name, toks):
+        res[name + "_ids"] = np.array([[t["id"], t["tid"]] for t in toks], np.int32).reshape(-1, 2)
+        res[name + "_p"] = np.array([[t["p"], t["pt"], t["ptsum"]] for t in toks], np.float32).reshape(-1, 3)
+
+    toks, sc = ctx.decode_timestamps_beam(3, prompt, 6)
+    recs("tsbeam", toks)
+    res["tsbeam_score"] = np.float64(sc)
+    for ruled in (False, True):
+        if ruled:
+            ctx.set_decode_rules(max_initial_ts=50, suppress_non_speech=True)
+        for T in (0.0, 0.8):
+            window = ctx.decode_timestamps_ruled if ruled else ctx.decode_timestamps_sampled
+            toks, plog, pn = window(prompt, 6, T, 7, 0)
+            name = f"{'ruled' if ruled else 'sampled'}_T{T}"
+            recs(name, toks)
+            res[name + "_plog"], res[name + "_pnosp"] = plog, np.float32(pn)
+    toks, sc, pn = ctx.decode_timestamps_ruled_beam(3, prompt, 6)
+    recs("rbeam", toks)
+    res["rbeam_score"], res["rbeam_pnosp"] = np.float64(sc), np.float32(pn)
+    res["rbeam_hist"] = ctx.rule_history(max(1, len(toks)))
+    ctx.set_decode_rules(default=True)
+    for i, (tk, sc) in enumerate(ctx.decode_beam(8, 8)):
+        res[f"beam8_tok{i}"], res[f"beam8_score{i}"] = tk, np.float64(sc)
     # the scalar-offset encode of a 2-clip batch away from frame 0, and
     # wmi_transcribe with its default setting (earlier text as context) over
     # several windows: on the segmenting fixture of tests/test_transcribe_batch.py
@@ -71,6 +100,14 @@ def run_one(out):
     res["tr_ids"] = np.array([[t["id"], t["tid"]] for s in segs for t in s["tokens"]], np.int32).reshape(-1, 2)
     res["tr_p"] = np.array([[t["p"], t["pt"], t["ptsum"]] for s in segs for t in s["tokens"]], np.float32).reshape(-1, 3)
     res["tr_prompt"] = np.frombuffer(ctx.debug_read(19, 64 * 4), np.int32).copy()
+    if os.path.exists(seg):
+        # a fallback whose entropy threshold no window meets: every window is sampled again at T > 0
+        ctx.set_fallback(temperature_inc=0.5, entropy_thold=20.0, seed=1)
+        segs = ctx.transcribe(synth.synth_pcm_tones(4.0, 21), max_tokens=10)
+        res["fb_t"] = np.array([[s["t0"], s["t1"]] for s in segs], np.int64).reshape(-1, 2)
+        res["fb_ids"] = np.array([[t["id"], t["tid"]] for s in segs for t in s["tokens"]], np.int32).reshape(-1, 2)
+        res["fb_p"] = np.array([[t["p"], t["pt"], t["ptsum"]] for s in segs for t in s["tokens"]], np.float32).reshape(-1, 3)
+        res["fb_windows_steps_attempts"] = np.frombuffer(ctx.debug_read(20, 24), np.int64).copy()
     ctx.close()
     lang = os.path.join(os.environ["WMI_MODEL_CACHE"], "ggml-micro-lang-51865.bin")
     if os.path.exists(lang):

@@ -15,7 +15,8 @@ k_rbeam_select) against the beam step under the timestamp rule (k_tsbeam_part
 Prints one JSON line.
 
 Usage: rules_beam_bench.py [--model base] [--seconds 60] [--beams 5] [--reps 5]
-       [--iters 200] [--max-tokens 220]   (needs the GPU)"""
+       [--iters 200] [--max-tokens 220] [--step-only]   (needs the GPU)
+--step-only ends after part 1 (an A/B of two builds runs it once per library)."""
 import argparse
 import json
 import os
@@ -35,6 +36,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--max-tokens", type=int, default=220)
+    ap.add_argument("--step-only", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import synth
@@ -82,6 +84,9 @@ def main():
                 "tsbeam_spread_us": round(max(t[15]) - min(t[15]), 2), "rbeam_spread_us": round(max(t[16]) - min(t[16]), 2),
                 "ratio": round(med(t[16]) / med(t[15]), 3)}
         ctx.close()
+    if a.step_only:
+        print(json.dumps(out))
+        return
 
     # 2. wmi_transcribe
     rec = synth.synth_pcm_tones(a.seconds, 4000)

@@ -14,7 +14,8 @@ clock around calls that end synchronised).
 
 Prints one JSON line.
 
-Usage: rules_bench.py [--model base] [--seconds 60] [--reps 3] [--max-tokens 220]   (needs the GPU)"""
+Usage: rules_bench.py [--model base] [--seconds 60] [--reps 3] [--max-tokens 220] [--window-only]   (needs the GPU)
+--window-only ends after part 1 (an A/B of two builds runs it once per library)."""
 import argparse
 import json
 import os
@@ -32,6 +33,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--max-tokens", type=int, default=220)
+    ap.add_argument("--window-only", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import synth
@@ -74,6 +76,10 @@ def main():
         out[k + "_tokens"] = toks[k]
         out[k + "_step_us"] = [round(t * 1e6 / steps, 2) for t in times[k]]
         out[k + "_step_us_median"] = round(med(times[k]) * 1e6 / steps, 2)
+    if a.window_only:
+        ctx.close()
+        print(json.dumps(out))
+        return
 
     def transcribe(on):
         rules(on)

@@ -24,6 +24,7 @@
 #include "wmi_device.h"
 #include "wmi_internal.h"
 #include "wmi_gemm_epi.h"
+#include "wmi_pick.h"
 
 #pragma clang fp contract(off)
 
@@ -2654,90 +2655,23 @@ hipError_t launch_logits_capture(hipStream_t s, const float *logits, float *all,
 // (ids < beg) the argmax over ids >= beg, else the argmax over every id but
 // sot / solm / not (whisper_sample_best); ties to the lowest id.  Records
 // {id, tid = argmax over ids >= beg, p, pt = max_ts / (sum_ts + 1e-10), ptsum}.
-__device__ __forceinline__ unsigned long long ts_key(float v, int id) {
-    return ((unsigned long long)ord_f32(v) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)id);
-}
-__device__ __forceinline__ int ts_key_id(unsigned long long k) { return (int)(0xffffffffu - (uint32_t)(k & 0xffffffffu)); }
-
 // One workgroup per decoder row b: logits row b, tok_out[b], records
 // rec[b * max_rec + t].  done[b] is set once row b has sampled EOT; from then
 // on the row records nothing and feeds EOT (the rows of a step share one
 // position, so a finished row keeps stepping until the host ends the round).
+// (prologue, row statistics and record: wmi_pick.h, shared with k_ts_sample_t)
 __global__ __launch_bounds__(1024) void k_ts_sample(TsArgs a) {
-    const int pos = a.st->pos;
-    if (pos < a.feed_len) return;  // still feeding the prompt
-    const int t = pos - a.feed_len;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int b = blockIdx.x;
-    if (a.done[b]) {  // (uniform over the workgroup; set by a previous launch)
-        if (tid == 0) a.tok_out[b] = a.eot;
-        return;
-    }
-    a.logits += (size_t)b * a.V;
-    __shared__ float smax[16];
-    __shared__ double ssum[16], sts[16];
-    __shared__ unsigned long long sk[3][16];
-    float mx = -INFINITY;
-    unsigned long long k_all = 0, k_ts = 0, k_ts1 = 0, k_tx = 0;
-    for (int i = tid; i < a.V; i += 1024) {
-        const float l = a.logits[i];
-        mx = fmaxf(mx, l);
-        const unsigned long long k = ts_key(l, i);
-        if (i >= a.beg) k_ts = k > k_ts ? k : k_ts;
-        else k_tx = k > k_tx ? k : k_tx;
-        if (i > a.beg) k_ts1 = k > k_ts1 ? k : k_ts1;
-        if (i != a.sot && i != a.solm && i != a.not_) k_all = k > k_all ? k : k_all;
-    }
-    mx = wave_max(mx);
-    k_all = wave_max_u64(k_all);
-    k_ts = wave_max_u64(k_ts);
-    k_ts1 = wave_max_u64(k_ts1);
-    k_tx = wave_max_u64(k_tx);
-    __shared__ unsigned long long stx[16];
-    if (lane == 0) { smax[w] = mx; sk[0][w] = k_all; sk[1][w] = k_ts; sk[2][w] = k_ts1; stx[w] = k_tx; }
-    __syncthreads();
-    mx = smax[0];
-    k_all = sk[0][0]; k_ts = sk[1][0]; k_ts1 = sk[2][0]; k_tx = stx[0];
-    for (int i = 1; i < 16; ++i) {
-        mx = fmaxf(mx, smax[i]);
-        k_all = sk[0][i] > k_all ? sk[0][i] : k_all;
-        k_ts = sk[1][i] > k_ts ? sk[1][i] : k_ts;
-        k_ts1 = sk[2][i] > k_ts1 ? sk[2][i] : k_ts1;
-        k_tx = stx[i] > k_tx ? stx[i] : k_tx;
-    }
-    double s = 0.0, st = 0.0;
-    for (int i = tid; i < a.V; i += 1024) {
-        const double e = exp((double)a.logits[i] - (double)mx);
-        s += e;
-        if (i >= a.beg) st += e;
-    }
-    s = wave_sum(s);
-    st = wave_sum(st);
-    if (lane == 0) { ssum[w] = s; sts[w] = st; }
-    __syncthreads();
-    if (tid != 0) return;
-    double Z = 0.0, TS = 0.0;
-    for (int i = 0; i < 16; ++i) { Z += ssum[i]; TS += sts[i]; }
-    const int id_ts = ts_key_id(k_ts), id_tx = ts_key_id(k_tx);
-    const double p_maxts = exp((double)a.logits[id_ts] - (double)mx) / Z;
-    const double p_maxtx = exp((double)a.logits[id_tx] - (double)mx) / Z;
-    const double sum_ts = TS / Z;
-    int id;
-    if (t == 0) id = ts_key_id(k_ts1);
-    else if (sum_ts > p_maxtx) id = id_ts;
-    else id = ts_key_id(k_all);
-    a.tok_out[b] = id;
-    if (id == a.eot) a.done[b] = 1;
-    if (t < a.max_rec) {
-        TsRec r;
-        r.id = id;
-        r.tid = id_ts;
-        r.p = (float)(exp((double)a.logits[id] - (double)mx) / Z);
-        r.pt = (float)(p_maxts / (sum_ts + 1e-10));
-        r.ptsum = (float)sum_ts;
-        r.pad = 0;
-        a.rec[(size_t)b * a.max_rec + t] = r;
-    }
+    int t;
+    if (!samp_begin(a, t)) return;
+    const float *lg = a.logits + (size_t)blockIdx.x * a.V;
+    __shared__ RowLds rl;
+    RowStats r;
+    row_reduce(a, lg, rl, r);
+    if (threadIdx.x != 0) return;
+    row_probs(lg, rl, r);
+    const int id = pick_key_id(t == 0 ? r.k_ts1 : r.sum_ts > r.p_maxtx ? r.k_ts : r.k_all);
+    samp_feed(a, id);
+    if (t < a.max_rec) row_record(a, lg, r, t, id);
 }
 
 hipError_t launch_ts_sample(hipStream_t s, const TsArgs &a) {
@@ -2753,8 +2687,8 @@ __global__ __launch_bounds__(64) void k_lang_detect(LangArgs a) {
     const float *l = a.logits + (size_t)b * a.V + a.first;
     const bool h0 = lane < a.n_lang, h1 = lane + 64 < a.n_lang;
     const float v0 = h0 ? l[lane] : -INFINITY, v1 = h1 ? l[lane + 64] : -INFINITY;
-    unsigned long long k = h0 ? ts_key(v0, lane) : 0ull;
-    if (h1) k = u64max(k, ts_key(v1, lane + 64));
+    unsigned long long k = h0 ? pick_key(v0, lane) : 0ull;
+    if (h1) k = u64max(k, pick_key(v1, lane + 64));
     k = wave_max_u64(k);
     const float mx = wave_max(fmaxf(v0, v1));
     const double e0 = h0 ? exp((double)v0 - (double)mx) : 0.0, e1 = h1 ? exp((double)v1 - (double)mx) : 0.0;
@@ -2762,7 +2696,7 @@ __global__ __launch_bounds__(64) void k_lang_detect(LangArgs a) {
     float *pr = a.probs + (size_t)clip * a.n_lang;
     if (h0) pr[lane] = (float)(e0 / Z);
     if (h1) pr[lane + 64] = (float)(e1 / Z);
-    int id = ts_key_id(k);
+    int id = pick_key_id(k);
     if (id < 0 || id >= a.n_lang) id = 0;  // (no finite key: NaN-only logits)
     if (lane == (id & 63)) {
         a.det[clip] = id;
@@ -2822,12 +2756,6 @@ hipError_t launch_dec_embed(hipStream_t s, const DecEmbedArgs &a) {
 // ============================================================================
 // beam search step (config C5; semantics in oracle/wmi_oracle.h)
 // ============================================================================
-// (value desc, id asc) as one unsigned key: larger key = earlier in the order
-__device__ __forceinline__ unsigned long long beam_key(float v, int id) {
-    return ((unsigned long long)ord_f32(v) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)id);
-}
-
-
 // one vocabulary split of one row: split max, sum exp(logit - max) (double)
 // and the split's top-(K+1)
 __global__ __launch_bounds__(256) void k_beam_topk(BeamArgs a) {
@@ -2872,7 +2800,7 @@ __global__ __launch_bounds__(256) void k_beam_topk(BeamArgs a) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int i = lo + tid + 256 * u;
-            const unsigned long long k = (i < hi && !((taken >> u) & 1u)) ? beam_key(v[u], i) : 0ull;
+            const unsigned long long k = (i < hi && !((taken >> u) & 1u)) ? pick_key(v[u], i) : 0ull;
             best = k > best ? k : best;
         }
         best = wave_max_u64(best);
@@ -2881,11 +2809,11 @@ __global__ __launch_bounds__(256) void k_beam_topk(BeamArgs a) {
         unsigned long long k0 = redk[0];
 #pragma unroll
         for (int i = 1; i < 4; ++i) k0 = redk[i] > k0 ? redk[i] : k0;
-        const int id = (int)(0xffffffffu - (uint32_t)(k0 & 0xffffffffull));
+        const int id = pick_key_id(k0);
         const int rel = id - lo;
         if (k0 && (rel & 255) == tid) taken |= 1u << (rel >> 8);
         if (tid == 0) {
-            out->val[r] = k0 ? unord_f32((uint32_t)(k0 >> 32)) : -INFINITY;
+            out->val[r] = k0 ? pick_key_val(k0) : -INFINITY;
             out->id[r] = k0 ? id : -1;
         }
         __syncthreads();
@@ -2896,15 +2824,13 @@ __global__ __launch_bounds__(256) void k_beam_topk(BeamArgs a) {
     }
 }
 
-// candidate i before candidate j in the ranking (score desc, beam asc, rank asc)
-__device__ __forceinline__ bool cand_before(double si, int bi, int ri, double sj, int bj, int rj) {
-    if (si != sj) return si > sj;
-    if (bi != bj) return bi < bj;
-    return ri < rj;
-}
-
 // one workgroup: merge the splits, rank the K x (K+1) candidates, fill the
-// next hypotheses, record finished ones, and re-point the KV history table
+// next hypotheses, record finished ones, and re-point the KV history table.
+// Its own text, with wmi_pick.h's keys and cand_before only: over the shared
+// row merge and back half of k_tsbeam_select / k_rbeam_select (sel_cand in
+// place of sel_tok / sel_score, the guards for a missing candidate, which a
+// row of 16 splits never lacks here) the beam benchmark measured 0.1 - 0.2 %
+// slower, outside the parent's spread (DESIGN.md "Shared pick code").
 __global__ __launch_bounds__(256) void k_beam_select(BeamArgs a) {
     BeamState *bs = a.bs;
     const int pos = a.st->pos;
@@ -2938,7 +2864,7 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamArgs a) {
             key[k] = 0ull;
             if (c < BEAM_NS * TK) {
                 const int id = pp[c / TK].id[c % TK];
-                if (id >= 0) key[k] = beam_key(pp[c / TK].val[c % TK], id);
+                if (id >= 0) key[k] = pick_key(pp[c / TK].val[c % TK], id);
             }
         }
         for (int r = 0; r < TK; ++r) {
@@ -2949,8 +2875,8 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamArgs a) {
             for (int k = 0; k < 3; ++k)
                 if (key[k] == best) key[k] = 0ull;
             if (lane == 0) {
-                cval[b * TK + r] = unord_f32((uint32_t)(best >> 32));
-                cid[b * TK + r] = (int)(0xffffffffu - (uint32_t)(best & 0xffffffffull));
+                cval[b * TK + r] = pick_key_val(best);
+                cid[b * TK + r] = pick_key_id(best);
             }
         }
     }

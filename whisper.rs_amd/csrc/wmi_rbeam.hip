@@ -5,29 +5,18 @@
 // A translation unit of its own, as wmi_tsbeam.hip and wmi_rules.hip: its
 // code object is loaded with the first ruled beam window, so every other path
 // runs on exactly the code objects it ran on before these kernels existed.
-// The ordering helpers restate wmi_tsbeam.hip's beam_key and cand_before, the
-// mask scalars k_ts_sample_r's (wmi_rules.hip).
+// The keys, the split rounds, the row merge and the back half of the select
+// are wmi_pick.h's, shared with wmi_tsbeam.hip (the keys and cand_before with
+// wmi_kernels.hip too); the mask scalars are derived as in k_ts_sample_r
+// (wmi_rules.hip).
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "wmi_device.h"
 #include "wmi_internal.h"
+#include "wmi_pick.h"
 
 namespace wmi {
-
-// (value desc, id asc) as one unsigned key: larger key = earlier in the order
-__device__ __forceinline__ unsigned long long rb_key(float v, int id) {
-    return ((unsigned long long)ord_f32(v) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)id);
-}
-__device__ __forceinline__ int rb_key_id(unsigned long long k) { return (int)(0xffffffffu - (uint32_t)(k & 0xffffffffull)); }
-__device__ __forceinline__ float rb_key_val(unsigned long long k) { return unord_f32((uint32_t)(k >> 32)); }
-
-// candidate i before candidate j in the ranking (score desc, beam asc, rank asc)
-__device__ __forceinline__ bool rb_before(double si, int bi, int ri, double sj, int bj, int rj) {
-    if (si != sj) return si > sj;
-    if (bi != bj) return bi < bj;
-    return ri < rj;
-}
 
 // One vocabulary split of one row.  The row's A' is a predicate over the
 // scalars of its hypothesis' history (tx_lo, lo, hi as k_ts_sample_r derives
@@ -58,16 +47,12 @@ __global__ __launch_bounds__(256) void k_rbeam_part(RBeamArgs ra) {
     __shared__ float redf[4];
     __shared__ double redd[2][4];
     __shared__ unsigned long long redk[2][4];
-    constexpr int U = 16;  // split length <= 4096
+    constexpr int U = SPLIT_U;
     const int chunk = (a.V + BEAM_NS - 1) / BEAM_NS, lo = sp * chunk, hi = min(a.V, lo + chunk);
     const bool has_ts = hi > ra.beg;  // (uniform over the workgroup)
     const float *row = a.logits + (int64_t)b * a.V;
     float v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int i = lo + tid + 256 * u;
-        v[u] = row[i < hi ? i : 0];
-    }
+    split_load(v, row, lo, hi);
     // membership of this thread's ids in A' and in its timestamps, one bit per id
     uint32_t el_a = 0, el_t = 0;
     float m_tx = -INFINITY;
@@ -76,7 +61,7 @@ __global__ __launch_bounds__(256) void k_rbeam_part(RBeamArgs ra) {
     for (int u = 0; u < U; ++u) {
         const int i = lo + tid + 256 * u;
         if (i >= hi) { v[u] = -INFINITY; continue; }
-        if (i >= ra.beg) k_all = u64max(k_all, rb_key(v[u], i));
+        if (i >= ra.beg) k_all = u64max(k_all, pick_key(v[u], i));
         const bool m0 = ((ra.m0[i >> 5] >> (i & 31)) & 1u) != 0;
         const bool ok = !m0 && (i < ra.beg ? i >= tx_lo : i >= ts_lo && i <= ts_hi);
         if (!ok) continue;
@@ -84,7 +69,6 @@ __global__ __launch_bounds__(256) void k_rbeam_part(RBeamArgs ra) {
         if (i >= ra.beg) el_t |= 1u << u;
         else m_tx = fmaxf(m_tx, v[u]);
     }
-    const uint32_t in_a = el_a, in_t = el_t;
     m_tx = wave_max(m_tx);
     if (has_ts) k_all = wave_max_u64(k_all);
     if (lane == 0) { redf[w] = m_tx; redk[0][w] = k_all; }
@@ -92,48 +76,25 @@ __global__ __launch_bounds__(256) void k_rbeam_part(RBeamArgs ra) {
     m_tx = fmaxf(fmaxf(redf[0], redf[1]), fmaxf(redf[2], redf[3]));
     k_all = u64max(u64max(redk[0][0], redk[0][1]), u64max(redk[0][2], redk[0][3]));
     __syncthreads();
-    // the two top-(K+1) lists, one workgroup-wide argmax per rank and list
+    // the two top-(K+1) lists
     RBeamPart *out = ra.rparts + (int64_t)b * BEAM_NS + sp;
-    float m_a = -INFINITY, m_t = -INFINITY;
-    for (int r = 0; r <= a.K; ++r) {
-        unsigned long long ba = 0, bt = 0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const unsigned long long k = rb_key(v[u], lo + tid + 256 * u);
-            if ((el_a >> u) & 1u) ba = u64max(ba, k);
-            if ((el_t >> u) & 1u) bt = u64max(bt, k);
-        }
-        ba = wave_max_u64(ba);
-        if (has_ts) bt = wave_max_u64(bt);
-        if (lane == 0) { redk[0][w] = ba; redk[1][w] = bt; }
-        __syncthreads();
-        ba = u64max(u64max(redk[0][0], redk[0][1]), u64max(redk[0][2], redk[0][3]));
-        bt = u64max(u64max(redk[1][0], redk[1][1]), u64max(redk[1][2], redk[1][3]));
-        const int ia = rb_key_id(ba), qa = ia - lo;
-        const int it = rb_key_id(bt), qt = it - lo;
-        if (ba && (qa & 255) == tid) el_a &= ~(1u << (qa >> 8));
-        if (bt && (qt & 255) == tid) el_t &= ~(1u << (qt >> 8));
-        const float va = ba ? rb_key_val(ba) : -INFINITY;
-        const float vt = bt ? rb_key_val(bt) : -INFINITY;
-        if (r == 0) { m_a = va; m_t = vt; }
-        if (tid == 0) {
-            out->ap_val[r] = va;
-            out->ap_id[r] = ba ? ia : -1;
-            out->ts_val[r] = vt;
-            out->ts_id[r] = bt ? it : -1;
-        }
-        __syncthreads();
-    }
+    float m_a, m_t;
+    split_rounds(v, lo, a.K, el_a, el_t, true, has_ts, redk, m_a, m_t, [&](int r, float va, int ia, float vt, int it) {
+        out->ap_val[r] = va;
+        out->ap_id[r] = ia;
+        out->ts_val[r] = vt;
+        out->ts_id[r] = it;
+    });
     // the sets' sums, each against its own maximum (one exp where they coincide)
     double s_a = 0.0, s_t = 0.0;
     if (m_a > -INFINITY) {
         const bool do_t = has_ts && m_t > -INFINITY;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            if (!((in_a >> u) & 1u)) continue;
+            if (!((el_a >> u) & 1u)) continue;
             const double l = (double)v[u], e = exp(l - (double)m_a);
             s_a += e;
-            if (do_t && ((in_t >> u) & 1u)) s_t += m_t == m_a ? e : exp(l - (double)m_t);
+            if (do_t && ((el_t >> u) & 1u)) s_t += m_t == m_a ? e : exp(l - (double)m_t);
         }
     }
     s_a = wave_sum(s_a);
@@ -151,42 +112,38 @@ __global__ __launch_bounds__(256) void k_rbeam_part(RBeamArgs ra) {
 
 // One workgroup, as k_tsbeam_select: per active row the splits merged into
 // the softmax quantities over A' (S', sum_ts, p_tx), with them the row's set,
-// its log-sum-exp and merged top-(K+1); then the ranking, walk and KV history
-// re-pointing, a TsRec per new slot and per finished hypothesis (under the
-// softmax over A' of the row that produced the token), and each new slot's
-// history: its parent's advanced by the id it took.  Every parent's history is
-// read before the first barrier and written after the last, since slots and
-// parents alias.
+// its log-sum-exp and merged top-(K+1) (beam_row_merge); then the ranking,
+// walk and KV history re-pointing (beam_select_tail), a TsRec per new slot and
+// per finished hypothesis (under the softmax over A' of the row that produced
+// the token), and each new slot's history: its parent's advanced by the id it
+// took.  Every parent's history is read before the first barrier and written
+// after the last, since slots and parents alias.
 __global__ __launch_bounds__(256) void k_rbeam_select(RBeamArgs ra) {
     const BeamArgs &a = ra.b;
     BeamState *bs = a.bs;
     const int pos = a.st->pos;
     if (pos < a.feed_len || bs->done) return;
-    const int t = pos - a.feed_len, K = a.K, TK = K + 1;
+    const int t = pos - a.feed_len, TK = a.K + 1;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    constexpr int NC = BEAM_MAX * BEAM_TK;
-    __shared__ double lse[BEAM_MAX], row_m[BEAM_MAX], row_z[BEAM_MAX], row_sts[BEAM_MAX];
-    __shared__ float row_pt[BEAM_MAX];
-    __shared__ int row_tid[BEAM_MAX];
-    __shared__ RuleHist h_old[BEAM_MAX];
-    __shared__ float cval[NC];
-    __shared__ int cid[NC];
-    __shared__ double cscore[NC];
-    __shared__ int order[NC];
-    __shared__ int sel_parent[BEAM_MAX], sel_cand[BEAM_MAX], n_new_s;
-    __shared__ int32_t src_old[BEAM_MAX][512];
+    struct Lds : BeamSelLds {  // (one block: apart, each array is padded to 16 bytes)
+        double row_m[BEAM_MAX], row_z[BEAM_MAX], row_sts[BEAM_MAX];
+        float row_pt[BEAM_MAX];
+        int row_tid[BEAM_MAX];
+        RuleHist h_old[BEAM_MAX];
+    };
+    __shared__ Lds sl;
     const int na_old = bs->n_active;
-    if (tid < BEAM_MAX) h_old[tid] = ra.hist[tid];
+    if (tid < BEAM_MAX) sl.h_old[tid] = ra.hist[tid];  // (every parent's history is read ahead of the first barrier)
     auto record = [&](int c) {  // candidate c as sampled from its row
         const int p = c / TK;
-        const double pd = exp((double)cval[c] - row_m[p]) / row_z[p];
-        const bool ts = cid[c] >= ra.beg;
+        const double pd = exp((double)sl.cval[c] - sl.row_m[p]) / sl.row_z[p];
+        const bool ts = sl.cid[c] >= ra.beg;
         TsRec r;
-        r.id = cid[c];
-        r.tid = ts ? cid[c] : row_tid[p];
+        r.id = sl.cid[c];
+        r.tid = ts ? sl.cid[c] : sl.row_tid[p];
         r.p = (float)pd;
-        r.pt = ts ? (float)(pd / (row_sts[p] + 1e-10)) : row_pt[p];
-        r.ptsum = (float)row_sts[p];
+        r.pt = ts ? (float)(pd / (sl.row_sts[p] + 1e-10)) : sl.row_pt[p];
+        r.ptsum = (float)sl.row_sts[p];
         r.pad = 0;
         return r;
     };
@@ -202,117 +159,45 @@ __global__ __launch_bounds__(256) void k_rbeam_select(RBeamArgs ra) {
         const float Mts = wave_max(pts);
         const double TS = wave_sum(pts > -INFINITY ? pp[lane].sum_ts * exp((double)pts - (double)Mts) : 0.0);
         const float Mtx = wave_max(in ? pp[lane].m_tx : -INFINITY);
-        const unsigned long long kts = wave_max_u64(hts ? rb_key(pts, pp[lane].ts_id[0]) : 0ull);
+        const unsigned long long kts = wave_max_u64(hts ? pick_key(pts, pp[lane].ts_id[0]) : 0ull);
         const unsigned long long kall = wave_max_u64(in ? pp[lane].k_all : 0ull);
         const double p_maxts = kts ? exp((double)Mts - (double)M) / Z : 0.0;
         const double sum_ts = kts ? TS * p_maxts : 0.0;
         const double p_tx = Mtx > -INFINITY ? exp((double)Mtx - (double)M) / Z : 0.0;
         const bool ts_set = sum_ts > p_tx;  // (the same on every lane)
         if (lane == 0) {
-            lse[b] = ts_set ? (double)Mts + log(TS) : (double)M + log(Z);
-            row_m[b] = (double)M;
-            row_z[b] = Z;
-            row_sts[b] = sum_ts;
+            sl.lse[b] = ts_set ? (double)Mts + log(TS) : (double)M + log(Z);
+            sl.row_m[b] = (double)M;
+            sl.row_z[b] = Z;
+            sl.row_sts[b] = sum_ts;
             // a text id's tid: the likeliest timestamp of A', else (A' holds none) of all ids >= beg with pt 0
-            row_tid[b] = kts ? rb_key_id(kts) : kall ? rb_key_id(kall) : -1;
-            row_pt[b] = kts ? (float)(p_maxts / (sum_ts + 1e-10)) : 0.0f;
+            sl.row_tid[b] = kts ? pick_key_id(kts) : kall ? pick_key_id(kall) : -1;
+            sl.row_pt[b] = kts ? (float)(p_maxts / (sum_ts + 1e-10)) : 0.0f;
         }
-        unsigned long long key[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int c = lane + 64 * k;
-            key[k] = 0ull;
-            if (c < BEAM_NS * TK) {
-                const RBeamPart &q = pp[c / TK];
-                const int id = ts_set ? q.ts_id[c % TK] : q.ap_id[c % TK];
-                if (id >= 0) key[k] = rb_key(ts_set ? q.ts_val[c % TK] : q.ap_val[c % TK], id);
-            }
-        }
-        for (int r = 0; r < TK; ++r) {
-            unsigned long long best = key[0] > key[1] ? key[0] : key[1];
-            best = key[2] > best ? key[2] : best;
-            best = wave_max_u64(best);
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                if (key[k] == best) key[k] = 0ull;
-            if (lane == 0) {  // (a set with fewer than K + 1 ids: no candidate, ranked last)
-                cval[b * TK + r] = best ? rb_key_val(best) : -INFINITY;
-                cid[b * TK + r] = best ? rb_key_id(best) : -1;
-            }
-        }
+        beam_row_merge(TK, [&](int sp, int r, float &val, int &id) {
+            const RBeamPart &q = pp[sp];
+            id = ts_set ? q.ts_id[r] : q.ap_id[r];
+            val = ts_set ? q.ts_val[r] : q.ap_val[r];
+        }, sl.cval + b * TK, sl.cid + b * TK);
     }
-    __syncthreads();
-    // 2. scores and ranking
-    const int nc = na_old * TK;
-    if (tid < nc) cscore[tid] = cid[tid] >= 0 ? bs->score[tid / TK] + ((double)cval[tid] - lse[tid / TK]) : -INFINITY;
-    __syncthreads();
-    if (tid < nc) {
-        int rank = 0;
-        const double si = cscore[tid];
-        const int bi = tid / TK, ri = tid % TK;
-        for (int j = 0; j < nc; ++j)
-            if (rb_before(cscore[j], j / TK, j % TK, si, bi, ri)) ++rank;
-        order[rank] = tid;
-    }
-    // history table of the parents, positions < pos - 1
-    for (int i = tid; i < na_old * (pos - 1); i += 256) {
-        const int r = i / (pos - 1), j = i - r * (pos - 1);
-        src_old[r][j] = a.kv_src[r * a.tctx + j];
-    }
-    __syncthreads();
-    // 3. walk the ranking
-    if (tid == 0) {
-        int na = 0, nf = bs->n_fin;
-        for (int k = 0; k < nc && na < K; ++k) {
-            const int c = order[k];
-            if (cid[c] < 0) continue;
-            if (cid[c] == a.eot) {
-                if (nf < K) {
-                    bs->fin_t[nf] = t;
-                    bs->fin_beam[nf] = c / TK;
-                    bs->fin_score[nf] = cscore[c];
-                    ra.fin_rec[nf] = record(c);
-                    ++nf;
-                }
-                continue;
-            }
-            sel_parent[na] = c / TK;
-            sel_cand[na] = c;
-            ++na;
-        }
-        n_new_s = na;
-        bs->n_fin = nf;
-        bs->n_active = na;
-        bs->n_steps = t + 1;
-        if (nf >= K || t + 1 >= a.max_tokens) bs->done = 1;
-    }
-    __syncthreads();
-    // 4. next hypotheses: scores, fed tokens, back-pointers, records, histories, KV history table
-    const int nn = n_new_s;
-    if (tid < BEAM_MAX) {
-        RuleHist hn{0, 0, 0, 0};
-        if (tid < nn) {
-            const int c = sel_cand[tid], id = cid[c];
-            const RuleHist hp = h_old[sel_parent[tid]];
-            bs->score[tid] = cscore[c];
-            bs->tok[tid] = id;
-            a.hist_parent[t * BEAM_MAX + tid] = sel_parent[tid];
-            a.hist_tok[t * BEAM_MAX + tid] = id;
-            ra.hist_rec[t * BEAM_MAX + tid] = record(c);
-            hn.last = id >= ra.beg;
-            hn.pen = t >= 1 ? hp.last : 0;
-            hn.lts1 = id >= ra.beg ? id + 1 : t >= 1 ? hp.lts1 : 0;
-        }
-        ra.hist[tid] = hn;
-        int32_t *tab = ra.hist_tab + ((int64_t)t * BEAM_MAX + tid) * 3;
+    // 2 - 4, with the records and the histories: a slot's is written after the
+    // tail's last barrier (the slot hook and the lines below it), from h_old
+    auto put_hist = [&](int s, RuleHist hn) {
+        ra.hist[s] = hn;
+        int32_t *tab = ra.hist_tab + ((int64_t)t * BEAM_MAX + s) * 3;
         tab[0] = hn.last;
         tab[1] = hn.pen;
         tab[2] = hn.lts1;
-    }
-    for (int i = tid; i < nn * pos; i += 256) {
-        const int sl = i / pos, j = i - sl * pos, p = sel_parent[sl];
-        a.kv_src[sl * a.tctx + j] = j < pos - 1 ? src_old[p][j] : p;
-    }
+    };
+    const int nn = beam_select_tail(a, sl, pos, na_old, [&](int nf, int c) { ra.fin_rec[nf] = record(c); },
+                                    [&](int s, int p, int c) {
+                                        const int id = sl.cid[c];
+                                        const RuleHist hp = sl.h_old[p];
+                                        ra.hist_rec[t * BEAM_MAX + s] = record(c);
+                                        put_hist(s, RuleHist{id >= ra.beg, t >= 1 ? hp.last : 0,
+                                                             id >= ra.beg ? id + 1 : t >= 1 ? hp.lts1 : 0, 0});
+                                    });
+    if (tid >= nn && tid < BEAM_MAX) put_hist(tid, RuleHist{0, 0, 0, 0});  // the slots left empty
 }
 
 hipError_t launch_rbeam_step(hipStream_t s, const RBeamArgs &a) {

@@ -5,28 +5,16 @@
 // A translation unit of its own, as wmi_sample.hip and wmi_tsbeam.hip: its
 // code object is loaded with the first ruled window, so a context whose rules
 // are off runs on exactly the code objects it ran on before this kernel
-// existed.  The key helpers and sm64 restate wmi_sample.hip's.
+// existed.  The keys, the prologue and the draw it has in common with
+// k_ts_sample_t are wmi_pick.h's.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "wmi_device.h"
 #include "wmi_internal.h"
+#include "wmi_pick.h"
 
 namespace wmi {
-
-__device__ __forceinline__ unsigned long long ts_key(float v, int id) {
-    return ((unsigned long long)ord_f32(v) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)id);
-}
-__device__ __forceinline__ int ts_key_id(unsigned long long k) { return (int)(0xffffffffu - (uint32_t)(k & 0xffffffffu)); }
-__device__ __forceinline__ float ts_key_val(unsigned long long k) { return unord_f32((uint32_t)(k >> 32)); }
-
-__device__ __forceinline__ unsigned long long sm64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    unsigned long long z = x;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // the bits of the ids base .. base + 31 that lie in [a, b]
 __device__ __forceinline__ uint32_t range_bits(int base, int a, int b) {
@@ -53,15 +41,10 @@ __device__ __forceinline__ uint32_t range_bits(int base, int a, int b) {
 //           is located by wave 0 (groups of 16 tiles, tile, id)
 __global__ __launch_bounds__(1024) void k_ts_sample_r(TsRuleArgs ra) {
     const TsArgs &a = ra.s.t;
-    const int pos = a.st->pos;
-    if (pos < a.feed_len) return;  // still feeding the prompt
-    const int t = pos - a.feed_len;
+    int t;
+    if (!samp_begin(a, t)) return;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int b = blockIdx.x;
-    if (a.done[b]) {  // (uniform over the workgroup; set by a previous launch)
-        if (tid == 0) a.tok_out[b] = a.eot;
-        return;
-    }
     const float *lg = a.logits + (size_t)b * a.V;
     // the row's history and the scalars of the mask
     const RuleHist h = ra.hist[b];
@@ -79,16 +62,15 @@ __global__ __launch_bounds__(1024) void k_ts_sample_r(TsRuleArgs ra) {
     __syncthreads();
     auto in_ap = [&](int i) { return ((s_ap[i >> 5] >> (i & 31)) & 1u) != 0; };
     __shared__ float smax[16];
-    __shared__ double ssum[16], sts[16], sse[16];
+    __shared__ double ssum[16], sts[16];
     __shared__ unsigned long long sk[3][16];
-    __shared__ double tsum[1024], gsum[64], wl[64], c_tile;
-    __shared__ int j_tile;
+    __shared__ DrawLds dl;
     float mx = -INFINITY;
     unsigned long long k_ts = 0, k_tx = 0, k_tsall = 0;
     for (int i = tid; i < a.V; i += 1024) {
         const float l = lg[i];
         mx = fmaxf(mx, l);
-        const unsigned long long k = ts_key(l, i);
+        const unsigned long long k = pick_key(l, i);
         if (i >= a.beg) k_tsall = k > k_tsall ? k : k_tsall;
         if (in_ap(i)) {
             if (i >= a.beg) k_ts = k > k_ts ? k : k_ts;
@@ -100,7 +82,7 @@ __global__ __launch_bounds__(1024) void k_ts_sample_r(TsRuleArgs ra) {
     k_tx = wave_max_u64(k_tx);
     k_tsall = wave_max_u64(k_tsall);
     if (lane == 0) { smax[w] = mx; sk[0][w] = k_ts; sk[1][w] = k_tx; sk[2][w] = k_tsall; }
-    tsum[tid] = 0.0;
+    dl.tsum[tid] = 0.0;  // (ahead of pass 1's barrier)
     __syncthreads();
     mx = smax[0];
     k_ts = sk[0][0]; k_tx = sk[1][0]; k_tsall = sk[2][0];
@@ -112,7 +94,7 @@ __global__ __launch_bounds__(1024) void k_ts_sample_r(TsRuleArgs ra) {
     }
     // (A' is never empty: EOT and the timestamps are in no suppress list)
     const unsigned long long k_ap = k_ts > k_tx ? k_ts : k_tx;
-    const float m_p = ts_key_val(k_ap);
+    const float m_p = pick_key_val(k_ap);
     double s = 0.0, st = 0.0;
     for (int i = tid; i < a.V; i += 1024) {
         if (!in_ap(i)) continue;
@@ -127,12 +109,11 @@ __global__ __launch_bounds__(1024) void k_ts_sample_r(TsRuleArgs ra) {
     double Z = 0.0, TS = 0.0;
     for (int i = 0; i < 16; ++i) { Z += ssum[i]; TS += sts[i]; }
     const double sum_ts = TS / Z;
-    const double p_maxtx = k_tx ? exp((double)ts_key_val(k_tx) - (double)m_p) / Z : 0.0;
+    const double p_maxtx = k_tx ? exp((double)pick_key_val(k_tx) - (double)m_p) / Z : 0.0;
     const bool ts_only = sum_ts > p_maxtx;
     const unsigned long long k_a = ts_only ? k_ts : k_ap;
-    const float m_a = ts_key_val(k_a);
+    const float m_a = pick_key_val(k_a);
     const float T = ra.s.rows[b].T;
-    const bool draw = T > 0.0f;
     auto in_a = [&](int i) { return (!ts_only || i >= a.beg) && in_ap(i); };
     double Zu = 0.0;
     if (t == 0) {  // the unmasked softmax's sum, for p_nosp
@@ -144,89 +125,21 @@ __global__ __launch_bounds__(1024) void k_ts_sample_r(TsRuleArgs ra) {
         __syncthreads();
         for (int i = 0; i < 16; ++i) Zu += ssum[i];
     }
-    // pass 3: tiles of 64 consecutive ids
-    const int nt = (a.V + 63) >> 6;
-    double se = 0.0;
-    // (one exp per loop, as in k_ts_sample_t: both in one body spill)
-    for (int j = w; j < nt; j += 16) {
-        const int i = j * 64 + lane;
-        if (i < a.V && in_a(i)) se += exp((double)lg[i] - (double)m_a);
-    }
-    if (draw)
-        for (int j = w; j < nt; j += 16) {
-            const int i = j * 64 + lane;
-            const bool in = i < a.V && in_a(i);
-            const double wt = wave_sum(in ? exp(((double)lg[i] - (double)m_a) / (double)T) : 0.0);
-            if (lane == 0) tsum[j] = wt;
-        }
-    se = wave_sum(se);
-    if (lane == 0) sse[w] = se;
-    __syncthreads();
-    int id = ts_key_id(k_a);
-    double target = 0.0;
-    if (draw) {
-        if (w == 0) {
-            double g = 0.0;
-            for (int k = 0; k < 16; ++k) g += tsum[16 * lane + k];
-            gsum[lane] = g;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double Q = 0.0;
+    tile_sums(dl, lg, a.V, in_a, m_a, T);
+    int id = pick_key_id(k_a);
+    if (T > 0.0f) {
+        const double target = draw_tile(dl, ra.s.rows[b].key + (unsigned long long)t, [&](int &J, double &c) {
+            // (rounding left no group past the target: the last tile with any weight, its last such id)
             #pragma unroll 1
-            for (int g = 0; g < 64; ++g) Q += gsum[g];
-            const double u = (double)(sm64(ra.s.rows[b].key + (unsigned long long)t) >> 11) * 0x1.0p-53;
-            target = u * Q;
-            double c = 0.0;
-            int G = -1;
-            #pragma unroll 1
-            for (int g = 0; g < 64; ++g) {
-                if (c + gsum[g] > target) { G = g; break; }
-                c += gsum[g];
-            }
-            int J = -1;
-            double cj = c;
-            if (G >= 0) {
-                // (rounding may leave no tile of the group past the target: its last tile with any weight)
-                #pragma unroll 1
-                for (int k = 0; k < 16; ++k) {
-                    const int j = 16 * G + k;
-                    if (tsum[j] > 0.0) { J = j; cj = c; }
-                    if (c + tsum[j] > target) break;
-                    c += tsum[j];
-                }
-            } else {
-                // (rounding left no group past the target: the last tile with any weight, its last such id)
-                #pragma unroll 1
-                for (int j = 0; j < 1024; ++j)
-                    if (tsum[j] > 0.0) J = j;
-                cj = -INFINITY;
-            }
-            j_tile = J;
-            c_tile = cj;
-        }
-        __syncthreads();
-        const int J = j_tile;  // (uniform; >= 0: A holds m_A's id, whose weight is 1)
-        if (J >= 0 && w == 0) {
-            const int i = J * 64 + lane;
-            wl[lane] = i < a.V && in_a(i) ? exp(((double)lg[i] - (double)m_a) / (double)T) : 0.0;
-        }
-        __syncthreads();
-        if (tid == 0 && J >= 0) {
-            double c = c_tile;
-            #pragma unroll 1
-            for (int k = 0; k < 64; ++k) {
-                if (wl[k] > 0.0) id = J * 64 + k;
-                if (c + wl[k] > target) break;
-                c += wl[k];
-            }
-        }
+            for (int j = 0; j < 1024; ++j)
+                if (dl.tsum[j] > 0.0) J = j;
+            c = -INFINITY;
+        });
+        // (a tile there is: A holds m_A's id, whose weight is 1; the argmax stands in for none)
+        id = draw_id(dl, target, lg, a.V, in_a, m_a, T, id);
     }
     if (tid != 0) return;
-    double SE = 0.0;
-    for (int i = 0; i < 16; ++i) SE += sse[i];
-    a.tok_out[b] = id;
-    if (id == a.eot) a.done[b] = 1;
+    samp_feed(a, id);
     RuleHist hn;
     hn.last = id >= a.beg;
     hn.pen = t >= 1 ? h.last : 0;
@@ -237,7 +150,7 @@ __global__ __launch_bounds__(1024) void k_ts_sample_r(TsRuleArgs ra) {
     if (t < a.max_rec) {
         // tid: the id itself if a timestamp, else the best timestamp of A', else (A' holds none) of all
         const bool tid_in = id >= a.beg || k_ts != 0;
-        const int id_t = id >= a.beg ? id : ts_key_id(k_ts ? k_ts : k_tsall);
+        const int id_t = id >= a.beg ? id : pick_key_id(k_ts ? k_ts : k_tsall);
         TsRec r;
         r.id = id;
         r.tid = id_t;
@@ -246,7 +159,7 @@ __global__ __launch_bounds__(1024) void k_ts_sample_r(TsRuleArgs ra) {
         r.ptsum = (float)sum_ts;
         r.pad = 0;
         a.rec[(size_t)b * a.max_rec + t] = r;
-        ra.s.plog[(size_t)b * a.max_rec + t] = (float)((double)lg[id] - ((double)m_a + log(SE)));
+        ra.s.plog[(size_t)b * a.max_rec + t] = draw_plog(dl, lg[id], m_a);
     }
 }
 

@@ -5,27 +5,17 @@
 // timestamped beam window, so a process that never asks for one runs on
 // exactly the code objects it ran on before these kernels existed (the
 // greedy, beam and timestamp paths of wmi_kernels.hip are byte for byte what
-// they were).  The ordering helpers restate wmi_kernels.hip's beam_key and
-// cand_before.
+// they were).  The keys, the split rounds, the row merge and the back half of
+// the select are wmi_pick.h's, shared with wmi_rbeam.hip (the keys and
+// cand_before with wmi_kernels.hip too).
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "wmi_device.h"
 #include "wmi_internal.h"
+#include "wmi_pick.h"
 
 namespace wmi {
-
-// (value desc, id asc) as one unsigned key: larger key = earlier in the order
-__device__ __forceinline__ unsigned long long beam_key(float v, int id) {
-    return ((unsigned long long)ord_f32(v) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)id);
-}
-
-// candidate i before candidate j in the ranking (score desc, beam asc, rank asc)
-__device__ __forceinline__ bool cand_before(double si, int bi, int ri, double sj, int bj, int rj) {
-    if (si != sj) return si > sj;
-    if (bi != bj) return bi < bj;
-    return ri < rj;
-}
 
 // ============================================================================
 // beam search step under the timestamp rule (k_ts_sample's rule per hypothesis
@@ -46,16 +36,12 @@ __global__ __launch_bounds__(256) void k_tsbeam_part(TsBeamArgs ta) {
     __shared__ float redf[2][4];
     __shared__ double redd[4][4];
     __shared__ unsigned long long redk[2][4];
-    constexpr int U = 16;  // split length <= 4096
+    constexpr int U = SPLIT_U;
     const int chunk = (a.V + BEAM_NS - 1) / BEAM_NS, lo = sp * chunk, hi = min(a.V, lo + chunk);
     const bool has_ts = hi > ta.beg;  // (uniform over the workgroup)
     const float *row = a.logits + (int64_t)b * a.V;
     float v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int i = lo + tid + 256 * u;
-        v[u] = row[i < hi ? i : 0];
-    }
+    split_load(v, row, lo, hi);
     // eligibility of this thread's ids for the two lists, one bit per id
     uint32_t el_a = 0, el_t = 0;
     float m_all = -INFINITY, m_tx = -INFINITY;
@@ -66,7 +52,7 @@ __global__ __launch_bounds__(256) void k_tsbeam_part(TsBeamArgs ta) {
         if (i >= hi) { v[u] = -INFINITY; continue; }
         m_all = fmaxf(m_all, v[u]);
         if (i < ta.beg) m_tx = fmaxf(m_tx, v[u]);
-        else k_ts = u64max(k_ts, beam_key(v[u], i));
+        else k_ts = u64max(k_ts, pick_key(v[u], i));
         if (!first && i != ta.sot && i != ta.solm && i != ta.not_) el_a |= 1u << u;
         if (first ? i > ta.beg : i >= ta.beg) el_t |= 1u << u;
     }
@@ -78,40 +64,17 @@ __global__ __launch_bounds__(256) void k_tsbeam_part(TsBeamArgs ta) {
     m_all = fmaxf(fmaxf(redf[0][0], redf[0][1]), fmaxf(redf[0][2], redf[0][3]));
     m_tx = fmaxf(fmaxf(redf[1][0], redf[1][1]), fmaxf(redf[1][2], redf[1][3]));
     k_ts = u64max(u64max(redk[0][0], redk[0][1]), u64max(redk[0][2], redk[0][3]));
-    const float m_ts = k_ts ? unord_f32((uint32_t)(k_ts >> 32)) : -INFINITY;
+    const float m_ts = k_ts ? pick_key_val(k_ts) : -INFINITY;
     __syncthreads();
-    // the two top-(K+1) lists, one workgroup-wide argmax per rank and list
+    // the two top-(K+1) lists (at the first token the first list's set is empty: its reduction is skipped)
     TsBeamPart *out = ta.tparts + (int64_t)b * BEAM_NS + sp;
-    float m_a = -INFINITY, m_tl = -INFINITY;
-    for (int r = 0; r <= a.K; ++r) {
-        unsigned long long ba = 0, bt = 0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const unsigned long long k = beam_key(v[u], lo + tid + 256 * u);
-            if ((el_a >> u) & 1u) ba = u64max(ba, k);
-            if ((el_t >> u) & 1u) bt = u64max(bt, k);
-        }
-        if (!first) ba = wave_max_u64(ba);
-        if (has_ts) bt = wave_max_u64(bt);
-        if (lane == 0) { redk[0][w] = ba; redk[1][w] = bt; }
-        __syncthreads();
-        ba = u64max(u64max(redk[0][0], redk[0][1]), u64max(redk[0][2], redk[0][3]));
-        bt = u64max(u64max(redk[1][0], redk[1][1]), u64max(redk[1][2], redk[1][3]));
-        const int ia = (int)(0xffffffffu - (uint32_t)(ba & 0xffffffffull)), ra = ia - lo;
-        const int it = (int)(0xffffffffu - (uint32_t)(bt & 0xffffffffull)), rt = it - lo;
-        if (ba && (ra & 255) == tid) el_a &= ~(1u << (ra >> 8));
-        if (bt && (rt & 255) == tid) el_t &= ~(1u << (rt >> 8));
-        const float va = ba ? unord_f32((uint32_t)(ba >> 32)) : -INFINITY;
-        const float vt = bt ? unord_f32((uint32_t)(bt >> 32)) : -INFINITY;
-        if (r == 0) { m_a = va; m_tl = vt; }
-        if (tid == 0) {
-            out->a_val[r] = va;
-            out->a_id[r] = ba ? ia : -1;
-            out->ts_val[r] = vt;
-            out->ts_id[r] = bt ? it : -1;
-        }
-        __syncthreads();
-    }
+    float m_a, m_tl;
+    split_rounds(v, lo, a.K, el_a, el_t, !first, has_ts, redk, m_a, m_tl, [&](int r, float va, int ia, float vt, int it) {
+        out->a_val[r] = va;
+        out->a_id[r] = ia;
+        out->ts_val[r] = vt;
+        out->ts_id[r] = it;
+    });
     // the sets' sums, each against its own maximum (one exp where they coincide)
     double s_all = 0.0, s_a = 0.0, s_ts = 0.0, s_tl = 0.0;
     const bool do_a = !first && m_a > -INFINITY, do_ts = has_ts && m_ts > -INFINITY;
@@ -140,7 +103,7 @@ __global__ __launch_bounds__(256) void k_tsbeam_part(TsBeamArgs ta) {
         out->m_all = m_all;
         out->m_tx = m_tx;
         out->m_ts = m_ts;
-        out->id_ts = k_ts ? (int)(0xffffffffu - (uint32_t)(k_ts & 0xffffffffull)) : -1;
+        out->id_ts = k_ts ? pick_key_id(k_ts) : -1;
         out->pad = 0;
         out->sum_all = ((redd[0][0] + redd[0][1]) + redd[0][2]) + redd[0][3];
         out->sum_a = ((redd[1][0] + redd[1][1]) + redd[1][2]) + redd[1][3];
@@ -153,35 +116,32 @@ __global__ __launch_bounds__(256) void k_tsbeam_part(TsBeamArgs ta) {
 
 // One workgroup: per active row the unmasked softmax quantities (Z, sum_ts,
 // p_tx, id_ts) and with them the row's allowed set; the log-sum-exp and the
-// merged top-(K+1) of that set; then k_beam_select's ranking, walk and KV
-// history re-pointing, plus a TsRec per new slot and per finished hypothesis
-// (under the unmasked softmax of the row that produced the token).
+// merged top-(K+1) of that set (beam_row_merge); then k_beam_select's ranking,
+// walk and KV history re-pointing (beam_select_tail), with a TsRec per new slot
+// and per finished hypothesis (under the unmasked softmax of the row that
+// produced the token).
 __global__ __launch_bounds__(256) void k_tsbeam_select(TsBeamArgs ta) {
     const BeamArgs &a = ta.b;
     BeamState *bs = a.bs;
     const int pos = a.st->pos;
     if (pos < a.feed_len || bs->done) return;
-    const int t = pos - a.feed_len, K = a.K, TK = K + 1;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    constexpr int NC = BEAM_MAX * BEAM_TK;
-    __shared__ double lse[BEAM_MAX], row_m[BEAM_MAX], row_z[BEAM_MAX];
-    __shared__ float row_pt[BEAM_MAX], row_ptsum[BEAM_MAX];
-    __shared__ int row_tid[BEAM_MAX];
-    __shared__ float cval[NC];
-    __shared__ int cid[NC];
-    __shared__ double cscore[NC];
-    __shared__ int order[NC];
-    __shared__ int sel_parent[BEAM_MAX], sel_cand[BEAM_MAX], n_new_s;
-    __shared__ int32_t src_old[BEAM_MAX][512];
+    const int t = pos - a.feed_len, TK = a.K + 1;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    struct Lds : BeamSelLds {  // (one block: apart, each array is padded to 16 bytes)
+        double row_m[BEAM_MAX], row_z[BEAM_MAX];
+        float row_pt[BEAM_MAX], row_ptsum[BEAM_MAX];
+        int row_tid[BEAM_MAX];
+    };
+    __shared__ Lds sl;
     const int na_old = bs->n_active;
     auto record = [&](int c) {  // candidate c as sampled from its row
         const int p = c / TK;
         TsRec r;
-        r.id = cid[c];
-        r.tid = row_tid[p];
-        r.p = (float)(exp((double)cval[c] - row_m[p]) / row_z[p]);
-        r.pt = row_pt[p];
-        r.ptsum = row_ptsum[p];
+        r.id = sl.cid[c];
+        r.tid = sl.row_tid[p];
+        r.p = (float)(exp((double)sl.cval[c] - sl.row_m[p]) / sl.row_z[p]);
+        r.pt = sl.row_pt[p];
+        r.ptsum = sl.row_ptsum[p];
         r.pad = 0;
         return r;
     };
@@ -197,7 +157,7 @@ __global__ __launch_bounds__(256) void k_tsbeam_select(TsBeamArgs ta) {
         const double TS = wave_sum(pts > -INFINITY ? pp[lane].sum_ts * exp((double)pts - (double)Mts) : 0.0);
         const float Mtx = wave_max(in ? pp[lane].m_tx : -INFINITY);
         const unsigned long long kts =
-            wave_max_u64(in && pp[lane].id_ts >= 0 ? beam_key(pts, pp[lane].id_ts) : 0ull);
+            wave_max_u64(in && pp[lane].id_ts >= 0 ? pick_key(pts, pp[lane].id_ts) : 0ull);
         const double p_maxts = exp((double)Mts - (double)M) / Z;
         const double sum_ts = TS * p_maxts;
         const double p_tx = Mtx > -INFINITY ? exp((double)Mtx - (double)M) / Z : 0.0;
@@ -207,97 +167,22 @@ __global__ __launch_bounds__(256) void k_tsbeam_select(TsBeamArgs ta) {
         const float SM = wave_max(sm);
         const double SS = wave_sum(sm > -INFINITY ? ss * exp((double)sm - (double)SM) : 0.0);
         if (lane == 0) {
-            lse[b] = (double)SM + log(SS);
-            row_m[b] = (double)M;
-            row_z[b] = Z;
-            row_tid[b] = kts ? (int)(0xffffffffu - (uint32_t)(kts & 0xffffffffull)) : -1;
-            row_pt[b] = (float)(p_maxts / (sum_ts + 1e-10));
-            row_ptsum[b] = (float)sum_ts;
+            sl.lse[b] = (double)SM + log(SS);
+            sl.row_m[b] = (double)M;
+            sl.row_z[b] = Z;
+            sl.row_tid[b] = kts ? pick_key_id(kts) : -1;
+            sl.row_pt[b] = (float)(p_maxts / (sum_ts + 1e-10));
+            sl.row_ptsum[b] = (float)sum_ts;
         }
-        unsigned long long key[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int c = lane + 64 * k;
-            key[k] = 0ull;
-            if (c < BEAM_NS * TK) {
-                const TsBeamPart &q = pp[c / TK];
-                const int id = ts_set ? q.ts_id[c % TK] : q.a_id[c % TK];
-                if (id >= 0) key[k] = beam_key(ts_set ? q.ts_val[c % TK] : q.a_val[c % TK], id);
-            }
-        }
-        for (int r = 0; r < TK; ++r) {
-            unsigned long long best = key[0] > key[1] ? key[0] : key[1];
-            best = key[2] > best ? key[2] : best;
-            best = wave_max_u64(best);
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                if (key[k] == best) key[k] = 0ull;
-            if (lane == 0) {  // (a set with fewer than K + 1 ids: no candidate, ranked last)
-                cval[b * TK + r] = best ? unord_f32((uint32_t)(best >> 32)) : -INFINITY;
-                cid[b * TK + r] = best ? (int)(0xffffffffu - (uint32_t)(best & 0xffffffffull)) : -1;
-            }
-        }
+        beam_row_merge(TK, [&](int sp, int r, float &val, int &id) {
+            const TsBeamPart &q = pp[sp];
+            id = ts_set ? q.ts_id[r] : q.a_id[r];
+            val = ts_set ? q.ts_val[r] : q.a_val[r];
+        }, sl.cval + b * TK, sl.cid + b * TK);
     }
-    __syncthreads();
-    // 2. scores and ranking
-    const int nc = na_old * TK;
-    if (tid < nc) cscore[tid] = cid[tid] >= 0 ? bs->score[tid / TK] + ((double)cval[tid] - lse[tid / TK]) : -INFINITY;
-    __syncthreads();
-    if (tid < nc) {
-        int rank = 0;
-        const double si = cscore[tid];
-        const int bi = tid / TK, ri = tid % TK;
-        for (int j = 0; j < nc; ++j)
-            if (cand_before(cscore[j], j / TK, j % TK, si, bi, ri)) ++rank;
-        order[rank] = tid;
-    }
-    // history table of the parents, positions < pos - 1
-    for (int i = tid; i < na_old * (pos - 1); i += 256) {
-        const int r = i / (pos - 1), j = i - r * (pos - 1);
-        src_old[r][j] = a.kv_src[r * a.tctx + j];
-    }
-    __syncthreads();
-    // 3. walk the ranking
-    if (tid == 0) {
-        int na = 0, nf = bs->n_fin;
-        for (int k = 0; k < nc && na < K; ++k) {
-            const int c = order[k];
-            if (cid[c] < 0) continue;
-            if (cid[c] == a.eot) {
-                if (nf < K) {
-                    bs->fin_t[nf] = t;
-                    bs->fin_beam[nf] = c / TK;
-                    bs->fin_score[nf] = cscore[c];
-                    ta.fin_rec[nf] = record(c);
-                    ++nf;
-                }
-                continue;
-            }
-            sel_parent[na] = c / TK;
-            sel_cand[na] = c;
-            ++na;
-        }
-        n_new_s = na;
-        bs->n_fin = nf;
-        bs->n_active = na;
-        bs->n_steps = t + 1;
-        if (nf >= K || t + 1 >= a.max_tokens) bs->done = 1;
-    }
-    __syncthreads();
-    // 4. next hypotheses: scores, fed tokens, back-pointers, records, KV history table
-    const int nn = n_new_s;
-    if (tid < nn) {
-        const int c = sel_cand[tid];
-        bs->score[tid] = cscore[c];
-        bs->tok[tid] = cid[c];
-        a.hist_parent[t * BEAM_MAX + tid] = sel_parent[tid];
-        a.hist_tok[t * BEAM_MAX + tid] = cid[c];
-        ta.hist_rec[t * BEAM_MAX + tid] = record(c);
-    }
-    for (int i = tid; i < nn * pos; i += 256) {
-        const int sl = i / pos, j = i - sl * pos, p = sel_parent[sl];
-        a.kv_src[sl * a.tctx + j] = j < pos - 1 ? src_old[p][j] : p;
-    }
+    // 2 - 4, with the records
+    beam_select_tail(a, sl, pos, na_old, [&](int nf, int c) { ta.fin_rec[nf] = record(c); },
+                     [&](int s, int, int c) { ta.hist_rec[t * BEAM_MAX + s] = record(c); });
 }
 
 hipError_t launch_tsbeam_step(hipStream_t s, const TsBeamArgs &a) {
