@@ -681,6 +681,84 @@ int wmi_resample_plan(int32_t sample_rate, int32_t *L, int32_t *M, int32_t *K);
 int wmi_resample_taps(int32_t sample_rate, float *h, size_t cap, size_t *n);
 int wmi_resampled_length(int32_t sample_rate, size_t n_frames, size_t *n_out);
 
+/* ---- chunked long-form transcription ---------------------------------- *
+ * One recording across the decoder rows.  wmi_transcribe walks a recording
+ * window by window, every seek waiting for the window before it: one decoder
+ * row.  With chunking on, wmi_transcribe_batch / wmi_transcribe_audio_batch
+ * cut every recording at quiet places into chunks and decode the chunks as
+ * the rows of the rounds.
+ *
+ * A chunk of recording c is a frame span [s, e), 0 <= s < e <= n_len, in
+ * 10 ms mel frames (n_len = n_samples / 160 of the 16 kHz mono samples y).
+ * It is a virtual recording: its own seek (from s), its own end e, its own
+ * text context, its own fallback attempt ordinal and its own segment and
+ * window lists; wherever the loop uses n_len (the window's class, the
+ * fallback's judge, the DTW pass's M), e stands.  Times stay absolute in the
+ * recording.  A chunk's windows take the recording's mel, normalised over
+ * the whole recording, for frames [seek, min(seek + window, e)) and zero from
+ * there on, which is what a window past the recording's end gets.
+ *
+ * Defining property: chunk [s, e) yields the segments the loop yields for a
+ * recording whose normalised mel is the first e frames of this recording's,
+ * started at seek s, under the same settings (context per wmi_set_no_context
+ * / wmi_set_batch_context, language, task, fallback, rules, initial prompt);
+ * whichever other chunks or recordings share the rounds, in any order.  The
+ * recording's result is its chunks' segments in chunk order; window infos
+ * likewise, first_segment renumbered.
+ *
+ * The built-in plan (exact, integer).  N = samples, P = the running sum of
+ * the energy envelope of the token-level timestamps (P[k], k in [0, N],
+ * uint64), Cmin <= Cmax and h in frames.  For a frame boundary k
+ *     S_k = P[min(160 (k + h), N)] - P[160 max(k - h, 0)]
+ * (the energy of h frames each side of the cut).  s_0 = 0; given s_i: if
+ * n_len - s_i <= Cmax the last chunk is [s_i, n_len); else s_{i+1} is the k
+ * in [s_i + Cmin, s_i + Cmax] of smallest S_k, of equal ones the largest k,
+ * and the chunk is [s_i, s_{i+1}).  A recording of 0 frames has no chunk.
+ * A recording of more than 2^26 samples is WMI_E_UNSUPPORTED under the plan.
+ * Silent chunks are not dropped (the fallback's no-speech rule skips silent
+ * windows); a caller with a voice-activity detector passes spans. */
+typedef struct wmi_chunk_params {
+    int32_t enable;        /* 0 (default, also params = NULL) */
+    int32_t max_frames;    /* Cmax; 0 = the window (2 * the audio context in force at the call) */
+    int32_t min_frames;    /* Cmin; 0 = Cmax / 2 (at least 1) */
+    int32_t smooth_frames; /* h; 0 = 10 */
+} wmi_chunk_params;
+/* With enable != 0, wmi_transcribe_batch and wmi_transcribe_audio_batch (one
+ * recording included) schedule the chunks of all recordings over the rounds
+ * in (recording, chunk) order, a freed row taking the next waiting chunk.  A
+ * round holds at most min(8, max_clips) rows: eight rows for one recording
+ * need a context of max_clips = 8.  WMI_LANG_AUTO: a recording's language is
+ * the one detected on its chunk 0's first window (chunk 0 is always in a
+ * round no later than its siblings).  Under wmi_set_batch_context(1) each
+ * chunk carries text context within itself, seeded by the initial prompt as
+ * a recording is.  Token timestamps and DTW work per chunk (the recording's
+ * envelope, absolute times, M from the chunk's end).  A beam size above 1
+ * stays WMI_E_UNSUPPORTED.  wmi_transcribe and wmi_transcribe_audio ignore
+ * the setting.  enable 0: every call runs exactly the kernels it ran before.
+ * WMI_E_INVALID_ARG: a negative field, min_frames > max_frames (checked again
+ * at the call once 0 has been resolved), smooth_frames > 100, max_frames >
+ * 2^20.  Holds until changed. */
+int wmi_set_chunking(wmi_context *ctx, const wmi_chunk_params *params);
+/* Caller's spans for recording `clip` (-1: every clip) in later chunked calls, instead of the plan:
+ * n (start, end) frame pairs, ascending, non-overlapping, start < end; ends are clipped to n_len at the
+ * call, spans at or past n_len dropped; audio between spans is not transcribed.  n = 0: back to the plan.
+ * WMI_E_INVALID_ARG: spans out of order, overlapping, empty or negative, clip outside [-1, max_clips). */
+int wmi_set_chunk_spans(wmi_context *ctx, int clip, const int64_t *spans, int n);
+/* Chunk i of recording `clip` in the last chunked call: its span, its
+ * segments [first_segment, + n_segments) in the _of getters' list and its
+ * window infos [first_window, + n_windows) (0 windows without the fallback).
+ * The count is 0 after a call with chunking off. */
+typedef struct wmi_chunk_info { int64_t start, end; int32_t first_segment, n_segments, first_window, n_windows; } wmi_chunk_info;
+int wmi_get_chunk_count(const wmi_context *ctx, int clip, int32_t *n);
+int wmi_get_chunk(const wmi_context *ctx, int clip, int i, wmi_chunk_info *out);
+/* The plan alone: on the device for loaded recording `clip` (computes and keeps its envelope), and on
+ * the host from P (no context, no device).  out[cap] (start, end) pairs, *n their count; WMI_E_NO_SPACE.
+ * Both use the parameters of wmi_set_chunking / params whatever `enable` is (params NULL: the defaults);
+ * `window` is the frames a window (2 * the audio context), used where max_frames is 0. */
+int wmi_plan_chunks(wmi_context *ctx, int clip, int64_t *out, size_t cap, int32_t *n);
+int wmi_plan_chunks_host(const uint64_t *P, size_t n_samples, const wmi_chunk_params *params, int window,
+                         int64_t *out, size_t cap, int32_t *n);
+
 /* ---- device-resident benchmark path --------------------------------- */
 
 /* Upload n_clips PCM clips to HBM once (untimed). */
@@ -788,7 +866,12 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * batch's mean prompt length and the share of its feed steps spent in
  * padding: scripts/transcribe_batch_bench.py).  In a run with rows of unequal
  * length row b's position p sits at step p + lo[b]: 13 holds its logits in slab p + lo[b], and 19 is [rows][Pmax] with -1 in the
- * lo[b] entries in front of row b's prompt. */
+ * lo[b] entries in front of row b's prompt.  32 = the plan of the last chunked
+ * call (int64, host): per recording its chunk count, then its (start, end)
+ * pairs, -1 behind the last; 33 = that call's chunks, rounds and summed rows
+ * over the rounds (int64 [3], host); 34 = hipEvent ms of the last k_chunk_plan
+ * launch (double, host; -1 before one).  In a chunked call 22's recording
+ * column names the recording each slot's chunk belongs to. */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

@@ -143,8 +143,9 @@ struct wmi_context {
     SampRow *d_samp_rows = nullptr;  // one allocation: rows [8], p_nosp [8], plog [8][n_text_ctx]
     float *d_samp_nosp = nullptr, *d_samp_plog = nullptr;
     std::vector<std::vector<wmi_window_info>> windows;  // per recording of the last transcribe under fb_on
-    int32_t *d_win = nullptr;   // batched transcription: source recording [8], then mel offset [8] of each encoder slot
-    int32_t win_host[2 * DEC_ROWS] = {};  // host copy of the last d_win upload (debug read 22)
+    // batched transcription: source recording [8], then mel offset [8] of each encoder slot, then (chunked calls) its end [8]
+    int32_t *d_win = nullptr;
+    int32_t win_host[3 * DEC_ROWS] = {};  // host copy of the last d_win upload (debug read 22: its first two columns)
     int win_slots = 0;                    // and its slot count (0: no batched round yet)
     bool no_context = false;    // wmi_set_no_context: windows of wmi_transcribe take no earlier text
     // text context in the batch (wmi_set_batch_context): rows of a round hold prompts of unequal length,
@@ -182,6 +183,18 @@ struct wmi_context {
     size_t tt_pcm_cap = 0;
     char *tt_spans = nullptr;               // one window's VadSeg [segments], then t0, t1 [text tokens]
     size_t tt_spans_cap = 0;
+    // chunked long-form transcription (wmi_set_chunking; wmi_chunks.hip).  env_live[clip]: tt_E / tt_P hold the
+    // envelope of the recording now loaded as clip (an upload or wmi_token_times clears it)
+    wmi_chunk_params ck_par{0, 0, 0, 0};
+    std::vector<std::vector<int64_t>> ck_spans;       // [max_clips] the caller's (start, end) pairs (empty: the plan)
+    std::vector<char> env_live;
+    char *d_plan = nullptr;                           // one allocation: ChunkPlanRec [R], counts [R], then every recording's pairs
+    size_t plan_cap = 0;
+    std::vector<std::vector<int64_t>> ck_plan;        // per recording of the last chunked call, its spans (debug read 32)
+    std::vector<std::vector<wmi_chunk_info>> ck_info; // ... and what each chunk yielded (empty after a call with chunking off)
+    int64_t ck_count[3] = {0, 0, 0};                  // its chunks, rounds and summed rows over the rounds (debug read 33)
+    hipEvent_t ck_ev[2] = {};                         // around the last plan launch (wmi_plan_chunks; scripts/chunk_bench.py)
+    float ck_plan_ms = -1.0f;
     struct TokTime { int64_t t0, t1; float vlen; };
     struct Segment { int64_t t0, t1; int first, count; std::string text; };
     struct SegList {
@@ -878,6 +891,7 @@ int stage_pcm(wmi_context *ctx, int n_clips, const float *const *pcm, const size
     std::vector<float *> ptrs(n_clips);
     ctx->n_len_host.assign(n_clips, 0);
     ctx->n_samp_host.assign(n_clips, 0);
+    ctx->env_live.assign((size_t)ctx->max_clips, 0);
     int64_t max_len = 0;
     for (int c = 0; c < n_clips; ++c) {
         const size_t ns = n_samples[c];
@@ -1034,6 +1048,7 @@ int stage_audio(wmi_context *ctx, int n_clips, const wmi_audio *clips) {
     std::vector<float *> ptrs(n_clips);
     ctx->n_len_host.assign(n_clips, 0);
     ctx->n_samp_host.assign(n_clips, 0);
+    ctx->env_live.assign((size_t)ctx->max_clips, 0);
     ctx->n_clips = 0;  // (until the clips are whole again)
     ctx->enc_T = 0;
     ctx->au_ms = 0.0f;
@@ -1116,15 +1131,18 @@ int run_mel(wmi_context *ctx) {
 
 // Encode B slots.  Without src / off: the loaded clips, each at mel_offset.
 // With them (device arrays [B]): slot b holds recording src[b]'s window at
-// off[b], B <= the loaded clips (a round of run_transcribe_batch).
+// off[b], B <= the loaded clips (a round of run_transcribe_batch).  With end
+// too (a chunked call's round): slot b's window ends at frame end[b] of its
+// recording, several slots may hold one recording, and B <= max_clips.
 int run_encode(wmi_context *ctx, int mel_offset, int slots = 0, const int32_t *src = nullptr,
-               const int32_t *off = nullptr) {
+               const int32_t *off = nullptr, const int32_t *end = nullptr) {
     const wmi_hparams &hp = ctx->hp;
     const int B = src ? slots : ctx->n_clips;
     const int T = ctx->cur_ctx > 0 ? ctx->cur_ctx : hp.n_audio_ctx, T2 = 2 * T;
     const int Tp = (int)up(T, 64);
     const int n = hp.n_audio_state, H = hp.n_audio_head, nt = hp.n_text_state;
-    if (B < 1 || B > ctx->n_clips) return set_err(ctx, WMI_E_INVALID_ARG, "encode before pcm_to_mel");
+    if (B < 1 || B > (end ? ctx->max_clips : ctx->n_clips) || ctx->n_clips < 1)
+        return set_err(ctx, WMI_E_INVALID_ARG, "encode before pcm_to_mel");
     if (mel_offset < 0) return set_err(ctx, WMI_E_INVALID_ARG, "negative mel_offset");
     {
         std::string why;
@@ -1156,8 +1174,12 @@ int run_encode(wmi_context *ctx, int mel_offset, int slots = 0, const int32_t *s
     const bool f32 = ctx->wf32;
     auto W32 = [&](const uint16_t *w) { return f32 ? (const float *)w : nullptr; };
     // (f16 models: conv2's zero pad rows of g1 are written by the window kernel)
-    HIPCHK(ctx, launch_mel_window(s, ctx->d_mel, ctx->mel_stride, hp.n_mels, ctx->d_nlen, mel_offset, T2, ctx->Cp1,
-                                  ctx->xconv, B, ctx->xconv32, f32 ? nullptr : ctx->g1, n, src, off));
+    if (end)
+        HIPCHK(ctx, launch_mel_window_end(s, ctx->d_mel, ctx->mel_stride, hp.n_mels, ctx->d_nlen, T2, ctx->Cp1, ctx->xconv, B,
+                                          ctx->xconv32, f32 ? nullptr : ctx->g1, n, src, off, end));
+    else
+        HIPCHK(ctx, launch_mel_window(s, ctx->d_mel, ctx->mel_stride, hp.n_mels, ctx->d_nlen, mel_offset, T2, ctx->Cp1,
+                                      ctx->xconv, B, ctx->xconv32, f32 ? nullptr : ctx->g1, n, src, off));
     if (f32) HIPCHK(ctx, hipMemsetAsync(ctx->g1, 0, (size_t)B * (T2 + 2) * n * 2, s));
     GemmArgs g{};
     // conv1 + bias + GELU (main.rs:1834-1855)
@@ -2354,6 +2376,8 @@ int tt_energy(wmi_context *ctx, int clip, const float *d_pcm, int64_t N) {
         ctx->tt_cap.resize(ctx->max_clips, 0);
         ctx->tt_n.resize(ctx->max_clips, -1);
     }
+    ctx->env_live.resize((size_t)ctx->max_clips, 0);
+    ctx->env_live[clip] = 0;  // (the caller knows whether d_pcm is the loaded recording)
     ctx->tt_n[clip] = -1;
     if (N > 0) {
         if ((size_t)N > ctx->tt_cap[clip]) {
@@ -2473,6 +2497,7 @@ int tt_energy_of_clips(wmi_context *ctx, int n_clips) {
     for (int c = 0; ctx->tt_on && c < n_clips; ++c) {
         int rc = tt_energy(ctx, c, ctx->pcm_dev[c], ctx->n_samp_host[c]);
         if (rc) return rc;
+        ctx->env_live[c] = 1;
     }
     return WMI_OK;
 }
@@ -2644,10 +2669,12 @@ bool fb_silence(const wmi_context *ctx, float p_nosp, const FbAttempt &att) {
 }
 
 // ---- whisper_full's loop: state, decode-attempt, settle ------------------------
-// One recording of a wmi_transcribe / wmi_transcribe_batch call.
+// One recording of a wmi_transcribe / wmi_transcribe_batch call, or under
+// wmi_set_chunking one chunk [s, e) of one: a virtual recording that starts at
+// seek s and ends at e.
 struct TrRec {
-    int clip;                   // its mel, segment list and window infos
-    int64_t seek, n_len;        // the current window's first frame, the recording's frames
+    int clip;                   // its mel, language and envelope
+    int64_t seek, n_len;        // the current window's first frame, the recording's frames (a chunk: its end e)
     int lang;                   // WMI_LANG_AUTO until its first window
     float lang_p;               // the detection's probability (-1: set explicitly)
     bool carry;                 // earlier text goes into later prompts (wmi_transcribe without no-context)
@@ -2655,28 +2682,42 @@ struct TrRec {
     int att;                    // the fallback's attempt at the current window
     uint64_t n_samp;            // T > 0 attempts so far (the ordinal behind each attempt's stream key)
     float p_nosp0;              // attempt 0's no-speech probability
+    int out;                    // its segment list and window infos (ctx->results / windows; a recording: its clip)
+    int chunk;                  // a chunk: its index in its recording
 };
 struct TrRun {
     int window, n_max;          // frames a window, sampled tokens a window at most
     std::vector<float> temps;   // the fallback's temperatures (empty: off)
     std::vector<TrRec> recs;
 };
+// a chunk of a chunked call, in (recording, chunk) order
+struct TrChunk {
+    int clip, idx;
+    int64_t s, e;
+};
 
 // A call's start: empty results and window infos, every recording at frame 0
-// with the language set for its clip.
-TrRun tr_begin(wmi_context *ctx, int R, int max_tokens, bool carry) {
+// with the language set for its clip.  With chunks: one TrRec a chunk, each
+// with a segment list and window infos of its own until ck_merge.
+TrRun tr_begin(wmi_context *ctx, int R, int max_tokens, bool carry, const std::vector<TrChunk> *chunks = nullptr) {
     const wmi_hparams &hp = ctx->hp;
     TrRun tr;
     tr.window = 2 * (ctx->cur_ctx > 0 ? ctx->cur_ctx : hp.n_audio_ctx);
     tr.n_max = std::min(max_tokens, hp.n_text_ctx / 2 - 4);
     if (ctx->fb_on) tr.temps = fb_temperatures(ctx->fb);
     // (with text context the initial prompt seeds it: window 0 sees it, later windows the tail of it + text)
-    for (int r = 0; r < R; ++r)
-        tr.recs.push_back({r, 0, ctx->n_len_host[r], ctx->lang_set[r], -1.0f, carry,
-                           carry ? ctx->init_prompt : std::vector<int32_t>{}, 0, 0, 0.0f});
-    ctx->results.assign((size_t)R, {});
+    const std::vector<int32_t> past = carry ? ctx->init_prompt : std::vector<int32_t>{};
+    if (chunks) {
+        for (const TrChunk &c : *chunks)
+            tr.recs.push_back({c.clip, c.s, c.e, ctx->lang_set[c.clip], -1.0f, carry, past, 0, 0, 0.0f, (int)tr.recs.size(), c.idx});
+    } else {
+        for (int r = 0; r < R; ++r) tr.recs.push_back({r, 0, ctx->n_len_host[r], ctx->lang_set[r], -1.0f, carry, past, 0, 0, 0.0f, r, 0});
+    }
+    const size_t lists = chunks ? std::max<size_t>(chunks->size(), 1) : (size_t)R;
+    ctx->results.assign(lists, {});
     ctx->windows.clear();
-    if (ctx->fb_on) ctx->windows.assign((size_t)R, {});
+    if (ctx->fb_on) ctx->windows.assign(lists, {});
+    ctx->ck_info.clear();
     return tr;
 }
 
@@ -2686,7 +2727,7 @@ TrRun tr_begin(wmi_context *ctx, int R, int max_tokens, bool carry) {
 int tr_resolve_languages(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows) {
     const int B = (int)rows.size();
     bool detect = false;
-    for (int r : rows) detect = detect || tr.recs[r].lang == WMI_LANG_AUTO;
+    for (int r : rows) detect = detect || (tr.recs[r].lang == WMI_LANG_AUTO && tr.recs[r].chunk == 0);
     int32_t det[DEC_ROWS] = {};
     float p[DEC_ROWS] = {};
     if (detect) {
@@ -2697,7 +2738,14 @@ int tr_resolve_languages(wmi_context *ctx, TrRun &tr, const std::vector<int> &ro
     }
     for (int b = 0; b < B; ++b) {
         TrRec &rec = tr.recs[rows[b]];
-        if (rec.lang == WMI_LANG_AUTO) { rec.lang = det[b]; rec.lang_p = p[b]; }
+        if (rec.lang == WMI_LANG_AUTO && rec.chunk == 0) { rec.lang = det[b]; rec.lang_p = p[b]; }
+        if (rec.lang == WMI_LANG_AUTO) {
+            // a later chunk takes its recording's language: chunk 0 entered the rows before it (rows keep the
+            // (recording, chunk) order), so it sits in an earlier row of this round or was resolved in an earlier one
+            rec.lang = ctx->lang_used[rec.clip];
+            rec.lang_p = ctx->lang_p[rec.clip];
+            if (rec.lang == WMI_LANG_AUTO) return set_err(ctx, WMI_E_UNEXPECTED, "internal: chunk %d of clip %d before chunk 0", rec.chunk, rec.clip);
+        }
         ctx->lang_used[rec.clip] = rec.lang;
         ctx->lang_p[rec.clip] = rec.lang_p;
     }
@@ -2782,7 +2830,7 @@ int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows,
 // wmi_set_dtw a committed window's text tokens are aligned first (al_window:
 // one more pass over encoder slot `slot`, which still holds the window).
 int tr_settle(wmi_context *ctx, const TrRun &tr, TrRec &rec, int slot, TrAttempt a, bool *done) {
-    wmi_context::SegList &res = ctx->results[rec.clip];
+    wmi_context::SegList &res = ctx->results[rec.out];
     std::vector<int32_t> *past = rec.carry ? &rec.past : nullptr;
     const size_t seg_first = res.segments.size(), tok_first = res.tokens.size();
     *done = true;
@@ -2832,7 +2880,7 @@ int tr_settle(wmi_context *ctx, const TrRun &tr, TrRec &rec, int slot, TrAttempt
         }
     }
     wi.n_segments = (int32_t)res.segments.size() - wi.first_segment;
-    ctx->windows[rec.clip].push_back(wi);
+    ctx->windows[rec.out].push_back(wi);
     rec.att = 0;
     rec.seek += delta;
     return WMI_OK;
@@ -2871,6 +2919,146 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
     return WMI_OK;
 }
 
+// ---- chunked long-form transcription (wmi_set_chunking) ---------------------------
+// The plans of the loaded recordings `clips` under (Cmax, Cmin, h): each one's
+// envelope if it is not there yet (shared with the token-level timestamps),
+// then one k_chunk_plan launch, a workgroup a recording; only the lists come
+// back.  (*out)[i]: clips[i]'s (start, end) pairs.
+int ck_plan_device(wmi_context *ctx, const std::vector<int> &clips, int Cmax, int Cmin, int h,
+                   std::vector<std::vector<int64_t>> *out) {
+    const size_t n = clips.size();
+    out->assign(n, {});
+    if (!n) return WMI_OK;
+    for (int c : clips) {
+        if (ctx->n_samp_host[c] > TT_MAX_SAMPLES)
+            return set_err(ctx, WMI_E_UNSUPPORTED, "the chunk plan takes at most 2^26 samples a recording (clip %d: %lld)", c,
+                           (long long)ctx->n_samp_host[c]);
+        if (c < (int)ctx->env_live.size() && ctx->env_live[c]) continue;
+        int rc = tt_energy(ctx, c, ctx->pcm_dev[c], ctx->n_samp_host[c]);
+        if (rc) return rc;
+        ctx->env_live[c] = 1;
+    }
+    // recs [n], counts [n] (int32, padded to 8 bytes), then each recording's pairs
+    const size_t o_cnt = n * sizeof(ChunkPlanRec), o_out = o_cnt + (size_t)up((int64_t)(n * 4), 8);
+    std::vector<size_t> at(n), cap(n);
+    size_t need = o_out;
+    for (size_t i = 0; i < n; ++i) {
+        cap[i] = (size_t)(ctx->n_len_host[clips[i]] / Cmin + 2);
+        at[i] = need;
+        need += cap[i] * 16;
+    }
+    if (need > ctx->plan_cap) {
+        if (ctx->d_plan) HIPCHK(ctx, hipFree(ctx->d_plan));
+        ctx->d_plan = nullptr; ctx->plan_cap = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->d_plan, 2 * need));
+        ctx->plan_cap = 2 * need;
+    }
+    if (!ctx->ck_ev[0])
+        for (hipEvent_t &e : ctx->ck_ev) HIPCHK(ctx, hipEventCreate(&e));
+    char *d = ctx->d_plan;
+    std::vector<ChunkPlanRec> recs(n);
+    for (size_t i = 0; i < n; ++i) {
+        const int c = clips[i];
+        recs[i] = ChunkPlanRec{ctx->n_samp_host[c] > 0 ? ctx->tt_P[c] : nullptr, (long long)ctx->n_samp_host[c],
+                               (long long *)(d + at[i]), (int32_t *)(d + o_cnt) + i, (int32_t)cap[i]};
+    }
+    HIPCHK(ctx, hipMemcpyAsync(d, recs.data(), o_cnt, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(ctx->ck_ev[0], ctx->stream));
+    HIPCHK(ctx, launch_chunk_plan(ctx->stream, (const ChunkPlanRec *)d, (int)n, Cmax, Cmin, h));
+    HIPCHK(ctx, hipEventRecord(ctx->ck_ev[1], ctx->stream));
+    std::vector<char> back(need - o_cnt);
+    HIPCHK(ctx, hipMemcpyAsync(back.data(), d + o_cnt, back.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipEventElapsedTime(&ctx->ck_plan_ms, ctx->ck_ev[0], ctx->ck_ev[1]);
+    for (size_t i = 0; i < n; ++i) {
+        int32_t cnt;
+        memcpy(&cnt, back.data() + i * 4, 4);
+        if (cnt < 0 || (size_t)cnt > cap[i])
+            return set_err(ctx, WMI_E_UNEXPECTED, "internal: a plan of %d chunks for clip %d (room for %zu)", cnt, clips[i], cap[i]);
+        (*out)[i].resize(2 * (size_t)cnt);
+        if (cnt) memcpy((*out)[i].data(), back.data() + (at[i] - o_cnt), (size_t)cnt * 16);
+    }
+    return WMI_OK;
+}
+
+// the parameters in force for a window of `window` frames
+int ck_resolve(wmi_context *ctx, int window, int *Cmax, int *Cmin, int *h) {
+    std::string err;
+    int rc = chunk_resolve(ctx->ck_par, window, Cmax, Cmin, h, err);
+    return rc ? set_err(ctx, rc, "%s", err.c_str()) : WMI_OK;
+}
+
+// The chunks of the R loaded recordings in (recording, chunk) order: the
+// caller's spans where given (ends clipped to the recording, spans at or past
+// its end dropped), else the plan.  Kept as the call's plan (debug read 32).
+int ck_build(wmi_context *ctx, int R, std::vector<TrChunk> *chunks) {
+    int Cmax, Cmin, h;
+    int rc = ck_resolve(ctx, 2 * (ctx->cur_ctx > 0 ? ctx->cur_ctx : ctx->hp.n_audio_ctx), &Cmax, &Cmin, &h);
+    if (rc) return rc;
+    ctx->ck_plan.assign((size_t)R, {});
+    std::vector<int> planned;
+    for (int c = 0; c < R; ++c) {
+        const std::vector<int64_t> *sp = c < (int)ctx->ck_spans.size() && !ctx->ck_spans[c].empty() ? &ctx->ck_spans[c] : nullptr;
+        if (!sp) { planned.push_back(c); continue; }
+        const int64_t nl = ctx->n_len_host[c];
+        for (size_t i = 0; i + 1 < sp->size(); i += 2) {
+            if ((*sp)[i] >= nl) break;
+            ctx->ck_plan[c].push_back((*sp)[i]);
+            ctx->ck_plan[c].push_back(std::min((*sp)[i + 1], nl));
+        }
+    }
+    std::vector<std::vector<int64_t>> plans;
+    rc = ck_plan_device(ctx, planned, Cmax, Cmin, h, &plans);
+    if (rc) return rc;
+    for (size_t i = 0; i < planned.size(); ++i) ctx->ck_plan[planned[i]] = std::move(plans[i]);
+    chunks->clear();
+    for (int c = 0; c < R; ++c)
+        for (size_t i = 0; i + 1 < ctx->ck_plan[c].size(); i += 2)
+            chunks->push_back({c, (int)(i / 2), ctx->ck_plan[c][i], ctx->ck_plan[c][i + 1]});
+    return WMI_OK;
+}
+
+// After the rounds: each recording's lists are its chunks' in chunk order
+// (segments' token offsets and window infos' first_segment renumbered), and
+// what each chunk yielded (wmi_get_chunk).
+void ck_merge(wmi_context *ctx, int R, const std::vector<TrChunk> &chunks) {
+    std::vector<wmi_context::SegList> merged((size_t)R);
+    std::vector<std::vector<wmi_window_info>> wins(ctx->windows.empty() ? 0 : (size_t)R);
+    ctx->ck_info.assign((size_t)R, {});
+    for (size_t i = 0; i < chunks.size(); ++i) {
+        const TrChunk &ch = chunks[i];
+        wmi_context::SegList &src = ctx->results[i], &dst = merged[ch.clip];
+        const int seg0 = (int)dst.segments.size(), tok0 = (int)dst.tokens.size();
+        wmi_chunk_info ci{ch.s, ch.e, seg0, (int32_t)src.segments.size(), 0, 0};
+        if (ctx->tt_on) {
+            dst.times.resize(dst.tokens.size(), {-1, -1, 0.0f});
+            src.times.resize(src.tokens.size(), {-1, -1, 0.0f});
+            dst.times.insert(dst.times.end(), src.times.begin(), src.times.end());
+        }
+        if (ctx->al_on) {
+            dst.dtw.resize(dst.tokens.size(), wmi_dtw_time{-1, -1});
+            src.dtw.resize(src.tokens.size(), wmi_dtw_time{-1, -1});
+            dst.dtw.insert(dst.dtw.end(), src.dtw.begin(), src.dtw.end());
+        }
+        for (wmi_context::Segment &sg : src.segments) {
+            sg.first += tok0;
+            dst.segments.push_back(std::move(sg));
+        }
+        dst.tokens.insert(dst.tokens.end(), src.tokens.begin(), src.tokens.end());
+        if (!wins.empty()) {
+            ci.first_window = (int32_t)wins[ch.clip].size();
+            ci.n_windows = (int32_t)ctx->windows[i].size();
+            for (wmi_window_info wi : ctx->windows[i]) {
+                wi.first_segment += seg0;
+                wins[ch.clip].push_back(wi);
+            }
+        }
+        ctx->ck_info[ch.clip].push_back(ci);
+    }
+    ctx->results = std::move(merged);
+    ctx->windows = std::move(wins);
+}
+
 // wmi_transcribe_batch: every loaded recording through whisper_full's loop,
 // up to DEC_ROWS of them per decoder step; without text context, or under
 // wmi_set_batch_context each with its own (TrRec::past).  All mels
@@ -2886,35 +3074,50 @@ int run_transcribe(wmi_context *ctx, int max_tokens) {
 // row; a waiting one takes a free row at the next round; under the fallback a
 // rejected recording stays at its seek and takes its next temperature in the
 // next round.
+//
+// Under wmi_set_chunking the rows hold chunks instead (ck_build: every
+// recording's spans, by the plan kernel or the caller's): a TrRec each, taken
+// in (recording, chunk) order, at most min(DEC_ROWS, max_clips) a round, the
+// encoder's windows cut at each chunk's end (run_encode's end column); the
+// round loop is the same, and ck_merge puts each recording's lists together.
 int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
     const int R = ctx->n_clips;
-    if (!ctx->d_win) HIPCHK(ctx, hipMalloc(&ctx->d_win, 2 * DEC_ROWS * 4));
-    TrRun tr = tr_begin(ctx, R, max_tokens, ctx->batch_context && !ctx->no_context);
+    const bool chunked = ctx->ck_par.enable != 0;
+    if (!ctx->d_win) HIPCHK(ctx, hipMalloc(&ctx->d_win, 3 * DEC_ROWS * 4));
+    std::vector<TrChunk> chunks;
+    if (chunked) {
+        int rc = ck_build(ctx, R, &chunks);
+        if (rc) return rc;
+    }
+    TrRun tr = tr_begin(ctx, R, max_tokens, ctx->batch_context && !ctx->no_context, chunked ? &chunks : nullptr);
     memset(ctx->trb_count, 0, sizeof ctx->trb_count);
     for (int r = 0; r < R; ++r) {
-        ctx->lang_used[r] = tr.recs[r].lang;  // (AUTO: until the recording's first window detects it)
+        ctx->lang_used[r] = ctx->lang_set[r];  // (AUTO: until the recording's first window detects it)
         ctx->lang_p[r] = -1.0f;
     }
-    std::vector<int> rows;  // recording of each decoder row
+    const int n_recs = (int)tr.recs.size();
+    const size_t max_rows = chunked ? (size_t)std::min(DEC_ROWS, ctx->max_clips) : (size_t)DEC_ROWS;
+    std::vector<int> rows;  // recording (chunk) of each decoder row
     int next = 0;
     for (;;) {
         size_t k = 0;
         for (int r : rows)
             if (tr.recs[r].seek < tr.recs[r].n_len) rows[k++] = r;
         rows.resize(k);
-        for (; next < R && rows.size() < (size_t)DEC_ROWS; ++next)
-            if (tr.recs[next].n_len > 0) rows.push_back(next);
+        for (; next < n_recs && rows.size() < max_rows; ++next)
+            if (tr.recs[next].seek < tr.recs[next].n_len) rows.push_back(next);
         if (rows.empty()) break;
         const int B = (int)rows.size();
-        int32_t win[2 * DEC_ROWS] = {};
+        int32_t win[3 * DEC_ROWS] = {};
         for (int b = 0; b < B; ++b) {
-            win[b] = rows[b];
+            win[b] = tr.recs[rows[b]].clip;
             win[DEC_ROWS + b] = (int32_t)tr.recs[rows[b]].seek;
+            win[2 * DEC_ROWS + b] = (int32_t)tr.recs[rows[b]].n_len;
         }
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_win, win, sizeof win, hipMemcpyHostToDevice, ctx->stream));
         memcpy(ctx->win_host, win, sizeof win);
         ctx->win_slots = B;
-        int rc = run_encode(ctx, 0, B, ctx->d_win, ctx->d_win + DEC_ROWS);
+        int rc = run_encode(ctx, 0, B, ctx->d_win, ctx->d_win + DEC_ROWS, chunked ? ctx->d_win + 2 * DEC_ROWS : nullptr);
         if (rc) return rc;
         rc = tr_resolve_languages(ctx, tr, rows);
         if (rc) return rc;
@@ -2943,6 +3146,12 @@ int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
             rc = tr_settle(ctx, tr, tr.recs[rows[b]], b, std::move(att[b]), &done);
             if (rc) return rc;
         }
+    }
+    if (chunked) {
+        ctx->ck_count[0] = (int64_t)chunks.size();
+        ctx->ck_count[1] = ctx->trb_count[0];
+        ctx->ck_count[2] = ctx->trb_count[4];
+        ck_merge(ctx, R, chunks);
     }
     return WMI_OK;
 }
@@ -3226,6 +3435,8 @@ static int wmi_init_from_file_impl(const char *path, int device, int max_clips, 
     ctx->lang_set.assign(max_clips, 0);
     ctx->lang_used.assign(max_clips, 0);
     ctx->lang_p.assign(max_clips, -1.0f);
+    ctx->ck_spans.assign(max_clips, {});
+    ctx->env_live.assign(max_clips, 0);
     // id_to_token incl. extra-token names (main.rs:442-467)
     ctx->vocab = std::move(pm.vocab);
     for (int32_t i = (int32_t)ctx->vocab.size(); i < pm.hp.n_vocab; ++i) {
@@ -3337,6 +3548,8 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->d_tsb_parts) (void)hipFree(ctx->d_tsb_parts);
     if (ctx->d_tsb_rec) (void)hipFree(ctx->d_tsb_rec);
     if (ctx->d_win) (void)hipFree(ctx->d_win);
+    if (ctx->d_plan) (void)hipFree(ctx->d_plan);
+    for (hipEvent_t e : ctx->ck_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->d_samp_rows) (void)hipFree(ctx->d_samp_rows);
     if (ctx->d_rule_m0) (void)hipFree(ctx->d_rule_m0);
     if (ctx->d_rb_hist) (void)hipFree(ctx->d_rb_hist);
@@ -3693,6 +3906,73 @@ int wmi_set_batch_context(wmi_context *ctx, int enable) {
     if (enable != 0 && enable != 1) return set_err(ctx, WMI_E_INVALID_ARG, "enable %d is neither 0 nor 1", enable);
     ctx->batch_context = enable != 0;
     return WMI_OK;
+}
+
+int wmi_set_chunking(wmi_context *ctx, const wmi_chunk_params *params) {
+    return guarded(ctx, [&] {
+        if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+        const wmi_chunk_params p = params ? *params : wmi_chunk_params{0, 0, 0, 0};
+        std::string err;
+        int rc = chunk_check_params(p, err);
+        if (rc) return set_err(ctx, rc, "%s", err.c_str());
+        ctx->ck_par = p;
+        return (int)WMI_OK;
+    });
+}
+
+int wmi_set_chunk_spans(wmi_context *ctx, int clip, const int64_t *spans, int n) {
+    return guarded(ctx, [&] {
+        if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+        if (clip < -1 || clip >= ctx->max_clips) return set_err(ctx, WMI_E_INVALID_ARG, "clip %d outside [-1, max_clips=%d)", clip, ctx->max_clips);
+        if (n < 0 || (n > 0 && !spans)) return set_err(ctx, WMI_E_INVALID_ARG, "%d spans, null pointer", n);
+        std::string err;
+        int rc = chunk_check_spans(spans, n, err);
+        if (rc) return set_err(ctx, rc, "%s", err.c_str());
+        const std::vector<int64_t> v(spans, spans + 2 * (size_t)n);
+        for (int c = 0; c < ctx->max_clips; ++c)
+            if (clip < 0 || c == clip) ctx->ck_spans[c] = v;
+        return (int)WMI_OK;
+    });
+}
+
+int wmi_get_chunk_count(const wmi_context *ctx, int clip, int32_t *n) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    wmi_context *ec = const_cast<wmi_context *>(ctx);  // (last_error only)
+    if (!n || clip < 0 || clip >= (int)ctx->results.size())
+        return set_err(ec, WMI_E_INVALID_ARG, "null n, or clip %d outside the %d recordings of the last transcribe", clip,
+                       (int)ctx->results.size());
+    *n = clip < (int)ctx->ck_info.size() ? (int32_t)ctx->ck_info[clip].size() : 0;
+    return WMI_OK;
+}
+
+int wmi_get_chunk(const wmi_context *ctx, int clip, int i, wmi_chunk_info *out) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    wmi_context *ec = const_cast<wmi_context *>(ctx);
+    if (!out || clip < 0 || clip >= (int)ctx->ck_info.size() || i < 0 || i >= (int)ctx->ck_info[clip].size())
+        return set_err(ec, WMI_E_INVALID_ARG, "null out, or chunk %d of clip %d outside the last chunked call's", i, clip);
+    *out = ctx->ck_info[clip][i];
+    return WMI_OK;
+}
+
+static int wmi_plan_chunks_impl(wmi_context *ctx, int clip, int64_t *out, size_t cap, int32_t *n) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (!n || (!out && cap > 0)) return set_err(ctx, WMI_E_INVALID_ARG, "null n / out");
+    if (clip < 0 || clip >= ctx->n_clips) return set_err(ctx, WMI_E_INVALID_ARG, "clip %d outside the %d loaded", clip, ctx->n_clips);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int Cmax, Cmin, h;
+    int rc = ck_resolve(ctx, 2 * (ctx->cur_ctx > 0 ? ctx->cur_ctx : ctx->hp.n_audio_ctx), &Cmax, &Cmin, &h);
+    if (rc) return rc;
+    std::vector<std::vector<int64_t>> plans;
+    rc = ck_plan_device(ctx, {clip}, Cmax, Cmin, h, &plans);
+    if (rc) return rc;
+    *n = (int32_t)(plans[0].size() / 2);
+    if (plans[0].size() > 2 * cap) return WMI_E_NO_SPACE;
+    if (!plans[0].empty()) memcpy(out, plans[0].data(), plans[0].size() * 8);
+    return WMI_OK;
+}
+
+int wmi_plan_chunks(wmi_context *ctx, int clip, int64_t *out, size_t cap, int32_t *n) {
+    return guarded(ctx, [&] { return wmi_plan_chunks_impl(ctx, clip, out, cap, n); });
 }
 
 int wmi_is_non_speech_token(const char *bytes, size_t len) {
@@ -4532,6 +4812,25 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
             memcpy(out, ctx->trb_count, std::min(sizeof ctx->trb_count, bytes));
             return WMI_OK;
         }
+        case 32: {  // host, int64: the last chunked call's plan, per recording its chunk count, then its (start, end) pairs
+            std::vector<int64_t> v;
+            for (const auto &pl : ctx->ck_plan) {
+                v.push_back((int64_t)(pl.size() / 2));
+                v.insert(v.end(), pl.begin(), pl.end());
+            }
+            memset(out, 0xff, bytes);
+            memcpy(out, v.data(), std::min(v.size() * 8, bytes));
+            return WMI_OK;
+        }
+        case 33: {  // host, int64 [3]: chunks, rounds and summed rows over the rounds of the last chunked call
+            memcpy(out, ctx->ck_count, std::min(sizeof ctx->ck_count, bytes));
+            return WMI_OK;
+        }
+        case 34: {  // host, double: hipEvent ms of the last k_chunk_plan launch (-1: none yet)
+            const double v = (double)ctx->ck_plan_ms;
+            memcpy(out, &v, std::min(sizeof v, bytes));
+            return WMI_OK;
+        }
         case 20: {  // host: windows, decoder steps (every attempt's) and fallback attempts of the last wmi_transcribe, int64 [3]
             memcpy(out, ctx->tr_count, std::min(sizeof ctx->tr_count, bytes));
             return WMI_OK;
@@ -4545,7 +4844,7 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
         case 22: {  // host: slots of the last wmi_transcribe_batch round, then their recording [8] and mel offset [8] (int32 [17])
             int32_t v[1 + 2 * DEC_ROWS];
             v[0] = ctx->win_slots;
-            memcpy(v + 1, ctx->win_host, sizeof ctx->win_host);
+            memcpy(v + 1, ctx->win_host, 2 * DEC_ROWS * 4);
             memcpy(out, v, std::min(sizeof v, bytes));
             return WMI_OK;
         }

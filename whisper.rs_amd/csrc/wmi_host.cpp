@@ -696,9 +696,106 @@ int dtw_head_table(const wmi_hparams &hp, const wmi_dtw_params &p, std::vector<i
     return WMI_OK;
 }
 
+int chunk_check_params(const wmi_chunk_params &p, std::string &err) {
+    char b[160];
+    if (p.max_frames < 0 || p.min_frames < 0 || p.smooth_frames < 0) {
+        snprintf(b, sizeof b, "negative field (max_frames %d, min_frames %d, smooth_frames %d)", p.max_frames, p.min_frames,
+                 p.smooth_frames);
+    } else if (p.max_frames > (1 << 20)) {
+        snprintf(b, sizeof b, "max_frames %d above 2^20", p.max_frames);
+    } else if (p.smooth_frames > 100) {
+        snprintf(b, sizeof b, "smooth_frames %d above 100", p.smooth_frames);
+    } else if (p.max_frames > 0 && p.min_frames > p.max_frames) {
+        snprintf(b, sizeof b, "min_frames %d above max_frames %d", p.min_frames, p.max_frames);
+    } else {
+        return WMI_OK;
+    }
+    err = b;
+    return WMI_E_INVALID_ARG;
+}
+
+int chunk_resolve(const wmi_chunk_params &p, int window, int *Cmax, int *Cmin, int *h, std::string &err) {
+    int rc = chunk_check_params(p, err);
+    if (rc) return rc;
+    char b[160];
+    *Cmax = p.max_frames > 0 ? p.max_frames : window;
+    if (*Cmax < 1 || *Cmax > (1 << 20)) {
+        snprintf(b, sizeof b, "max_frames 0 with a window of %d frames", window);
+        err = b;
+        return WMI_E_INVALID_ARG;
+    }
+    *Cmin = p.min_frames > 0 ? p.min_frames : (*Cmax / 2 > 1 ? *Cmax / 2 : 1);
+    *h = p.smooth_frames > 0 ? p.smooth_frames : 10;
+    if (*Cmin > *Cmax) {
+        snprintf(b, sizeof b, "min_frames %d above the %d frames of max_frames / the window", *Cmin, *Cmax);
+        err = b;
+        return WMI_E_INVALID_ARG;
+    }
+    return WMI_OK;
+}
+
+int chunk_check_spans(const int64_t *spans, int n, std::string &err) {
+    int64_t prev = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t s = spans[2 * i], e = spans[2 * i + 1];
+        if (s < prev || e <= s) {
+            char b[160];
+            snprintf(b, sizeof b, "span %d [%lld, %lld) is empty, negative, or starts before %lld", i, (long long)s, (long long)e,
+                     (long long)prev);
+            err = b;
+            return WMI_E_INVALID_ARG;
+        }
+        prev = e;
+    }
+    return WMI_OK;
+}
+
+std::vector<int64_t> chunk_plan(const uint64_t *P, int64_t N, int Cmax, int Cmin, int h) {
+    std::vector<int64_t> out;
+    const int64_t n_len = N / 160;
+    int64_t s = 0;
+    while (n_len - s > Cmax) {
+        uint64_t best = 0;
+        int64_t at = -1;
+        for (int64_t k = s + Cmin; k <= s + Cmax; ++k) {
+            const int64_t hi = std::min<int64_t>(160 * (k + h), N), lo = 160 * std::max<int64_t>(k - h, 0);
+            const uint64_t S = P[hi] - P[lo];
+            if (at < 0 || S <= best) { best = S; at = k; }
+        }
+        out.push_back(s);
+        out.push_back(at);
+        s = at;
+    }
+    if (n_len > 0) {
+        out.push_back(s);
+        out.push_back(n_len);
+    }
+    return out;
+}
+
 }  // namespace wmi
 
 extern "C" {
+
+int wmi_plan_chunks_host(const uint64_t *P, size_t n_samples, const wmi_chunk_params *params, int window, int64_t *out,
+                         size_t cap, int32_t *n) {
+    if (!n || (!P && n_samples > 0) || (!out && cap > 0)) return WMI_E_INVALID_ARG;
+    if (n_samples > ((size_t)1 << 26)) return WMI_E_UNSUPPORTED;
+    try {
+        const wmi_chunk_params p = params ? *params : wmi_chunk_params{0, 0, 0, 0};
+        int Cmax, Cmin, h;
+        std::string err;
+        int rc = wmi::chunk_resolve(p, window, &Cmax, &Cmin, &h, err);
+        if (rc) return rc;
+        const std::vector<int64_t> plan = wmi::chunk_plan(P, (int64_t)n_samples, Cmax, Cmin, h);
+        *n = (int32_t)(plan.size() / 2);
+        if (plan.size() > 2 * cap) return WMI_E_NO_SPACE;
+        if (!plan.empty()) memcpy(out, plan.data(), plan.size() * 8);
+    } catch (...) {
+        return WMI_E_UNEXPECTED;
+    }
+    return WMI_OK;
+}
 
 // S6 of the header on the host: D row by row in int64, a trace byte a cell
 int wmi_dtw_path_host(const int32_t *cost, int rows, int cols, int32_t *first) {

@@ -99,6 +99,17 @@ std::vector<TokPiece> split_segment(const std::vector<std::string> &vocab, int32
 // with the reason in err
 int dtw_head_table(const wmi_hparams &hp, const wmi_dtw_params &p, std::vector<int32_t> &pairs, std::string &err);
 
+// ---- chunked long-form transcription: the plan on the host (the header's
+// "chunked long-form transcription" states it) ---------------------------------
+// wmi_set_chunking's checks of the fields as given; the reason in err
+int chunk_check_params(const wmi_chunk_params &p, std::string &err);
+// Cmax, Cmin and h with the zeros resolved for a window of `window` frames; WMI_E_INVALID_ARG if Cmin > Cmax or no Cmax
+int chunk_resolve(const wmi_chunk_params &p, int window, int *Cmax, int *Cmin, int *h, std::string &err);
+// n (start, end) pairs: ascending, non-overlapping, start < end, none negative
+int chunk_check_spans(const int64_t *spans, int n, std::string &err);
+// the chain of cuts over P [N + 1] (P may be null while n_len <= Cmax: no cut is then looked for)
+std::vector<int64_t> chunk_plan(const uint64_t *P, int64_t N, int Cmax, int Cmin, int h);
+
 // ---- audio of any rate (DESIGN.md "Audio front end"; the header's "audio of
 // any format" states the plan and the taps) --------------------------------
 // L, M, K of a rate, or WMI_E_UNSUPPORTED outside the plan

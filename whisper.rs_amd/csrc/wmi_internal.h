@@ -398,6 +398,21 @@ struct VadArgs {
     long long *t0, *t1;      // the spans after step B, in 10 ms units; moved in place
 };
 hipError_t launch_token_vad(hipStream_t s, const VadArgs &a, int n_segs);
+// ---- chunked long-form transcription (wmi_chunks.hip; DESIGN.md "Chunked
+// long-form transcription"; the plan is stated in the public header) ----
+struct ChunkPlanRec {
+    const unsigned long long *P;  // the recording's running envelope sum [N + 1] (not read while N / 160 <= Cmax)
+    long long N;                  // its samples
+    long long *out;               // (start, end) pairs [cap]
+    int32_t *count;               // the pairs of the plan (above cap: the list is cut short)
+    int32_t cap;
+};
+// one workgroup a recording (recs: device array [n_recs]); 1 <= Cmin <= Cmax <= 2^20, 1 <= h <= 100
+hipError_t launch_chunk_plan(hipStream_t s, const ChunkPlanRec *recs, int n_recs, int Cmax, int Cmin, int h);
+// launch_mel_window's slot form with slot b's window ending at frame end[b] of its recording
+hipError_t launch_mel_window_end(hipStream_t s, const float *mel, int64_t mel_stride, int n_mel, const int64_t *n_len, int T2,
+                                 int Cp, uint16_t *xconv, int slots, float *xconv32, uint16_t *g1, int n, const int32_t *src,
+                                 const int32_t *off, const int32_t *end);
 // ---- token times from cross-attention alignment (wmi_align.hip; DESIGN.md
 // "Token times from cross-attention alignment"; S1 - S7 in the public header) ----
 constexpr int AL_HEADS_MAX = 32, AL_WIDTH_MAX = 15;

@@ -74,6 +74,8 @@ EXPORTS = (
     "wmi_set_dtw", "wmi_align_tokens", "wmi_dtw_path", "wmi_dtw_path_host", "wmi_get_segment_dtw_of",
     "wmi_audio_to_mel_batch", "wmi_stage_audio", "wmi_transcribe_audio", "wmi_transcribe_audio_batch", "wmi_get_pcm",
     "wmi_get_audio_timing", "wmi_resample_plan", "wmi_resample_taps", "wmi_resampled_length",
+    "wmi_set_chunking", "wmi_set_chunk_spans", "wmi_get_chunk_count", "wmi_get_chunk", "wmi_plan_chunks",
+    "wmi_plan_chunks_host",
     "wmi_pcm_to_mel", "wmi_pcm_to_mel_batch", "wmi_encode", "wmi_decode_greedy", "wmi_decode_logits",
     "wmi_decode_beam", "wmi_full", "wmi_stage_pcm", "wmi_run_staged", "wmi_run_staged_beam", "wmi_get_tokens", "wmi_get_timings", "wmi_sync",
     "wmi_get_mel", "wmi_get_checksums", "wmi_get_encoder_out", "wmi_get_cross_kv", "wmi_bench_kernel", "wmi_decode_alg_bytes",
@@ -143,6 +145,21 @@ class WindowInfo(C.Structure):
     _fields_ = [("seek", C.c_int64), ("n_attempts", C.c_int32), ("temperature", C.c_float),
                 ("avg_logprob", C.c_float), ("entropy", C.c_float), ("no_speech_prob", C.c_float),
                 ("flags", C.c_int32), ("first_segment", C.c_int32), ("n_segments", C.c_int32)]
+
+
+class ChunkParams(C.Structure):
+    """wmi_chunk_params."""
+    _fields_ = [("enable", C.c_int32), ("max_frames", C.c_int32), ("min_frames", C.c_int32),
+                ("smooth_frames", C.c_int32)]
+
+
+class ChunkInfo(C.Structure):
+    """wmi_chunk_info."""
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("first_segment", C.c_int32), ("n_segments", C.c_int32),
+                ("first_window", C.c_int32), ("n_windows", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class Audio(C.Structure):
@@ -235,6 +252,13 @@ def lib():
             L.wmi_dtw_path.argtypes = [vp, vp, C.c_int, C.c_int, vp]
             L.wmi_dtw_path_host.argtypes = [vp, C.c_int, C.c_int, vp]
             L.wmi_get_segment_dtw_of.argtypes = [vp, C.c_int, C.c_int, vp, sz, C.POINTER(i32)]
+        if hasattr(L, "wmi_set_chunking"):  # (as above: an older build has no chunking)
+            L.wmi_set_chunking.argtypes = [vp, C.POINTER(ChunkParams)]
+            L.wmi_set_chunk_spans.argtypes = [vp, C.c_int, vp, C.c_int]
+            L.wmi_get_chunk_count.argtypes = [vp, C.c_int, C.POINTER(i32)]
+            L.wmi_get_chunk.argtypes = [vp, C.c_int, C.c_int, C.POINTER(ChunkInfo)]
+            L.wmi_plan_chunks.argtypes = [vp, C.c_int, vp, sz, C.POINTER(i32)]
+            L.wmi_plan_chunks_host.argtypes = [vp, sz, C.POINTER(ChunkParams), C.c_int, vp, sz, C.POINTER(i32)]
         L.wmi_get_window_count.argtypes = [vp, C.c_int, C.POINTER(i32)]
         L.wmi_get_window_info.argtypes = [vp, C.c_int, C.c_int, C.POINTER(WindowInfo)]
         L.wmi_decode_timestamps_batch.argtypes =[vp, vp, C.c_int, C.c_int, vp, vp]
@@ -840,6 +864,47 @@ class WhisperContext:
         self.n_clips = len(clips)
         return [self.segments_of(c, int(nseg[c])) for c in range(len(clips))]
 
+    # --- chunked long-form transcription --------------------------------------
+    def set_chunking(self, enable: bool = True, max_frames: int = 0, min_frames: int = 0, smooth_frames: int = 0,
+                     default: bool = False) -> None:
+        """transcribe_batch() / transcribe_audio_batch() cut every recording at
+        quiet places into chunks and decode the chunks as the rows of the rounds
+        (wmi_set_chunking; at most min(8, max_clips) rows a round).  0 fields:
+        max_frames = the window, min_frames = max_frames / 2, smooth_frames = 10.
+        enable=False (or default=True: a NULL parameter block) switches it off."""
+        if default:
+            _raise(lib().wmi_set_chunking(self._h, None), self._h)
+            return
+        p = ChunkParams(int(bool(enable)), int(max_frames), int(min_frames), int(smooth_frames))
+        _raise(lib().wmi_set_chunking(self._h, C.byref(p)), self._h)
+
+    def set_chunk_spans(self, spans, clip: int = -1) -> None:
+        """The caller's (start, end) frame spans of recording `clip` (-1: every
+        clip) in later chunked calls, instead of the plan; () = back to the plan."""
+        a = np.ascontiguousarray(spans, dtype=np.int64).reshape(-1, 2)
+        _raise(lib().wmi_set_chunk_spans(self._h, int(clip), _ptr(a) if a.size else None, a.shape[0]), self._h)
+
+    def chunks_of(self, clip: int = 0):
+        """[wmi_chunk_info dict] of recording `clip` in the last chunked call ([] after one with chunking off)."""
+        n = C.c_int32()
+        _raise(lib().wmi_get_chunk_count(self._h, clip, C.byref(n)), self._h)
+        out = []
+        for i in range(n.value):
+            ci = ChunkInfo()
+            _raise(lib().wmi_get_chunk(self._h, clip, i, C.byref(ci)), self._h)
+            out.append(ci.as_dict())
+        return out
+
+    def plan_chunks(self, clip: int = 0) -> np.ndarray:
+        """The built-in plan of loaded recording `clip` on the device: int64 [n][2] (wmi_plan_chunks)."""
+        n = C.c_int32()
+        rc = lib().wmi_plan_chunks(self._h, clip, None, 0, C.byref(n))
+        if rc not in (WMI_OK, NotEnoughSpace.code):
+            _raise(rc, self._h)
+        out = np.zeros((n.value, 2), np.int64)
+        _raise(lib().wmi_plan_chunks(self._h, clip, _ptr(out), n.value, C.byref(n)), self._h)
+        return out
+
     def pcm(self, clip: int = 0) -> np.ndarray:
         """The 16 kHz mono samples clip holds (wmi_get_pcm)."""
         n = C.c_size_t()
@@ -1028,6 +1093,23 @@ def whisper_pcm_to_mel(ctx: WhisperContext, samples) -> None:
 def whisper_encode(ctx: WhisperContext, n_threads: int, mel_offset: int) -> None:
     """main.rs:1799-2063 (n_threads accepted and ignored, as in the reference)."""
     ctx.encode(n_threads, mel_offset)
+
+
+def plan_chunks_host(P, n_samples: int, window: int, max_frames: int = 0, min_frames: int = 0,
+                     smooth_frames: int = 0) -> np.ndarray:
+    """The built-in chunk plan from the running envelope sum P (uint64
+    [n_samples + 1]) on the host, no context: int64 [n][2] (wmi_plan_chunks_host)."""
+    P = np.ascontiguousarray(P, dtype=np.uint64)
+    if P.size < int(n_samples) + 1:
+        raise ValueError(f"P holds {P.size} entries for {n_samples} samples")
+    p = ChunkParams(0, int(max_frames), int(min_frames), int(smooth_frames))
+    n = C.c_int32()
+    rc = lib().wmi_plan_chunks_host(_ptr(P), int(n_samples), C.byref(p), int(window), None, 0, C.byref(n))
+    if rc not in (WMI_OK, NotEnoughSpace.code):
+        _raise(rc)
+    out = np.zeros((n.value, 2), np.int64)
+    _raise(lib().wmi_plan_chunks_host(_ptr(P), int(n_samples), C.byref(p), int(window), _ptr(out), n.value, C.byref(n)))
+    return out
 
 
 def dtw_path_host(cost):
