@@ -376,6 +376,65 @@ typedef struct wmi_window_info {
 int wmi_get_window_count(const wmi_context *ctx, int clip, int32_t *n);
 int wmi_get_window_info(const wmi_context *ctx, int clip, int i, wmi_window_info *out);
 
+/* ---- best-of-N sampled attempts ------------------------------------------ */
+
+/* A best-of window of N candidates (1 <= N <= 8) of an encoded clip after
+ * `prompt`, at temperature T in (0, 1], as attempt ordinal n of `seed`
+ * (OpenAI's and whisper.cpp's best_of).
+ * Candidates and keys: candidate c has the stream key k_0 = sm64(seed + n)
+ * (wmi_decode_timestamps_sampled's key) and k_c = sm64(k_0 + c * 2^32) for
+ * c >= 1; its draws are u_t = (sm64(k_c + t) >> 11) * 2^-53 as there.  Each
+ * candidate is a window of wmi_decode_timestamps_sampled with that key; with
+ * rules enabled a window of wmi_decode_timestamps_ruled, with a history of
+ * its own.
+ * Shared first step: candidate c's first generated token is drawn from the
+ * logits of the prompt's last step.  That step is computed once, on one
+ * decoder row, and every candidate reads the same row; the no-speech
+ * probability is that row's and is computed once.  From the second generated
+ * step on candidate c decodes on a decoder row of its own, after its own
+ * tokens; the prompt's keys and values are read where the one row left them
+ * (nothing is copied).  A candidate that has drawn EOT writes no further
+ * record and feeds EOT.  The window ends when every candidate has met EOT, or
+ * at max_tokens.
+ * Ranking: n_c = candidate c's records, EOT included; S_c = the sum of its
+ * f32 log-probabilities (plog), taken in float64 in index order; a_c = S_c /
+ * n_c.  The chosen candidate is the one with the largest a_c, ties to the
+ * lowest c.  a_c is wmi_set_fallback's avg_logprob: one figure serves the
+ * ranking and the threshold (OpenAI divides by the length without EOT for the
+ * ranking and with it for the threshold).
+ * N = 1 is exactly wmi_decode_timestamps_sampled / wmi_decode_timestamps_ruled:
+ * the same kernels and the same bits.
+ *
+ * wmi_set_best_of: best_of 1..8, default 1; anything else WMI_E_INVALID_ARG.
+ * Holds until changed.  Above 1, every attempt of wmi_transcribe /
+ * wmi_transcribe_audio at T > 0 under wmi_set_fallback is a best-of window:
+ * the chosen candidate is judged and committed as the single draw is, and one
+ * attempt still takes one ordinal n.  Attempts at T = 0 are untouched (the
+ * greedy pick, the beam window or the ruled beam window).
+ * wmi_transcribe_batch, wmi_transcribe_audio_batch and chunked calls are
+ * WMI_E_UNSUPPORTED, checked at the call, when best_of is above 1 and a
+ * temperature above 0 can be reached (temperature > 0 or temperature_inc >
+ * 0): as for a beam size, the rows do not fit.  With best_of 1 every call
+ * runs the kernels and code objects it ran before this interface. */
+int wmi_set_best_of(wmi_context *ctx, int best_of);
+/* One best-of window of the encoded clip 0.  out[max_tokens], *n_out and
+ * plog[max_tokens] (optional) receive the chosen candidate, *p_nosp
+ * (optional) the no-speech probability, *chosen (optional) its index;
+ * cand_avg[best_of] and cand_len[best_of] (optional) every candidate's a_c
+ * and n_c.  Rules are used if enabled.  best_of outside [1, 8], or above 1
+ * with temperature at or below 0: WMI_E_INVALID_ARG. */
+int wmi_decode_timestamps_best_of(wmi_context *ctx, int best_of, const int32_t *prompt, int n_prompt, int max_tokens,
+                                  float temperature, uint64_t seed, int n, wmi_token_data *out, int32_t *n_out,
+                                  float *plog, float *p_nosp, int32_t *chosen, float *cand_avg, int32_t *cand_len);
+/* *key = k_c of attempt ordinal n of `seed` (host only: needs no context and
+ * no device).  n < 0 or c outside [0, 8): WMI_E_INVALID_ARG. */
+int wmi_best_of_key(uint64_t seed, int n, int c, uint64_t *key);
+/* Of the window that wmi_get_window_info(ctx, clip, i) describes: the
+ * candidate that became its result and the candidates its attempt drew.
+ * *chosen is -1 (and *n_candidates 0) when the window's result did not come
+ * from a best-of attempt. */
+int wmi_get_window_candidate(const wmi_context *ctx, int clip, int i, int32_t *chosen, int32_t *n_candidates);
+
 /* OpenAI's decoding rules (SuppressTokens and ApplyTimestampRules restated)
  * for every window of wmi_transcribe / wmi_transcribe_batch and for
  * wmi_decode_timestamps_ruled, in the place of the whisper.cpp-1.0.3 rule.
@@ -871,7 +930,13 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * pairs, -1 behind the last; 33 = that call's chunks, rounds and summed rows
  * over the rounds (int64 [3], host); 34 = hipEvent ms of the last k_chunk_plan
  * launch (double, host; -1 before one).  In a chunked call 22's recording
- * column names the recording each slot's chunk belongs to. */
+ * column names the recording each slot's chunk belongs to.  35 = the last
+ * best-of window (int32 [4], host): its candidates N, the decoder steps run
+ * on one row, the decoder steps run on N rows, and the chosen candidate (-1
+ * before one).  36 = every candidate of that window (int32 words, host): N,
+ * M = the longest candidate's records, len [N], the records [N][M] of six
+ * words {id, tid, p, pt, ptsum (f32 bits), 0} (-1 behind a candidate's end),
+ * and plog [N][M] (f32 bits, 0 behind the end). */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

@@ -143,6 +143,13 @@ struct wmi_context {
     SampRow *d_samp_rows = nullptr;  // one allocation: rows [8], p_nosp [8], plog [8][n_text_ctx]
     float *d_samp_nosp = nullptr, *d_samp_plog = nullptr;
     std::vector<std::vector<wmi_window_info>> windows;  // per recording of the last transcribe under fb_on
+    // best-of-N sampled attempts (wmi_set_best_of; wmi_bestof.hip)
+    int best_of = 1;            // candidates of a T > 0 attempt of wmi_transcribe (1: the single draw)
+    int32_t bo_count[4] = {0, 0, 0, -1};  // the last best-of window: N, steps on one row, steps on N rows, chosen (debug read 35)
+    std::vector<std::vector<TsRec>> bo_rec;   // ... and every candidate's records
+    std::vector<std::vector<float>> bo_plog;  // ... and log-probabilities (debug read 36)
+    // per window of `windows`: {chosen candidate (-1: not a best-of attempt), candidates} (wmi_get_window_candidate)
+    std::vector<std::vector<std::pair<int32_t, int32_t>>> win_cand;
     // batched transcription: source recording [8], then mel offset [8] of each encoder slot, then (chunked calls) its end [8]
     int32_t *d_win = nullptr;
     int32_t win_host[3 * DEC_ROWS] = {};  // host copy of the last d_win upload (debug read 22: its first two columns)
@@ -1287,6 +1294,12 @@ struct DecRun {
     int align = 0;
     // RUN_TS of several rows whose prompts differ in length: row b's starts at step d_lo[b] (run_ts_rows)
     int ragged = 0;
+    // RUN_TS with sampled, a best-of window (run_best_of).  cands: the B rows are candidates of clip b0, the one-clip
+    // geometry of a beam run without its kernels: every row reads clip b0's cross K/V, self-attention keys below the
+    // current position come from the cache slot the kv_src table names, and a row feeds dts_tok.  fan (B = 1, the
+    // prompt's row): -1 no sampler follows the step (the prompt is being fed); N > 0 the fan-out sampler for N
+    // candidates follows it (launch_bestof_fan)
+    int cands = 0, fan = 0;
 };
 
 // beam-step kernel arguments of a beam run
@@ -1337,9 +1350,17 @@ TsArgs ts_args(wmi_context *ctx, const DecRun &run) {
 // (after the last kernel of a chain step, after a one-step persistent launch)
 int enqueue_step_tail(wmi_context *ctx, const DecRun &run) {
     if (run.kind == RUN_TS && run.sampled) {
+        if (run.fan < 0) return WMI_OK;
         TsSampArgs sa{};
         sa.t = ts_args(ctx, run);
         sa.rows = ctx->d_samp_rows; sa.plog = ctx->d_samp_plog; sa.p_nosp = ctx->d_samp_nosp;
+        if (run.fan > 0) {  // the prompt's last step of a best-of window: one row of logits, N picks
+            TsRuleArgs ra{};
+            sa.t.B = run.fan;
+            ra.s = sa; ra.m0 = ctx->d_rule_m0; ra.hist = ctx->d_rule_hist; ra.max_initial_ts = ctx->max_initial_ts;
+            HIPCHK(ctx, launch_bestof_fan(ctx->stream, ra, run.ruled != 0));
+            return WMI_OK;
+        }
         if (run.ruled) {
             TsRuleArgs ra{};
             ra.s = sa; ra.m0 = ctx->d_rule_m0; ra.hist = ctx->d_rule_hist; ra.max_initial_ts = ctx->max_initial_ts;
@@ -1422,7 +1443,7 @@ int enqueue_dec_step(wmi_context *ctx, const DecRun &run) {
         at.reset_amax = (l == 0 && !beam) ? ctx->damax : nullptr;
         at.clip_div = 1;
         if (run.ragged) at.lo = ctx->d_lo;
-        if (beam) {
+        if (beam || run.cands) {
             at.kv_src = ctx->dkvsrc;
             at.kv_src_stride = hp.n_text_ctx;
         }
@@ -1456,7 +1477,7 @@ int enqueue_dec_step(wmi_context *ctx, const DecRun &run) {
         at.sync = ctx->use_coop ? ctx->dsync + (size_t)l * 8 * H : nullptr;
         if (f32) { at.Wq = nullptr; at.q = ctx->dq16; at.sync = nullptr; }
         at.err = ctx->derr;
-        at.clip_div = beam ? B : 1;  // beam rows all read clip b0's cross K/V
+        at.clip_div = beam || run.cands ? B : 1;  // beam rows (and a best-of window's candidates) all read clip b0's cross K/V
         if (fuse_wo) {
             at.res_parts = ctx->dwoparts; at.res_bias = d.bo; at.x_out = X[cur ^ 1];
             cur ^= 1;
@@ -1504,7 +1525,7 @@ int enqueue_dec_step(wmi_context *ctx, const DecRun &run) {
     // WMI_LOGITS_ALL: what the persistent launches keep — a greedy run's rows
     // b0.., a beam step's [K][V] — so a debug read 13 of a chain decode holds
     // the decode's logits, not the buffer's zeros
-    if (ctx->d_lgall && (run.kind == RUN_GREEDY || beam || (ts && run.sampled)) && (beam ? 0 : b0) + B <= ctx->lg_rows)
+    if (ctx->d_lgall && (run.kind == RUN_GREEDY || beam || (ts && run.sampled && !run.cands)) && (beam ? 0 : b0) + B <= ctx->lg_rows)
         HIPCHK(ctx, launch_logits_capture(s, ctx->dlogits, ctx->d_lgall + (beam ? 0 : (size_t)b0 * hp.n_vocab), ctx->dstate,
                                           B, hp.n_vocab, (int64_t)ctx->lg_rows * hp.n_vocab, hp.n_text_ctx));
     return enqueue_step_tail(ctx, run);
@@ -1564,6 +1585,16 @@ int finish_run(wmi_context *ctx) {
     return err ? dec_err(ctx, err) : WMI_OK;
 }
 
+// the step tail of a RUN_TS run in the graph key: 1 k_ts_sample, 3 k_ts_sample_t, 5 k_ts_sample_r; a best-of window's
+// 8 / 9 the fan-out sampler (plain / ruled; its N is a field of its own), 10 none, 11 / 12 k_ts_sample_t / _r on
+// candidate rows
+int ts_tail_code(const DecRun &run) {
+    if (run.fan > 0) return run.ruled ? 9 : 8;
+    if (run.fan < 0) return 10;
+    if (run.cands) return run.ruled ? 12 : 11;
+    return run.ruled ? 5 : run.sampled ? 3 : 1;
+}
+
 // run `steps` decoder steps of the run, the first at position pos0, via
 // captured hipGraphs: one per configuration and self-attention key capacity,
 // so a chunk is split where pos + 1 crosses 64 / 128 / 256
@@ -1589,11 +1620,11 @@ int run_dec_steps(wmi_context *ctx, const DecRun &run0, int pos0, int steps) {
             char key[192];
             // (a forced step enqueues what a greedy step does: they share graphs)
             // (... but an aligned one also captures scores: a field of its own)
-            snprintf(key, sizeof key, "%d/%d/%d/%d/%d/%d/%d/%d/%p/%p/%d/%d/%d/%d/%d/%d/%d", run.b0, run.B, run.feed_len,
+            snprintf(key, sizeof key, "%d/%d/%d/%d/%d/%d/%d/%d/%p/%p/%d/%d/%d/%d/%d/%d/%d/%d", run.b0, run.B, run.feed_len,
                      run.feed_stride, run.suppress_eot, run.out_stride, ctx->enc_T, ctx->enc_clips, (void *)ctx->dfeed,
                      (void *)ctx->dtokens, run.K, run.max_tokens, mk,
-                     run.kind == RUN_TS ? (run.ruled ? 5 : run.sampled ? 3 : 1) : run.ts_beam ? (run.ruled ? (run.nosp ? 7 : 6) : run.nosp ? 4 : 2) : 0,
-                     reps, run.align, run.ragged);
+                     run.kind == RUN_TS ? ts_tail_code(run) : run.ts_beam ? (run.ruled ? (run.nosp ? 7 : 6) : run.nosp ? 4 : 2) : 0,
+                     reps, run.align, run.ragged, run.fan);
             auto it = ctx->graphs.find(key);
             if (it == ctx->graphs.end()) {
                 if (ctx->graphs.size() >= 32) ctx->clear_graphs();
@@ -1708,7 +1739,7 @@ PersistArgs persist_args(wmi_context *ctx, const DecRun &run, int G) {
     const wmi_hparams &hp = ctx->hp;
     const int n = hp.n_text_state, H = hp.n_text_head, T = ctx->enc_T;
     const int b0 = run.b0, B = run.B, out_stride = run.out_stride;
-    const bool beam = run.kind == RUN_BEAM;
+    const bool beam = run.kind == RUN_BEAM || run.cands;  // (the one-clip geometry: hypotheses, or a best-of window's candidates)
     PersistArgs a{};
     a.layers = ctx->d_players; a.te = ctx->te; a.pe = ctx->d_pe; a.dln_w = ctx->dln_w; a.dln_b = ctx->dln_b;
     a.gelu_tab = ctx->gelu_tab; a.exp_tab = ctx->exp_tab; a.n_exp = ctx->n_exp; a.exp_fb = ctx->d_expfb;
@@ -1771,6 +1802,7 @@ PersistArgs persist_args(wmi_context *ctx, const DecRun &run, int G) {
         a.kv_src = ctx->dkvsrc;
         a.kv_src_stride = hp.n_text_ctx;
         a.tokens_out = ctx->dtokens;  // (unused: no argmax in beam mode)
+        if (run.cands) a.cur_tok = ctx->dts_tok;  // (candidate c feeds what the sampler picked for it)
     } else {
         a.out_stride = 0;  // (record no token: dtokens holds decode results)
         // the timestamp sampler picks the next token into dts_tok, which the next launch feeds
@@ -1846,7 +1878,7 @@ int advance_run(wmi_context *ctx, const DecRun &run, RunGrid gr, int pos0, int s
             if (run.kind == RUN_BEAM && ctx->d_lgall && s_all < hp.n_text_ctx)  // WMI_LOGITS_ALL: this step's [K][V]
                 HIPCHK(ctx, hipMemcpyAsync(ctx->d_lgall + (size_t)s_all * ctx->lg_rows * hp.n_vocab, ctx->dlogits,
                                            (size_t)run.K * hp.n_vocab * 4, hipMemcpyDeviceToDevice, ctx->stream));
-            if (run.kind == RUN_TS && run.sampled && ctx->d_lgall && s_all < hp.n_text_ctx && run.b0 + run.B <= ctx->lg_rows)
+            if (run.kind == RUN_TS && run.sampled && !run.cands && ctx->d_lgall && s_all < hp.n_text_ctx && run.b0 + run.B <= ctx->lg_rows)
                 HIPCHK(ctx, hipMemcpyAsync(ctx->d_lgall + ((size_t)s_all * ctx->lg_rows + run.b0) * hp.n_vocab, ctx->dlogits,
                                            (size_t)run.B * hp.n_vocab * 4, hipMemcpyDeviceToDevice, ctx->stream));
             int rc = enqueue_step_tail(ctx, run);
@@ -2157,6 +2189,20 @@ int ensure_samp_buffers(wmi_context *ctx) {
     return WMI_OK;
 }
 
+// the rows' next tokens, done words, rule histories and starts (one allocation), and their records
+int ensure_ts_buffers(wmi_context *ctx) {
+    if (ctx->dts_tok) return WMI_OK;
+    const size_t nb = 2 * DEC_ROWS * 4 + DEC_ROWS * sizeof(RuleHist) + DEC_ROWS * 4;
+    HIPCHK(ctx, hipMalloc(&ctx->dts_tok, nb));
+    HIPCHK(ctx, hipMemset(ctx->dts_tok, 0, nb));
+    ctx->dts_done = ctx->dts_tok + DEC_ROWS;
+    ctx->d_rule_hist = (RuleHist *)(ctx->dts_done + DEC_ROWS);
+    ctx->d_lo = (int32_t *)(ctx->d_rule_hist + DEC_ROWS);
+    HIPCHK(ctx, hipMalloc(&ctx->dts_rec, (size_t)DEC_ROWS * ctx->hp.n_text_ctx * sizeof(TsRec)));
+    ctx->clear_graphs();
+    return WMI_OK;
+}
+
 // Rows [b0, b0 + B) of the encoded batch, row b after the np tokens feed[b * np ..).
 // With `lens` the rows' prompts differ in length: feed holds them one behind
 // the other, row b's lens[b] tokens, and np is ignored.  The run then takes
@@ -2207,17 +2253,9 @@ int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &fee
     if (np < 1 || max_tokens < 1 || np + max_tokens > hp.n_text_ctx)
         return set_err(ctx, WMI_E_INVALID_ARG, "prompt %d + max_tokens %d exceed n_text_ctx %d", np, max_tokens,
                        hp.n_text_ctx);
-    if (!ctx->dts_tok) {
-        const size_t nb = 2 * DEC_ROWS * 4 + DEC_ROWS * sizeof(RuleHist) + DEC_ROWS * 4;
-        HIPCHK(ctx, hipMalloc(&ctx->dts_tok, nb));
-        HIPCHK(ctx, hipMemset(ctx->dts_tok, 0, nb));
-        ctx->dts_done = ctx->dts_tok + DEC_ROWS;
-        ctx->d_rule_hist = (RuleHist *)(ctx->dts_done + DEC_ROWS);
-        ctx->d_lo = (int32_t *)(ctx->d_rule_hist + DEC_ROWS);
-        HIPCHK(ctx, hipMalloc(&ctx->dts_rec, (size_t)DEC_ROWS * hp.n_text_ctx * sizeof(TsRec)));
-        ctx->clear_graphs();
-    }
-    int rc = ensure_decode_buffers(ctx, DEC_ROWS * np, 1);
+    int rc = ensure_ts_buffers(ctx);
+    if (rc) return rc;
+    rc = ensure_decode_buffers(ctx, DEC_ROWS * np, 1);
     if (rc) return rc;
     ctx->ts_prompt = ragged ? shown : feed;
     ctx->ts_lo[0] = B;
@@ -2289,6 +2327,141 @@ int run_ts_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt
     int rc = run_ts_rows(ctx, clip, 1, prompt, (int)prompt.size(), max_tokens, &rows);
     if (rc) return rc;
     *out = std::move(rows[0]);
+    return WMI_OK;
+}
+
+// ---- best-of-N sampled windows (wmi_set_best_of; the semantics are stated in the public header) ----
+// candidate c's stream key of attempt ordinal n of `seed`
+uint64_t best_of_key(uint64_t seed, uint64_t n, int c) {
+    const uint64_t k0 = sm64(seed + n);
+    return c == 0 ? k0 : sm64(k0 + ((uint64_t)c << 32));
+}
+
+// The candidate with the largest mean log-probability (the sum in double in index order over the f32 values, EOT
+// included; ties: the lowest c).  avg [N] optional.
+int best_of_choose(const std::vector<std::vector<float>> &plog, double *avg) {
+    int best = 0;
+    double a_best = 0.0;
+    for (size_t c = 0; c < plog.size(); ++c) {
+        double S = 0.0;
+        for (float v : plog[c]) S += (double)v;
+        const double a = plog[c].empty() ? 0.0 : S / (double)plog[c].size();
+        if (avg) avg[c] = a;
+        if (c == 0 || a > a_best) { best = (int)c; a_best = a; }
+    }
+    return best;
+}
+
+// N >= 2 candidates of encoded clip `clip` after `prompt` at temperature T > 0, candidate c with stream key key[c],
+// in two phases under one DecState.  Phase 1: the prompt's np steps as a one-row run on cache slot 0, the fan-out
+// sampler behind the last (every candidate's first token from the one row of logits).  Phase 2: N rows from
+// position np, each after its own tokens, k_ts_sample_t / _r behind every step; kv_src[c][j] = 0 for j < np and c
+// from np on, so every candidate reads the prompt's keys from slot 0 and no cache row is copied.  Ends when every
+// candidate has met EOT, or at max_tokens.  The candidates' records and log-probabilities are kept for debug read 36
+// and the step counts for 35.
+int run_best_of(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, int N, int max_tokens, float T,
+                const uint64_t *key, bool ruled, std::vector<std::vector<TsRec>> *recs, std::vector<std::vector<float>> *plog,
+                float *p_nosp) {
+    const wmi_hparams &hp = ctx->hp;
+    const int np = (int)prompt.size();
+    if (ctx->enc_T <= 0) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
+    if (N < 2 || N > DEC_ROWS || clip < 0 || clip >= ctx->enc_clips)
+        return set_err(ctx, WMI_E_INVALID_ARG, "%d candidates of clip %d (%d encoded clips)", N, clip, ctx->enc_clips);
+    if (np < 1 || max_tokens < 1 || np + max_tokens > hp.n_text_ctx)
+        return set_err(ctx, WMI_E_INVALID_ARG, "prompt %d + max_tokens %d exceed n_text_ctx %d", np, max_tokens,
+                       hp.n_text_ctx);
+    int rc = samp_supported(ctx);
+    if (rc) return rc;
+    rc = ensure_ts_buffers(ctx);
+    if (rc) return rc;
+    rc = ensure_decode_buffers(ctx, DEC_ROWS * np, 1);
+    if (rc) return rc;
+    rc = ensure_samp_buffers(ctx);
+    if (rc) return rc;
+    ctx->ts_prompt = prompt;
+    ctx->ts_lo[0] = 1;
+    ctx->ts_lo[1] = np;
+    memset(ctx->ts_lo + 2, 0, DEC_ROWS * 4);
+    SampRow srows[DEC_ROWS] = {};
+    for (int c = 0; c < N; ++c) { srows[c].T = T; srows[c].key = key[c]; }
+    std::vector<int32_t> table((size_t)N * hp.n_text_ctx);
+    for (int c = 0; c < N; ++c)
+        for (int j = 0; j < hp.n_text_ctx; ++j) table[(size_t)c * hp.n_text_ctx + j] = j < np ? 0 : c;
+    DecRun feed_run{RUN_TS, clip, 1, np, np};
+    feed_run.sampled = 1;
+    feed_run.ruled = ruled ? 1 : 0;
+    DecRun cand_run = feed_run;
+    cand_run.B = N;
+    cand_run.cands = 1;
+    const int total2 = max_tokens - 1;  // steps on N rows at most
+    int steps2 = 0;
+    do {
+        const RunGrid g1 = run_grid(ctx, feed_run), g2 = run_grid(ctx, cand_run);
+        rc = reset_run(ctx, true, g1.G, 0, false, prompt.data(), np, true, ruled);
+        if (rc) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_samp_rows, srows, sizeof srows, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->dkvsrc, table.data(), table.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        // phase 1: no sampler behind a step that feeds the prompt, the fan-out sampler behind the last
+        DecRun r1 = feed_run;
+        r1.fan = -1;
+        if (np > 1) {
+            rc = advance_run(ctx, r1, g1, 0, np - 1);
+            if (rc) return rc;
+        }
+        r1.fan = N;
+        rc = advance_run(ctx, r1, g1, np - 1, 1);
+        if (rc) return rc;
+        // between the phases: pos stays.  The exchange blocks of the N-row grid start from zero; on the kernel
+        // chain the cooperative cross-attention's arrival counters, which only row 0 has advanced (or no row, where
+        // phase 1 ran on the persistent decoder), stand for every row where np steps leave them: np * chunks
+        if (g2.G > 0) {
+            HIPCHK(ctx, hipMemsetAsync(ctx->d_xg, 0, ctx->xg_bytes, ctx->stream));
+        } else if (ctx->use_coop && total2 > 0) {
+            std::vector<XSync> sy(ctx->sync_bytes / sizeof(XSync));
+            const uint32_t cnt = (uint32_t)np * (uint32_t)((ctx->enc_T + 127) / 128);
+            for (XSync &x : sy) { memset(&x, 0, sizeof x); x.cnt = cnt; }
+            HIPCHK(ctx, hipMemcpyAsync(ctx->dsync, sy.data(), ctx->sync_bytes, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (sy leaves scope)
+        }
+        // phase 2
+        steps2 = 0;
+        while (steps2 < total2) {
+            const int chunk = std::min(16, total2 - steps2);
+            rc = advance_run(ctx, cand_run, g2, np + steps2, chunk);
+            if (rc) return rc;
+            steps2 += chunk;
+            if (steps2 >= total2) break;
+            int32_t dn[DEC_ROWS];
+            HIPCHK(ctx, hipMemcpyAsync(dn, ctx->dts_done, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            bool all = true;
+            for (int c = 0; c < N; ++c) all = all && dn[c] != 0;
+            if (all) break;
+        }
+        const int have = 1 + steps2;  // records written so far (per candidate that has not met EOT)
+        recs->assign((size_t)N, std::vector<TsRec>((size_t)have));
+        plog->assign((size_t)N, std::vector<float>((size_t)have));
+        for (int c = 0; c < N; ++c) {
+            HIPCHK(ctx, hipMemcpyAsync((*recs)[c].data(), ctx->dts_rec + (size_t)c * hp.n_text_ctx, (size_t)have * sizeof(TsRec),
+                                       hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync((*plog)[c].data(), ctx->d_samp_plog + (size_t)c * hp.n_text_ctx, (size_t)have * 4,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIPCHK(ctx, hipMemcpyAsync(p_nosp, ctx->d_samp_nosp, 4, hipMemcpyDeviceToHost, ctx->stream));
+        rc = finish_run(ctx);
+    } while (rc == RERUN_ON_CHAIN);
+    if (rc) return rc;
+    // (a candidate that met EOT wrote nothing behind it: what lies there is stale)
+    for (int c = 0; c < N; ++c) {
+        auto &r = (*recs)[c];
+        for (size_t i = 0; i < r.size(); ++i)
+            if (r[i].id == ctx->sp.eot) { r.resize(i + 1); break; }
+        (*plog)[c].resize(r.size());
+    }
+    ctx->last_run_steps = np + steps2;
+    ctx->bo_count[0] = N; ctx->bo_count[1] = np; ctx->bo_count[2] = steps2; ctx->bo_count[3] = -1;
+    ctx->bo_rec = *recs;
+    ctx->bo_plog = *plog;
     return WMI_OK;
 }
 
@@ -2717,6 +2890,7 @@ TrRun tr_begin(wmi_context *ctx, int R, int max_tokens, bool carry, const std::v
     ctx->results.assign(lists, {});
     ctx->windows.clear();
     if (ctx->fb_on) ctx->windows.assign(lists, {});
+    ctx->win_cand.assign(ctx->windows.size(), {});
     ctx->ck_info.clear();
     return tr;
 }
@@ -2773,6 +2947,7 @@ struct TrAttempt {
     std::vector<TsRec> toks;
     double logprob_sum;
     float p_nosp, T;
+    int chosen = -1, n_cand = 0;  // a best-of attempt: the candidate that became toks, and their number
 };
 // The recordings `rows` sit in the encoded rows 0..B-1 and row b is fed the np
 // tokens feed[b * np ..): each row's attempt at its recording's temperature.
@@ -2797,6 +2972,23 @@ int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows,
         // (rules on: the caller has checked wmi_set_rules_beam, and the window is the ruled beam window)
         return run_ts_beam_window(ctx, 0, feed, ctx->beam_size, tr.n_max, &a.toks, fb ? &a.logprob_sum : nullptr,
                                   fb ? &a.p_nosp : nullptr, ctx->rules_on);
+    }
+    if (ctx->best_of > 1 && fb && (*out)[0].T > 0.0f) {  // a best-of window: the chosen candidate is the attempt
+        if (B != 1 || lens) return set_err(ctx, WMI_E_UNSUPPORTED, "a best-of window decodes one recording (%d rows)", B);
+        TrAttempt &a = (*out)[0];
+        const int N = ctx->best_of;
+        uint64_t key[DEC_ROWS] = {};
+        const uint64_t n = tr.recs[rows[0]].n_samp++;  // (one attempt, one ordinal)
+        for (int c = 0; c < N; ++c) key[c] = best_of_key(ctx->fb.seed, n, c);
+        std::vector<std::vector<TsRec>> recs;
+        std::vector<std::vector<float>> plog;
+        int rc = run_best_of(ctx, 0, feed, N, tr.n_max, a.T, key, ctx->rules_on, &recs, &plog, &a.p_nosp);
+        if (rc) return rc;
+        a.chosen = ctx->bo_count[3] = best_of_choose(plog, nullptr);
+        a.n_cand = N;
+        a.toks = std::move(recs[a.chosen]);
+        for (float v : plog[a.chosen]) a.logprob_sum += (double)v;
+        return WMI_OK;
     }
     TsSampled sp;
     for (int b = 0; b < B && fb; ++b) {
@@ -2881,6 +3073,7 @@ int tr_settle(wmi_context *ctx, const TrRun &tr, TrRec &rec, int slot, TrAttempt
     }
     wi.n_segments = (int32_t)res.segments.size() - wi.first_segment;
     ctx->windows[rec.out].push_back(wi);
+    ctx->win_cand[rec.out].push_back({silence ? -1 : a.chosen, silence ? 0 : a.n_cand});
     rec.att = 0;
     rec.seek += delta;
     return WMI_OK;
@@ -3057,6 +3250,7 @@ void ck_merge(wmi_context *ctx, int R, const std::vector<TrChunk> &chunks) {
     }
     ctx->results = std::move(merged);
     ctx->windows = std::move(wins);
+    ctx->win_cand.clear();  // (no chunked call holds a best-of attempt: wmi_get_window_candidate reports none)
 }
 
 // wmi_transcribe_batch: every loaded recording through whisper_full's loop,
@@ -3790,6 +3984,62 @@ static int wmi_decode_timestamps_ruled_beam_impl(wmi_context *ctx, int beam_size
     return WMI_OK;
 }
 
+// A best-of window puts N candidates of one recording on the decoder rows: as for a beam size, the rows of a batch
+// (and the chunks of a chunked call) do not fit beside them.  Refused only where a temperature above 0 can be reached.
+static int best_of_unsupported(wmi_context *ctx, const char *what) {
+    if (ctx->best_of > 1 && ctx->fb_on && (ctx->fb.temperature > 0.0f || ctx->fb.temperature_inc > 0.0f))
+        return set_err(ctx, WMI_E_UNSUPPORTED, "%s draws one sample an attempt: best_of %d is set and a temperature above 0 "
+                       "can be reached (wmi_set_best_of(ctx, 1), or wmi_transcribe per recording)", what, ctx->best_of);
+    return WMI_OK;
+}
+
+// N candidates of one window of clip 0, the chosen one returned (N = 1: wmi_decode_timestamps_sampled / _ruled itself)
+static int wmi_decode_timestamps_best_of_impl(wmi_context *ctx, int best_of, const int32_t *prompt, int n_prompt, int max_tokens,
+                                              float temperature, uint64_t seed, int n, wmi_token_data *out, int32_t *n_out,
+                                              float *plog, float *p_nosp, int32_t *chosen, float *cand_avg, int32_t *cand_len) {
+    int rc = check_ts_args(ctx, prompt, n_prompt, max_tokens, out, n_out);
+    if (rc) return rc;
+    if (best_of < 1 || best_of > DEC_ROWS) return set_err(ctx, WMI_E_INVALID_ARG, "best_of %d outside [1, %d]", best_of, DEC_ROWS);
+    if (!(temperature >= 0.0f && temperature <= 1.0f) || n < 0)
+        return set_err(ctx, WMI_E_INVALID_ARG, "temperature %g outside [0, 1], or attempt ordinal %d below 0",
+                       (double)temperature, n);
+    if (best_of > 1 && !(temperature > 0.0f))
+        return set_err(ctx, WMI_E_INVALID_ARG, "best_of %d at temperature 0: every candidate would be the same", best_of);
+    rc = samp_supported(ctx);
+    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const std::vector<int32_t> pr(prompt, prompt + n_prompt);
+    std::vector<std::vector<TsRec>> recs;
+    std::vector<std::vector<float>> pl;
+    float nosp = 0.0f;
+    if (best_of == 1) {  // the sampled (or ruled) window: the same kernels, the same bits
+        TsSampled sp;
+        sp.T[0] = temperature;
+        if (temperature > 0.0f) sp.key[0] = best_of_key(seed, (uint64_t)n, 0);
+        rc = run_ts_rows(ctx, 0, 1, pr, n_prompt, max_tokens, &recs, &sp, ctx->rules_on);
+        if (rc) return rc;
+        pl = sp.plog;
+        nosp = sp.p_nosp[0];
+    } else {
+        uint64_t key[DEC_ROWS] = {};
+        for (int c = 0; c < best_of; ++c) key[c] = best_of_key(seed, (uint64_t)n, c);
+        rc = run_best_of(ctx, 0, pr, best_of, max_tokens, temperature, key, ctx->rules_on, &recs, &pl, &nosp);
+        if (rc) return rc;
+    }
+    double avg[DEC_ROWS] = {};
+    const int best = best_of_choose(pl, avg);
+    if (best_of > 1) ctx->bo_count[3] = best;
+    copy_out_tokens(recs[best], out, n_out);
+    if (plog) std::copy(pl[best].begin(), pl[best].end(), plog);
+    if (p_nosp) *p_nosp = nosp;
+    if (chosen) *chosen = best;
+    for (int c = 0; c < best_of; ++c) {
+        if (cand_avg) cand_avg[c] = (float)avg[c];
+        if (cand_len) cand_len[c] = (int32_t)recs[c].size();
+    }
+    return WMI_OK;
+}
+
 static int wmi_transcribe_impl(wmi_context *ctx, const float *pcm, size_t n_samples, int max_tokens, int32_t *n_segments) {
     if (!valid(ctx) || (!pcm && n_samples) || max_tokens < 1 || !n_segments) return WMI_E_INVALID_ARG;
     int rcr = rules_beam_unsupported(ctx, ctx->beam_size);
@@ -3877,6 +4127,7 @@ static int wmi_transcribe_batch_impl(wmi_context *ctx, int n_clips, const float 
     if (ctx->beam_size > 1)  // (8 recordings x K hypotheses do not fit the 8 decoder rows; no silent greedy)
         return set_err(ctx, WMI_E_UNSUPPORTED, "wmi_transcribe_batch decodes greedily only: beam size %d is set "
                        "(wmi_set_beam_size(ctx, 1), or wmi_transcribe per recording)", ctx->beam_size);
+    if (best_of_unsupported(ctx, "wmi_transcribe_batch")) return WMI_E_UNSUPPORTED;
     for (int c = 0; c < n_clips; ++c)  // (wmi_set_language / wmi_set_task refuse these; checked where they are used)
         if (ctx->n_lang == 0 && (ctx->lang_set[c] != 0 || ctx->task != WMI_TASK_TRANSCRIBE))
             return set_err(ctx, WMI_E_INVALID_ARG, "language %d / task %d on an English-only model (clip %d)",
@@ -4233,6 +4484,34 @@ int wmi_set_beam_size(wmi_context *ctx, int beam_size) {
     return WMI_OK;
 }
 
+int wmi_set_best_of(wmi_context *ctx, int best_of) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    if (best_of < 1 || best_of > DEC_ROWS)
+        return set_err(ctx, WMI_E_INVALID_ARG, "best_of %d outside [1, %d]", best_of, DEC_ROWS);
+    ctx->best_of = best_of;
+    return WMI_OK;
+}
+
+int wmi_best_of_key(uint64_t seed, int n, int c, uint64_t *key) {
+    if (!key || n < 0 || c < 0 || c >= DEC_ROWS) return WMI_E_INVALID_ARG;
+    *key = best_of_key(seed, (uint64_t)n, c);
+    return WMI_OK;
+}
+
+int wmi_get_window_candidate(const wmi_context *ctx, int clip, int i, int32_t *chosen, int32_t *n_candidates) {
+    wmi_context *ec = const_cast<wmi_context *>(ctx);  // (last_error only)
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    if (!chosen || !n_candidates || clip < 0 || clip >= (int)ctx->windows.size() || i < 0 || i >= (int)ctx->windows[clip].size())
+        return set_err(ec, WMI_E_INVALID_ARG, "null chosen / n_candidates, or window %d of clip %d out of range", i, clip);
+    *chosen = -1;
+    *n_candidates = 0;
+    if (clip < (int)ctx->win_cand.size() && i < (int)ctx->win_cand[clip].size()) {
+        *chosen = ctx->win_cand[clip][i].first;
+        *n_candidates = ctx->win_cand[clip][i].second;
+    }
+    return WMI_OK;
+}
+
 int wmi_get_segment_of(const wmi_context *ctx, int clip, int i, int64_t *t0, int64_t *t1, char *text, size_t cap,
                        size_t *len) {
     if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
@@ -4467,6 +4746,7 @@ static int wmi_transcribe_audio_batch_impl(wmi_context *ctx, int n_clips, const 
     if (ctx->beam_size > 1)  // (as wmi_transcribe_batch)
         return set_err(ctx, WMI_E_UNSUPPORTED, "wmi_transcribe_audio_batch decodes greedily only: beam size %d is set "
                        "(wmi_set_beam_size(ctx, 1), or wmi_transcribe_audio per recording)", ctx->beam_size);
+    if (best_of_unsupported(ctx, "wmi_transcribe_audio_batch")) return WMI_E_UNSUPPORTED;
     for (int c = 0; c < n_clips; ++c)
         if (ctx->n_lang == 0 && (ctx->lang_set[c] != 0 || ctx->task != WMI_TASK_TRANSCRIBE))
             return set_err(ctx, WMI_E_INVALID_ARG, "language %d / task %d on an English-only model (clip %d)",
@@ -4869,6 +5149,28 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
         case 29:  // the last ruled beam window's slot histories after every step, int32 [steps][BEAM_MAX][3] = {last, pen, lts1}
             if (!ctx->d_rb_tab || ctx->rb_steps < 1) return WMI_E_INVALID_ARG;
             src = ctx->d_rb_tab; have = (size_t)ctx->rb_steps * BEAM_MAX * 3 * 4; break;
+        case 35: {  // host, int32 [4]: the last best-of window's candidates, steps on one row, steps on N rows, chosen candidate
+            memcpy(out, ctx->bo_count, std::min(sizeof ctx->bo_count, bytes));
+            return WMI_OK;
+        }
+        case 36: {  // host, int32 words: N, M = the longest candidate, len [N], records [N][M][6], plog [N][M] (-1 / 0 behind a candidate's end)
+            const size_t N = ctx->bo_rec.size();
+            size_t M = 0;
+            for (const auto &r : ctx->bo_rec) M = std::max(M, r.size());
+            std::vector<int32_t> v(2 + N + N * M * 6 + N * M, 0);
+            v[0] = (int32_t)N; v[1] = (int32_t)M;
+            static_assert(sizeof(TsRec) == 24, "six words a record");
+            for (size_t c = 0; c < N; ++c) {
+                v[2 + c] = (int32_t)ctx->bo_rec[c].size();
+                int32_t *r = v.data() + 2 + N + c * M * 6;
+                for (size_t k = 0; k < M * 6; ++k) r[k] = -1;
+                memcpy(r, ctx->bo_rec[c].data(), ctx->bo_rec[c].size() * sizeof(TsRec));
+                memcpy(v.data() + 2 + N + N * M * 6 + c * M, ctx->bo_plog[c].data(), ctx->bo_plog[c].size() * 4);
+            }
+            memset(out, 0, bytes);
+            memcpy(out, v.data(), std::min(v.size() * 4, bytes));
+            return WMI_OK;
+        }
         case 11: {  // host: decodes re-run on the kernel chain after a persistent exchange timeout
             const int32_t v = ctx->n_fallbacks;
             memcpy(out, &v, std::min(sizeof v, bytes));
@@ -5025,6 +5327,14 @@ int wmi_decode_timestamps_sampled(wmi_context *ctx, const int32_t *prompt, int n
     });
 }
 
+int wmi_decode_timestamps_best_of(wmi_context *ctx, int best_of, const int32_t *prompt, int n_prompt, int max_tokens,
+                                  float temperature, uint64_t seed, int n, wmi_token_data *out, int32_t *n_out,
+                                  float *plog, float *p_nosp, int32_t *chosen, float *cand_avg, int32_t *cand_len) {
+    return guarded(ctx, [&] {
+        return wmi_decode_timestamps_best_of_impl(ctx, best_of, prompt, n_prompt, max_tokens, temperature, seed, n, out, n_out,
+                                                  plog, p_nosp, chosen, cand_avg, cand_len);
+    });
+}
 int wmi_decode_timestamps_ruled(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens, float temperature,
                                 uint64_t seed, int n, wmi_token_data *out, int32_t *n_out, float *plog, float *p_nosp) {
     return guarded(ctx, [&] {

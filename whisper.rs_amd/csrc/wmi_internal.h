@@ -355,6 +355,13 @@ struct TsRuleArgs {
     int max_initial_ts;      // first timestamp <= beg + this (< 0: no cap)
 };
 hipError_t launch_ts_sample_r(hipStream_t s, const TsRuleArgs &a);
+// ---- best-of-N sampled windows (wmi_bestof.hip; DESIGN.md "Best-of-N sampled
+// attempts"): after the prompt's last step, run on one decoder row, workgroup
+// c of a.B = N draws candidate c's first token from logits row 0 with rows[c]
+// and writes row c of tok_out, done, rec, plog (and hist); workgroup 0 also
+// p_nosp[0].  k_ts_sample_t's first step, or with `ruled` k_ts_sample_r's
+// (m0, hist and max_initial_ts are read only then) ------------------------------
+hipError_t launch_bestof_fan(hipStream_t s, const TsRuleArgs &a, bool ruled);
 // ---- beam search under the decoding rules (wmi_rbeam.hip; DESIGN.md "Decoding
 // rules in the beam window"): k_ts_sample_r's masks per hypothesis row, each
 // row's history following the beam step's parent selection; the ranking, walk

@@ -70,6 +70,7 @@ EXPORTS = (
     "wmi_set_fallback", "wmi_decode_timestamps_sampled", "wmi_get_window_count", "wmi_get_window_info",
     "wmi_set_decode_rules", "wmi_non_speech_tokens", "wmi_decode_timestamps_ruled", "wmi_set_initial_prompt",
     "wmi_set_rules_beam", "wmi_decode_timestamps_ruled_beam",
+    "wmi_set_best_of", "wmi_decode_timestamps_best_of", "wmi_best_of_key", "wmi_get_window_candidate",
     "wmi_is_non_speech_token", "wmi_set_token_timestamps", "wmi_token_times",
     "wmi_set_dtw", "wmi_align_tokens", "wmi_dtw_path", "wmi_dtw_path_host", "wmi_get_segment_dtw_of",
     "wmi_audio_to_mel_batch", "wmi_stage_audio", "wmi_transcribe_audio", "wmi_transcribe_audio_batch", "wmi_get_pcm",
@@ -233,6 +234,12 @@ def lib():
             L.wmi_set_rules_beam.argtypes = [vp, C.c_int]
             L.wmi_decode_timestamps_ruled_beam.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, C.POINTER(i32),
                                                            C.POINTER(C.c_double), C.POINTER(C.c_float)]
+        if hasattr(L, "wmi_set_best_of"):  # (as above: an older build has no best-of windows)
+            L.wmi_set_best_of.argtypes = [vp, C.c_int]
+            L.wmi_decode_timestamps_best_of.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int,
+                                                        vp, C.POINTER(i32), vp, C.POINTER(C.c_float), C.POINTER(i32), vp, vp]
+            L.wmi_best_of_key.argtypes = [C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+            L.wmi_get_window_candidate.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32)]
         if hasattr(L, "wmi_set_token_timestamps"):  # (as above: an older build has no token-level timestamps)
             L.wmi_set_token_timestamps.argtypes = [vp, C.POINTER(TokenTsParams)]
             L.wmi_token_times.argtypes = [vp, vp, sz, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int]
@@ -692,6 +699,67 @@ class WhisperContext:
                                                  C.byref(pn)), self._h)
         return [out[i].as_dict() for i in range(cnt.value)], plog[:cnt.value].copy(), pn.value
 
+    # --- best-of-N sampled attempts --------------------------------------------
+    def set_best_of(self, best_of: int) -> None:
+        """Candidates of every T > 0 attempt of transcribe() under set_fallback
+        (wmi_set_best_of; 1, the default: the single draw)."""
+        _raise(lib().wmi_set_best_of(self._h, int(best_of)), self._h)
+
+    def decode_timestamps_best_of(self, best_of: int, prompt, max_tokens: int, temperature: float, seed: int = 0,
+                                  n: int = 0):
+        """One best-of window of encoded clip 0 (rules are used if enabled):
+        ([WhisperTokenData dict] of the chosen candidate, its plog float32
+        [tokens], p_nosp, chosen, cand_avg float32 [best_of], cand_len int32
+        [best_of])."""
+        prompt = np.ascontiguousarray(prompt, dtype=np.int32)
+        out = (TokenData * max(1, max_tokens))()
+        cnt = C.c_int32()
+        plog = np.zeros(max(1, max_tokens), np.float32)
+        pn = C.c_float()
+        ch = C.c_int32(-1)
+        avg = np.zeros(max(1, best_of), np.float32)
+        ln = np.zeros(max(1, best_of), np.int32)
+        _raise(lib().wmi_decode_timestamps_best_of(self._h, best_of, _ptr(prompt), prompt.size, max_tokens, temperature,
+                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, n, out, C.byref(cnt), _ptr(plog),
+                                                   C.byref(pn), C.byref(ch), _ptr(avg), _ptr(ln)), self._h)
+        return ([out[i].as_dict() for i in range(cnt.value)], plog[:cnt.value].copy(), pn.value, ch.value,
+                avg[:best_of].copy(), ln[:best_of].copy())
+
+    def best_of_counters(self):
+        """The last best-of window: (candidates, decoder steps on one row,
+        decoder steps on N rows, chosen candidate) (debug read 35)."""
+        return tuple(int(v) for v in np.frombuffer(self.debug_read(35, 16), np.int32))
+
+    def best_of_candidates(self):
+        """Every candidate of the last best-of window: a list of ([record
+        dict {id, tid, p, pt, ptsum}], plog float32 [records]) (debug read 36)."""
+        head = np.frombuffer(self.debug_read(36, 8), np.int32)
+        N, M = int(head[0]), int(head[1])
+        w = np.frombuffer(self.debug_read(36, 4 * (2 + N + 7 * N * M)), np.int32)
+        lens = w[2:2 + N]
+        rec = w[2 + N:2 + N + 6 * N * M].reshape(N, M, 6)
+        pl = w[2 + N + 6 * N * M:].view(np.float32).reshape(N, M)
+        out = []
+        for c in range(N):
+            r = rec[c, :lens[c]]
+            f = r[:, 2:5].copy().view(np.float32)
+            out.append(([{"id": int(r[i, 0]), "tid": int(r[i, 1]), "p": float(f[i, 0]), "pt": float(f[i, 1]),
+                          "ptsum": float(f[i, 2])} for i in range(lens[c])], pl[c, :lens[c]].copy()))
+        return out
+
+    def window_candidates(self, clip: int = 0):
+        """Per window of windows_of(clip): (chosen candidate, candidates) of
+        the attempt that became its result; (-1, 0) where that was no best-of
+        attempt (wmi_get_window_candidate)."""
+        n = C.c_int32()
+        _raise(lib().wmi_get_window_count(self._h, clip, C.byref(n)), self._h)
+        out = []
+        for i in range(n.value):
+            ch, nc = C.c_int32(), C.c_int32()
+            _raise(lib().wmi_get_window_candidate(self._h, clip, i, C.byref(ch), C.byref(nc)), self._h)
+            out.append((ch.value, nc.value))
+        return out
+
     def set_rules_beam(self, on: bool = True) -> None:
         """With rules and a beam size above 1, transcribe() windows and
         decode_timestamps_beam() take the ruled beam window
@@ -1121,3 +1189,12 @@ def dtw_path_host(cost):
     if rc:
         _raise(rc, None)
     return out[:rows]
+
+
+def best_of_key(seed: int, n: int, c: int) -> int:
+    """Candidate c's stream key of attempt ordinal n of `seed` (wmi_best_of_key; host only)."""
+    k = C.c_uint64()
+    rc = lib().wmi_best_of_key(int(seed) & 0xFFFFFFFFFFFFFFFF, int(n), int(c), C.byref(k))
+    if rc:
+        _raise(rc, None)
+    return k.value
