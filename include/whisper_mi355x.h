@@ -435,6 +435,39 @@ int wmi_best_of_key(uint64_t seed, int n, int c, uint64_t *key);
  * from a best-of attempt. */
 int wmi_get_window_candidate(const wmi_context *ctx, int clip, int i, int32_t *chosen, int32_t *n_candidates);
 
+/* Prompt prefill.  A window's prompt is known before the window starts, so its
+ * first len - 1 tokens need no decoder steps: they go through every decoder
+ * layer in one pass of MFMA GEMMs and two attention kernels (wmi_prefill.hip),
+ * which writes the self-attention cache rows the steps would have written.
+ * The run then starts at the prompt's last token, an ordinary decoder step, so
+ * every sampler, rule, fallback and record behind it is what it was.
+ * wmi_set_prefill: min_prompt 0 (the default) is off, and every call launches
+ * what it launched before this interface.  N >= 2: a timestamp run
+ * (wmi_decode_timestamps and its _sampled, _ruled, _batch, _rows and _best_of
+ * forms, the windows of wmi_transcribe / wmi_transcribe_audio and the rounds
+ * of wmi_transcribe_batch, ragged and chunked ones included) prefills when its
+ * longest prompt has at least N tokens and at most 257 (a pass holds 256
+ * positions); otherwise it feeds stepwise.  1 or a negative value is
+ * WMI_E_INVALID_ARG.  Holds until changed; a call also zeroes the counts of
+ * debug read 37.  Beam windows, the aligned pass of wmi_set_dtw,
+ * wmi_decode_greedy and wmi_run_staged always feed stepwise.  The pass runs
+ * on the f16 decoder matrices: an f32 file (ftype 0) is WMI_E_UNSUPPORTED
+ * here; a q5_1 file keeps dequantised f16 copies of every decoder matrix on
+ * the device (the values its block GEMVs compute), and the pass reads those.
+ * The pass does not reproduce the step decoder's bits (MFMA sums, a blocked
+ * cross-attention softmax), which is why it is opt-in; it stays inside the
+ * logit bar of the parity tests.  Recommended min_prompt: 16 (Whisper-base
+ * shapes on one MI355X: the pass costs about 0.6 ms whatever the length, so a
+ * 4-token prompt is 0.95 x, 16 tokens 1.19 x, 228 tokens 5.3 x the stepwise
+ * feed; scripts/prefill_bench.py).
+ * wmi_prefill_logits: wmi_decode_logits' contract, teacher-forced
+ * logits[n_tokens][n_vocab] from position 0 of encoded clip `clip`, all
+ * positions in one pass with the final LayerNorm and the vocabulary product
+ * as a GEMM; whatever wmi_set_prefill says.  n_tokens above 256 or an f32
+ * file: WMI_E_UNSUPPORTED. */
+int wmi_set_prefill(wmi_context *ctx, int min_prompt);
+int wmi_prefill_logits(wmi_context *ctx, int clip, const int32_t *tokens, int n_tokens, float *logits);
+
 /* OpenAI's decoding rules (SuppressTokens and ApplyTimestampRules restated)
  * for every window of wmi_transcribe / wmi_transcribe_batch and for
  * wmi_decode_timestamps_ruled, in the place of the whisper.cpp-1.0.3 rule.
@@ -936,7 +969,11 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * before one).  36 = every candidate of that window (int32 words, host): N,
  * M = the longest candidate's records, len [N], the records [N][M] of six
  * words {id, tid, p, pt, ptsum (f32 bits), 0} (-1 behind a candidate's end),
- * and plog [N][M] (f32 bits, 0 behind the end). */
+ * and plog [N][M] (f32 bits, 0 behind the end).  37 = the prompt prefill
+ * (int64 [4], host): the passes since wmi_set_prefill, the rows and the
+ * tokens of the last pass, and the decoder steps saved since wmi_set_prefill.
+ * 13 holds no logits for prefilled positions (slabs 0 .. Pmax - 2 of such a
+ * run keep what an earlier run left there). */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

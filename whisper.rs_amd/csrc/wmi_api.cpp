@@ -150,6 +150,18 @@ struct wmi_context {
     std::vector<std::vector<float>> bo_plog;  // ... and log-probabilities (debug read 36)
     // per window of `windows`: {chosen candidate (-1: not a best-of attempt), candidates} (wmi_get_window_candidate)
     std::vector<std::vector<std::pair<int32_t, int32_t>>> win_cand;
+    // prompt prefill (wmi_set_prefill, wmi_prefill_logits; wmi_prefill.hip).  The scratch comes with the first pass,
+    // one allocation for pf_cap packed rows: the f32 residual stream [cap][n], the QKV product [cap][3 n] f32, then
+    // f16 LN output, q and attention output [cap][n] each, the MLP's hidden rows [cap][4 n] and the rows' cache rows
+    // (int32 [cap])
+    int prefill_min = 0;        // 0: off; N >= 2: timestamp runs whose longest prompt has at least N tokens prefill
+    int64_t pf_count[4] = {0, 0, 0, 0};  // passes, rows / tokens of the last pass, decoder steps saved (debug read 37)
+    float *pf_x = nullptr, *pf_qkv32 = nullptr;
+    uint16_t *pf_ln16 = nullptr, *pf_q16 = nullptr, *pf_att16 = nullptr, *pf_hid16 = nullptr;
+    int32_t *pf_rowmap = nullptr;
+    int pf_cap = 0;
+    float *pf_logits = nullptr; // wmi_prefill_logits: [pf_logits_cap][n_vocab]
+    int pf_logits_cap = 0;
     // batched transcription: source recording [8], then mel offset [8] of each encoder slot, then (chunked calls) its end [8]
     int32_t *d_win = nullptr;
     int32_t win_host[3 * DEC_ROWS] = {};  // host copy of the last d_win upload (debug read 22: its first two columns)
@@ -2203,6 +2215,140 @@ int ensure_ts_buffers(wmi_context *ctx) {
     return WMI_OK;
 }
 
+// ---- prompt prefill (wmi_set_prefill, wmi_prefill_logits; wmi_prefill.hip; DESIGN.md "Prompt prefill") ----
+int ensure_pf_buffers(wmi_context *ctx, int M, bool logits) {
+    const size_t n = (size_t)ctx->hp.n_text_state;
+    if (M > ctx->pf_cap) {
+        if (ctx->pf_x) HIPCHK(ctx, hipFree(ctx->pf_x));
+        ctx->pf_x = nullptr;
+        ctx->pf_cap = 0;
+        const size_t cap = (size_t)up(M, 64);
+        void *p = nullptr;
+        HIPCHK(ctx, hipMalloc(&p, cap * (n * 4 + 3 * n * 4 + 3 * n * 2 + 4 * n * 2 + 4)));
+        ctx->pf_x = (float *)p;
+        ctx->pf_qkv32 = ctx->pf_x + cap * n;
+        ctx->pf_ln16 = (uint16_t *)(ctx->pf_qkv32 + cap * 3 * n);
+        ctx->pf_q16 = ctx->pf_ln16 + cap * n;
+        ctx->pf_att16 = ctx->pf_q16 + cap * n;
+        ctx->pf_hid16 = ctx->pf_att16 + cap * n;
+        ctx->pf_rowmap = (int32_t *)(ctx->pf_hid16 + cap * 4 * n);
+        ctx->pf_cap = (int)cap;
+    }
+    if (logits && M > ctx->pf_logits_cap) {
+        if (ctx->pf_logits) HIPCHK(ctx, hipFree(ctx->pf_logits));
+        ctx->pf_logits = nullptr;
+        ctx->pf_logits_cap = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->pf_logits, (size_t)M * ctx->hp.n_vocab * 4));
+        ctx->pf_logits_cap = M;
+    }
+    return WMI_OK;
+}
+
+// a timestamp run of np feed steps takes the prefill
+bool prefill_on(const wmi_context *ctx, int np) {
+    return ctx->prefill_min >= 2 && np >= ctx->prefill_min && np - 1 <= PF_MAX_KEYS;
+}
+
+// One pass: the recordings' tokens (dfeed, recording r's at r * feed_stride + lo ..) through the decoder layers,
+// K and V of every position into the self-attention cache where a step would have stored them.  Without `logits`
+// the pass ends behind the last layer's QKV product (nothing later is read by a step); with it the final LayerNorm
+// and the vocabulary product follow, into pf_logits [M][n_vocab].
+int prefill_pass(wmi_context *ctx, PfRecs recs, int feed_stride, bool logits) {
+    const wmi_hparams &hp = ctx->hp;
+    const int n = hp.n_text_state, H = hp.n_text_head, T = ctx->enc_T, Bt = ctx->enc_clips, tctx = hp.n_text_ctx;
+    int M = 0;
+    recs.max_len = 0;
+    for (int r = 0; r < recs.n; ++r) {
+        recs.r[r].row0 = M;
+        M += recs.r[r].len;
+        recs.max_len = std::max(recs.max_len, recs.r[r].len);
+    }
+    if (M < 1) return WMI_OK;
+    int rc = ensure_pf_buffers(ctx, M, logits);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const float qs = powf((float)n / (float)H, -0.25f);
+    HIPCHK(ctx, launch_pf_embed(s, recs, ctx->te, ctx->d_pe, ctx->dfeed, feed_stride, n, hp.n_vocab, tctx, ctx->pf_x,
+                                ctx->pf_rowmap));
+    auto gemm = [&](const uint16_t *A, int K, const uint16_t *W, const float *bias, int N) {
+        GemmArgs g{};
+        g.tune = &ctx->tune;
+        g.A = A; g.lda = K; g.B = W; g.bias = bias; g.M = M; g.N = N; g.K = K;
+        return g;
+    };
+    PfAttnArgs at{};
+    at.recs = recs; at.q = ctx->pf_q16; at.out = ctx->pf_att16; at.n = n; at.H = H; at.tctx = tctx; at.T = T;
+    for (int l = 0; l < ctx->dec_layers; ++l) {
+        const DecLayerDev &d = ctx->dec[l];
+        HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, d.ln1_w, d.ln1_b, ctx->pf_ln16, nullptr));
+        GemmArgs g = gemm(ctx->pf_ln16, n, d.wqkv, nullptr, 3 * n);
+        g.out32 = ctx->pf_qkv32; g.ldo = 3 * n;
+        HIPCHK(ctx, launch_gemm(s, EPI_F32, g));
+        PfQkvArgs qa{};
+        qa.acc = ctx->pf_qkv32; qa.bias = d.bqkv; qa.rowmap = ctx->pf_rowmap; qa.q = ctx->pf_q16;
+        qa.k = ctx->kcache + (size_t)l * DEC_ROWS * tctx * n;
+        qa.v = ctx->vcache + (size_t)l * DEC_ROWS * tctx * n;
+        qa.M = M; qa.N = 3 * n; qa.n = n; qa.qscale = qs;
+        HIPCHK(ctx, launch_pf_qkv_store(s, qa));
+        if (!logits && l == ctx->dec_layers - 1) break;
+        at.K = qa.k; at.V = qa.v;
+        HIPCHK(ctx, launch_pf_self_attn(s, at));
+        g = gemm(ctx->pf_att16, n, d.wo, d.bo, n);
+        g.out32 = ctx->pf_x; g.ldo = n;
+        HIPCHK(ctx, launch_gemm(s, EPI_RESID, g));
+        HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, d.lnc_w, d.lnc_b, ctx->pf_ln16, nullptr));
+        g = gemm(ctx->pf_ln16, n, d.wcq, nullptr, n);
+        g.out32 = ctx->pf_qkv32; g.ldo = n;
+        HIPCHK(ctx, launch_gemm(s, EPI_F32, g));
+        qa.bias = d.bcq; qa.N = n;  // (the q part alone)
+        HIPCHK(ctx, launch_pf_qkv_store(s, qa));
+        at.K = ctx->ck + (size_t)l * Bt * T * n; at.V = ctx->cv + (size_t)l * Bt * T * n;
+        HIPCHK(ctx, launch_pf_cross_attn(s, at));
+        g = gemm(ctx->pf_att16, n, d.wco, d.bco, n);
+        g.out32 = ctx->pf_x; g.ldo = n;
+        HIPCHK(ctx, launch_gemm(s, EPI_RESID, g));
+        HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, d.ln2_w, d.ln2_b, ctx->pf_ln16, nullptr));
+        g = gemm(ctx->pf_ln16, n, d.w0, d.b0, 4 * n);
+        g.out16 = ctx->pf_hid16; g.ldo = 4 * n; g.gelu_tab = ctx->gelu_tab; g.gelu_min = gelu_min_of(ctx);
+        HIPCHK(ctx, launch_gemm(s, EPI_GELU16, g));
+        g = gemm(ctx->pf_hid16, 4 * n, d.w1, d.b1, n);
+        g.out32 = ctx->pf_x; g.ldo = n;
+        HIPCHK(ctx, launch_gemm(s, EPI_RESID, g));
+    }
+    if (logits) {
+        HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, ctx->dln_w, ctx->dln_b, ctx->pf_ln16, nullptr));
+        GemmArgs g = gemm(ctx->pf_ln16, n, ctx->te, nullptr, hp.n_vocab);
+        g.out32 = ctx->pf_logits; g.ldo = hp.n_vocab;
+        HIPCHK(ctx, launch_gemm(s, EPI_F32, g));
+    }
+    return WMI_OK;
+}
+
+// The prefill of a timestamp run behind its reset: rows b < B (cache row b, encoder slot clip0 + b, its
+// prompt from step lo[b] on) take steps 0 .. np - 2 in one pass, and the step state is what np - 1 steps leave
+int prefill_rows(wmi_context *ctx, int clip0, int B, const int32_t *lo, int np) {
+    PfRecs recs{};
+    recs.n = B;
+    int64_t tokens = 0;
+    for (int b = 0; b < B; ++b) {
+        recs.r[b].slot = b;
+        recs.r[b].clip = clip0 + b;
+        recs.r[b].lo = lo[b];
+        recs.r[b].len = np - 1 - lo[b];
+        tokens += recs.r[b].len;
+    }
+    int rc = prefill_pass(ctx, recs, np, false);
+    if (rc) return rc;
+    const int n_sync = ctx->use_coop ? (int)(ctx->sync_bytes / sizeof(XSync)) : 0;
+    HIPCHK(ctx, launch_pf_start(ctx->stream, ctx->dstate, np - 1, ctx->dsync, n_sync,
+                                (uint32_t)(np - 1) * (uint32_t)((ctx->enc_T + 127) / 128)));
+    ++ctx->pf_count[0];
+    ctx->pf_count[1] = B;
+    ctx->pf_count[2] = tokens;
+    ctx->pf_count[3] += np - 1;
+    return WMI_OK;
+}
+
 // Rows [b0, b0 + B) of the encoded batch, row b after the np tokens feed[b * np ..).
 // With `lens` the rows' prompts differ in length: feed holds them one behind
 // the other, row b's lens[b] tokens, and np is ignored.  The run then takes
@@ -2272,6 +2418,11 @@ int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &fee
         for (int b = 0; b < B; ++b) { srows[b].T = samp->T[b]; srows[b].key = samp->key[b]; }
     }
     const int total = np + max_tokens - 1;
+    // with the prefill the prompt's steps 0 .. np - 2 are one pass behind the reset and the run starts at the
+    // prompt's last token (a re-run on the kernel chain prefills again: the counts of debug read 37 start over)
+    const bool pf = prefill_on(ctx, np);
+    const int start = pf ? np - 1 : 0;
+    const int64_t pf_passes = ctx->pf_count[0], pf_saved = ctx->pf_count[3];
     int have = 0;
     do {
         const RunGrid gr = run_grid(ctx, run);
@@ -2279,13 +2430,19 @@ int run_ts_rows(wmi_context *ctx, int b0, int B, const std::vector<int32_t> &fee
         if (rc) return rc;
         if (samp) HIPCHK(ctx, hipMemcpyAsync(ctx->d_samp_rows, srows, sizeof srows, hipMemcpyHostToDevice, ctx->stream));
         if (ragged) HIPCHK(ctx, hipMemcpyAsync(ctx->d_lo, ctx->ts_lo + 2, sizeof lo, hipMemcpyHostToDevice, ctx->stream));
+        if (pf) {
+            ctx->pf_count[0] = pf_passes;
+            ctx->pf_count[3] = pf_saved;
+            rc = prefill_rows(ctx, b0, B, lo, np);
+            if (rc) return rc;
+        }
         have = 0;
-        for (int done = 0; done < total;) {
+        for (int done = start; done < total;) {
             const int chunk = std::min(16, total - done);
             rc = advance_run(ctx, run, gr, done, chunk);
             if (rc) return rc;
             done += chunk;
-            ctx->last_run_steps = done;
+            ctx->last_run_steps = done - start;
             have = done - np + 1;  // records written so far (per row that has not met EOT)
             if (have <= 0 || done >= total) continue;
             int32_t dn[DEC_ROWS];
@@ -2395,6 +2552,9 @@ int run_best_of(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, 
     cand_run.cands = 1;
     const int total2 = max_tokens - 1;  // steps on N rows at most
     int steps2 = 0;
+    const bool pf = prefill_on(ctx, np);
+    const int64_t pf_passes = ctx->pf_count[0], pf_saved = ctx->pf_count[3];
+    const int steps1 = pf ? 1 : np;     // steps on one row
     do {
         const RunGrid g1 = run_grid(ctx, feed_run), g2 = run_grid(ctx, cand_run);
         rc = reset_run(ctx, true, g1.G, 0, false, prompt.data(), np, true, ruled);
@@ -2404,7 +2564,13 @@ int run_best_of(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, 
         // phase 1: no sampler behind a step that feeds the prompt, the fan-out sampler behind the last
         DecRun r1 = feed_run;
         r1.fan = -1;
-        if (np > 1) {
+        if (pf) {  // (the prompt's steps 0 .. np - 2 as one prefill pass into cache row 0)
+            const int32_t lo0[DEC_ROWS] = {};
+            ctx->pf_count[0] = pf_passes;
+            ctx->pf_count[3] = pf_saved;
+            rc = prefill_rows(ctx, clip, 1, lo0, np);
+            if (rc) return rc;
+        } else if (np > 1) {
             rc = advance_run(ctx, r1, g1, 0, np - 1);
             if (rc) return rc;
         }
@@ -2458,8 +2624,8 @@ int run_best_of(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, 
             if (r[i].id == ctx->sp.eot) { r.resize(i + 1); break; }
         (*plog)[c].resize(r.size());
     }
-    ctx->last_run_steps = np + steps2;
-    ctx->bo_count[0] = N; ctx->bo_count[1] = np; ctx->bo_count[2] = steps2; ctx->bo_count[3] = -1;
+    ctx->last_run_steps = steps1 + steps2;
+    ctx->bo_count[0] = N; ctx->bo_count[1] = steps1; ctx->bo_count[2] = steps2; ctx->bo_count[3] = -1;
     ctx->bo_rec = *recs;
     ctx->bo_plog = *plog;
     return WMI_OK;
@@ -3745,6 +3911,8 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->d_plan) (void)hipFree(ctx->d_plan);
     for (hipEvent_t e : ctx->ck_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->d_samp_rows) (void)hipFree(ctx->d_samp_rows);
+    if (ctx->pf_x) (void)hipFree(ctx->pf_x);
+    if (ctx->pf_logits) (void)hipFree(ctx->pf_logits);
     if (ctx->d_rule_m0) (void)hipFree(ctx->d_rule_m0);
     if (ctx->d_rb_hist) (void)hipFree(ctx->d_rb_hist);
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
@@ -4492,6 +4660,17 @@ int wmi_set_best_of(wmi_context *ctx, int best_of) {
     return WMI_OK;
 }
 
+int wmi_set_prefill(wmi_context *ctx, int min_prompt) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    if (min_prompt == 1 || min_prompt < 0)
+        return set_err(ctx, WMI_E_INVALID_ARG, "min_prompt %d: 0 (off) or at least 2", min_prompt);
+    if (min_prompt && ctx->wf32)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "the prompt prefill runs the f16 MFMA GEMMs: this model's decoder matrices are f32");
+    ctx->prefill_min = min_prompt;
+    ctx->pf_count[0] = ctx->pf_count[1] = ctx->pf_count[2] = ctx->pf_count[3] = 0;
+    return WMI_OK;
+}
+
 int wmi_best_of_key(uint64_t seed, int n, int c, uint64_t *key) {
     if (!key || n < 0 || c < 0 || c >= DEC_ROWS) return WMI_E_INVALID_ARG;
     *key = best_of_key(seed, (uint64_t)n, c);
@@ -4655,6 +4834,32 @@ static int wmi_decode_logits_impl(wmi_context *ctx, int clip, const int32_t *tok
         rc = finish_run(ctx);
     } while (rc == RERUN_ON_CHAIN);
     return rc;
+}
+
+static int wmi_prefill_logits_impl(wmi_context *ctx, int clip, const int32_t *tokens, int n_tokens, float *logits) {
+    if (!valid(ctx) || !tokens || !logits || n_tokens < 1) return WMI_E_INVALID_ARG;
+    if (ctx->wf32)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "the prompt prefill runs the f16 MFMA GEMMs: this model's decoder matrices are f32");
+    if (ctx->enc_T <= 0) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
+    if (clip < 0 || clip >= ctx->enc_clips) return set_err(ctx, WMI_E_INVALID_ARG, "clip %d", clip);
+    if (n_tokens > ctx->hp.n_text_ctx) return set_err(ctx, WMI_E_INVALID_ARG, "too many tokens");
+    if (n_tokens > PF_MAX_KEYS)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "a prefill pass holds at most %d positions (%d)", PF_MAX_KEYS, n_tokens);
+    for (int i = 0; i < n_tokens; ++i)
+        if (tokens[i] < 0 || tokens[i] >= ctx->hp.n_vocab) return set_err(ctx, WMI_E_INVALID_ARG, "token id %d", tokens[i]);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_decode_buffers(ctx, n_tokens, 1);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->dfeed, tokens, (size_t)n_tokens * 4, hipMemcpyHostToDevice, ctx->stream));
+    PfRecs recs{};
+    recs.n = 1;
+    recs.r[0].clip = clip;
+    recs.r[0].len = n_tokens;
+    rc = prefill_pass(ctx, recs, n_tokens, true);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(logits, ctx->pf_logits, (size_t)n_tokens * ctx->hp.n_vocab * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return WMI_OK;
 }
 
 static int wmi_decode_beam_impl(wmi_context *ctx, int beam_size, int max_tokens, int suppress_eot, int32_t *tokens,
@@ -5171,6 +5376,11 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
             memcpy(out, v.data(), std::min(v.size() * 4, bytes));
             return WMI_OK;
         }
+        case 37: {  // host, int64 [4]: prefill passes since wmi_set_prefill, rows and tokens of the last pass, decoder steps saved
+            const int64_t v[4] = {ctx->pf_count[0], ctx->pf_count[1], ctx->pf_count[2], ctx->pf_count[3]};
+            memcpy(out, v, std::min(sizeof v, bytes));
+            return WMI_OK;
+        }
         case 11: {  // host: decodes re-run on the kernel chain after a persistent exchange timeout
             const int32_t v = ctx->n_fallbacks;
             memcpy(out, &v, std::min(sizeof v, bytes));
@@ -5395,6 +5605,10 @@ int wmi_decode_greedy(wmi_context *ctx, int max_tokens, int suppress_eot, int32_
 
 int wmi_decode_logits(wmi_context *ctx, int clip, const int32_t *tokens, int n_tokens, float *logits) {
     return guarded(ctx, [&] { return wmi_decode_logits_impl(ctx, clip, tokens, n_tokens, logits); });
+}
+
+int wmi_prefill_logits(wmi_context *ctx, int clip, const int32_t *tokens, int n_tokens, float *logits) {
+    return guarded(ctx, [&] { return wmi_prefill_logits_impl(ctx, clip, tokens, n_tokens, logits); });
 }
 
 int wmi_decode_beam(wmi_context *ctx, int beam_size, int max_tokens, int suppress_eot, int32_t *tokens,

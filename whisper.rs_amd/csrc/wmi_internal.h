@@ -522,6 +522,44 @@ struct DecEmbedArgs {
 };
 hipError_t launch_dec_embed(hipStream_t s, const DecEmbedArgs &a);
 
+// ---- prompt prefill (wmi_prefill.hip; DESIGN.md "Prompt prefill"): the prompts of a round's rows through the
+// decoder layers as one packed [M][n] activation matrix.  Recording r owns packed rows [row0, row0 + len): its
+// tokens feed[r * feed_stride + lo + i], i < len, at step positions lo + i of cache row `slot`, position
+// embedding pe[i], cross K / V of encoder slot `clip`
+constexpr int PF_MAX_KEYS = 256;  // keys k_pf_self_attn holds in LDS and registers: a longer prompt feeds stepwise
+struct PfRec { int32_t slot, clip, lo, len, row0, pad[3]; };
+struct PfRecs { PfRec r[DEC_ROWS]; int32_t n, max_len; };
+// x[row0 + i] = te[tok] + pe[i] (f32 residual stream) and rowmap[row0 + i] = slot * tctx + lo + i
+hipError_t launch_pf_embed(hipStream_t s, const PfRecs &recs, const uint16_t *te, const float *pe, const int32_t *feed,
+                           int feed_stride, int n, int V, int tctx, float *x, int32_t *rowmap);
+// The QKV product's f32 result (launch_gemm EPI_F32, no bias) into the form the step kernels store (DEC_QKV):
+// q[m][c] = f16((acc + bias) * qscale); K and V of packed row m go to cache row rowmap[m]: k[rowmap[m]][c] =
+// f16(acc * qscale), v[rowmap[m]][c] = f16(bias + acc).  N = 3 n (bias [q; 0; v]), or N = n: the q part alone
+// (the cross-attention query projection)
+struct PfQkvArgs {
+    const float *acc;        // [M][N]
+    const float *bias;       // [N]
+    const int32_t *rowmap;   // [M]
+    uint16_t *q, *k, *v;     // q [M][n]; k, v: a layer's cache [DEC_ROWS * tctx][n]
+    int M, N, n;
+    float qscale;
+};
+hipError_t launch_pf_qkv_store(hipStream_t s, const PfQkvArgs &a);
+struct PfAttnArgs {
+    PfRecs recs;
+    const uint16_t *q;       // [M][n] f16, scaled (k_pf_qkv_store)
+    const uint16_t *K, *V;   // self: a layer's cache [DEC_ROWS][tctx][n]; cross: a layer's [Bt][T][n]
+    uint16_t *out;           // [M][n] f16: the input of the output projection
+    int n, H, tctx, T;
+};
+// causal self-attention of every recording over its own packed rows (len <= PF_MAX_KEYS)
+hipError_t launch_pf_self_attn(hipStream_t s, const PfAttnArgs &a);
+// every packed row against the T encoder keys of its recording's clip
+hipError_t launch_pf_cross_attn(hipStream_t s, const PfAttnArgs &a);
+// the state a run starts from behind a prefill of np - 1 steps: st->pos = pos, and the cooperative chain
+// cross-attention's arrival counters where pos steps leave them (cnt = pos * chunks; sync null: none)
+hipError_t launch_pf_start(hipStream_t s, DecState *st, int pos, XSync *sync, int n_sync, uint32_t cnt);
+
 // ---- persistent decoder: one launch runs n_steps greedy decoder steps -------
 // (wmi_persist.hip).  Every decoder step is a fixed sequence of phases; the
 // workgroups of the launch (all co-resident, one per CU) hand each phase's

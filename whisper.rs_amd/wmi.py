@@ -71,6 +71,7 @@ EXPORTS = (
     "wmi_set_decode_rules", "wmi_non_speech_tokens", "wmi_decode_timestamps_ruled", "wmi_set_initial_prompt",
     "wmi_set_rules_beam", "wmi_decode_timestamps_ruled_beam",
     "wmi_set_best_of", "wmi_decode_timestamps_best_of", "wmi_best_of_key", "wmi_get_window_candidate",
+    "wmi_set_prefill", "wmi_prefill_logits",
     "wmi_is_non_speech_token", "wmi_set_token_timestamps", "wmi_token_times",
     "wmi_set_dtw", "wmi_align_tokens", "wmi_dtw_path", "wmi_dtw_path_host", "wmi_get_segment_dtw_of",
     "wmi_audio_to_mel_batch", "wmi_stage_audio", "wmi_transcribe_audio", "wmi_transcribe_audio_batch", "wmi_get_pcm",
@@ -240,6 +241,9 @@ def lib():
                                                         vp, C.POINTER(i32), vp, C.POINTER(C.c_float), C.POINTER(i32), vp, vp]
             L.wmi_best_of_key.argtypes = [C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
             L.wmi_get_window_candidate.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i32), C.POINTER(i32)]
+        if hasattr(L, "wmi_set_prefill"):  # (as above: an older build has no prompt prefill)
+            L.wmi_set_prefill.argtypes = [vp, C.c_int]
+            L.wmi_prefill_logits.argtypes = [vp, C.c_int, vp, C.c_int, vp]
         if hasattr(L, "wmi_set_token_timestamps"):  # (as above: an older build has no token-level timestamps)
             L.wmi_set_token_timestamps.argtypes = [vp, C.POINTER(TokenTsParams)]
             L.wmi_token_times.argtypes = [vp, vp, sz, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int]
@@ -1012,6 +1016,22 @@ class WhisperContext:
         out = np.zeros((tokens.size, self.hparams["n_vocab"]), np.float32)
         _raise(lib().wmi_decode_logits(self._h, clip, _ptr(tokens), tokens.size, _ptr(out)), self._h)
         return out
+
+    def set_prefill(self, min_prompt: int) -> None:
+        """Timestamp runs whose longest prompt has at least min_prompt tokens put all but its last token through
+        the decoder in one prefill pass (wmi_set_prefill; 0, the default: every prompt token is a decoder step)."""
+        _raise(lib().wmi_set_prefill(self._h, int(min_prompt)), self._h)
+
+    def prefill_logits(self, tokens, clip: int = 0) -> np.ndarray:
+        """decode_logits' result, every position computed in one prefill pass (wmi_prefill_logits)."""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        out = np.zeros((tokens.size, self.hparams["n_vocab"]), np.float32)
+        _raise(lib().wmi_prefill_logits(self._h, clip, _ptr(tokens), tokens.size, _ptr(out)), self._h)
+        return out
+
+    def prefill_counts(self):
+        """Debug read 37: prefill passes since set_prefill, rows and tokens of the last pass, decoder steps saved."""
+        return [int(v) for v in np.frombuffer(self.debug_read(37, 32), np.int64)]
 
     def full(self, pcm, max_tokens: int = 224) -> np.ndarray:
         """Transcribe: pcm_to_mel -> encode -> greedy decode (token ids)."""
