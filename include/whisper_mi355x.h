@@ -308,7 +308,8 @@ int wmi_get_segment_tokens_of(const wmi_context *ctx, int clip, int i, wmi_token
  * alone, up to the order of the key sums.  A round costs the steps of its
  * longest prompt.  enable 0 (default): every call runs exactly the kernels it
  * ran before.  Neither 0 nor 1: WMI_E_INVALID_ARG.  Holds until changed.  A
- * beam size above 1 in the batch stays WMI_E_UNSUPPORTED. */
+ * beam size above 1 in the batch stays WMI_E_UNSUPPORTED unless
+ * wmi_set_batch_beam (below) is on. */
 int wmi_set_batch_context(wmi_context *ctx, int enable);
 /* wmi_decode_timestamps_batch with a prompt per row: row b (encoded clip b)
  * decodes after prompts[b * prompt_stride .. + n_prompt[b]); out is
@@ -318,6 +319,39 @@ int wmi_set_batch_context(wmi_context *ctx, int enable);
  * max n_prompt + max_tokens > n_text_ctx: WMI_E_INVALID_ARG. */
 int wmi_decode_timestamps_rows(wmi_context *ctx, const int32_t *prompts, const int32_t *n_prompt, int prompt_stride,
                                int max_tokens, wmi_token_data *out, int32_t *n_out);
+
+/* ---- beam search in the batch ------------------------------------------- */
+
+/* One beam window (wmi_decode_timestamps_beam's search, K = beam_size
+ * hypotheses) for every encoded clip, in rounds of up to eight clips, clip b
+ * after prompts[b * prompt_stride .. + n_prompt[b]).  A round decodes on the
+ * wide decoder step: R = clips x K <= 64 rows a step, the recordings side by
+ * side and independent, each from its own prompt's last position (no
+ * right-alignment), one that is done idle while the others go on.  Clip b
+ * yields what wmi_decode_timestamps_beam yields for it alone with the same
+ * prompt and K, up to the order of the floating-point sums.  out is
+ * [n_clips][max_tokens] (the chosen hypothesis' records, its EOT included),
+ * n_out [n_clips], score [n_clips] (its summed log-probability; may be NULL).
+ * Needs no opt-in.  The prompt's positions go through one prefill pass
+ * whatever wmi_set_prefill says: a prompt above 257 tokens, and an f32 file
+ * (the step runs the f16 MFMA GEMMs), are WMI_E_UNSUPPORTED.  The decoding
+ * rules are not applied.  The wide step keeps self-attention caches of its
+ * own, [n_text_layer][clips x K][n_text_ctx][n_text_state] f16 for K and for
+ * V, allocated with the first wide window and grown on demand: 64 rows at
+ * large-v3 take 4.7 GB. */
+int wmi_decode_timestamps_beam_rows(wmi_context *ctx, int beam_size, const int32_t *prompts, int prompt_stride,
+                                    const int32_t *n_prompt, int max_tokens, wmi_token_data *out, int32_t *n_out, double *score);
+/* enable 1: wmi_transcribe_batch / wmi_transcribe_audio_batch with a beam size
+ * above 1 (wmi_set_beam_size) decode every round's windows as beam windows on
+ * the wide step, with and without wmi_set_batch_context.  A round of one
+ * recording takes wmi_transcribe's beam window.  With the opt-in and a beam size above 1
+ * the batch calls are WMI_E_UNSUPPORTED, checked at the call, for an f32 file,
+ * with the decoding rules on, with the fallback on (a round would hold beam
+ * rows and sampled rows at once) and with best_of above 1.  enable 0
+ * (default): a beam size above 1 in the batch is WMI_E_UNSUPPORTED and every
+ * call launches what it launched before.  Neither 0 nor 1:
+ * WMI_E_INVALID_ARG.  Holds until changed. */
+int wmi_set_batch_beam(wmi_context *ctx, int enable);
 
 /* ---- temperature fallback, quality thresholds, no-speech ---------------- */
 
@@ -973,7 +1007,12 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * (int64 [4], host): the passes since wmi_set_prefill, the rows and the
  * tokens of the last pass, and the decoder steps saved since wmi_set_prefill.
  * 13 holds no logits for prefilled positions (slabs 0 .. Pmax - 2 of such a
- * run keep what an earlier run left there). */
+ * run keep what an earlier run left there).  38 = the last wide run (int32
+ * [11], host): its recordings B, hypotheses K, steps, and each recording's
+ * position p_c [8] when it ended.  39 = under WMI_LOGITS_ALL that run's logits,
+ * f32 [B][max_tokens][K][n_vocab]: row k of recording c's step t (zero where
+ * the row was idle).  40 / 41 = its parent slots and slot tokens, int32
+ * [8][n_text_ctx][8] (recording, step, slot). */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

@@ -162,6 +162,20 @@ struct wmi_context {
     int pf_cap = 0;
     float *pf_logits = nullptr; // wmi_prefill_logits: [pf_logits_cap][n_vocab]
     int pf_logits_cap = 0;
+    // beam search in the batch (wmi_set_batch_beam, wmi_decode_timestamps_beam_rows; wmi_wide.hip).  Everything comes
+    // with the first wide window and grows on demand: the wide caches [L][wd_rows][tctx][n] f16 for K and V, one
+    // allocation for the recordings' table (wd_tb) with rowmap [64] behind it, the rows' logits [64][n_vocab], the
+    // cross-attention partials, and under WMI_LOGITS_ALL every row's logits of every step [B][wd_lg_steps][K][V]
+    bool batch_beam = false;
+    uint16_t *wd_k = nullptr, *wd_v = nullptr;
+    int wd_rows = 0;
+    void *wd_tab = nullptr;
+    WdTable wd_tb{};
+    int32_t *wd_rowmap = nullptr;
+    float *wd_logits = nullptr, *wd_part = nullptr, *wd_lgall = nullptr;
+    size_t wd_part_cap = 0, wd_lgall_cap = 0;
+    int wd_lg_steps = 0;
+    int32_t wd_last[3 + DEC_ROWS] = {};  // the last wide run's B, K, steps and p_c[8] (debug read 38)
     // batched transcription: source recording [8], then mel offset [8] of each encoder slot, then (chunked calls) its end [8]
     int32_t *d_win = nullptr;
     int32_t win_host[3 * DEC_ROWS] = {};  // host copy of the last d_win upload (debug read 22: its first two columns)
@@ -2253,7 +2267,9 @@ bool prefill_on(const wmi_context *ctx, int np) {
 // K and V of every position into the self-attention cache where a step would have stored them.  Without `logits`
 // the pass ends behind the last layer's QKV product (nothing later is read by a step); with it the final LayerNorm
 // and the vocabulary product follow, into pf_logits [M][n_vocab].
-int prefill_pass(wmi_context *ctx, PfRecs recs, int feed_stride, bool logits) {
+// kbase / vbase: the cache the pass writes, [L][cache_rows][tctx][n] (null: the context's 8-row caches).
+int prefill_pass(wmi_context *ctx, PfRecs recs, int feed_stride, bool logits, uint16_t *kbase = nullptr,
+                 uint16_t *vbase = nullptr, int cache_rows = DEC_ROWS) {
     const wmi_hparams &hp = ctx->hp;
     const int n = hp.n_text_state, H = hp.n_text_head, T = ctx->enc_T, Bt = ctx->enc_clips, tctx = hp.n_text_ctx;
     int M = 0;
@@ -2286,8 +2302,8 @@ int prefill_pass(wmi_context *ctx, PfRecs recs, int feed_stride, bool logits) {
         HIPCHK(ctx, launch_gemm(s, EPI_F32, g));
         PfQkvArgs qa{};
         qa.acc = ctx->pf_qkv32; qa.bias = d.bqkv; qa.rowmap = ctx->pf_rowmap; qa.q = ctx->pf_q16;
-        qa.k = ctx->kcache + (size_t)l * DEC_ROWS * tctx * n;
-        qa.v = ctx->vcache + (size_t)l * DEC_ROWS * tctx * n;
+        qa.k = (kbase ? kbase : ctx->kcache) + (size_t)l * cache_rows * tctx * n;
+        qa.v = (vbase ? vbase : ctx->vcache) + (size_t)l * cache_rows * tctx * n;
         qa.M = M; qa.N = 3 * n; qa.n = n; qa.qscale = qs;
         HIPCHK(ctx, launch_pf_qkv_store(s, qa));
         if (!logits && l == ctx->dec_layers - 1) break;
@@ -3001,6 +3017,8 @@ std::vector<int32_t> ts_init_prompt(const wmi_context *ctx, int lang) {
 
 int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, int K, int max_tokens,
                        std::vector<TsRec> *out, double *score, float *p_nosp = nullptr, bool ruled = false);
+int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector<std::vector<int32_t>> &prompts, int max_tokens,
+                       std::vector<std::vector<TsRec>> *out, std::vector<double> *scores);
 
 // after attempt 0: probably silence (OpenAI's no_speech_threshold rule)
 bool fb_silence(const wmi_context *ctx, float p_nosp, const FbAttempt &att) {
@@ -3133,7 +3151,23 @@ int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows,
     out->assign((size_t)B, {});
     for (int b = 0; b < B; ++b) (*out)[b].T = fb ? tr.temps[tr.recs[rows[b]].att] : 0.0f;
     if (ctx->beam_size > 1 && (*out)[0].T == 0.0f) {
-        if (B != 1) return set_err(ctx, WMI_E_UNSUPPORTED, "a beam window decodes one recording (%d rows)", B);
+        if (B != 1) {
+            if (!ctx->batch_beam) return set_err(ctx, WMI_E_UNSUPPORTED, "a beam window decodes one recording (%d rows)", B);
+            // (wmi_set_batch_beam: every row's beam window on the wide step; the entry points have refused rules,
+            // the fallback and f32 files)
+            std::vector<std::vector<int32_t>> prompts((size_t)B);
+            size_t at = 0;
+            for (int b = 0; b < B; ++b) {
+                const size_t len = lens ? (size_t)(*lens)[b] : (size_t)np;
+                prompts[b].assign(feed.begin() + at, feed.begin() + at + len);
+                at += len;
+            }
+            std::vector<std::vector<TsRec>> toks;
+            int rc = run_wide_beam_rows(ctx, 0, B, ctx->beam_size, prompts, tr.n_max, &toks, nullptr);
+            if (rc) return rc;
+            for (int b = 0; b < B; ++b) (*out)[b].toks = std::move(toks[b]);
+            return WMI_OK;
+        }
         TrAttempt &a = (*out)[0];
         // (rules on: the caller has checked wmi_set_rules_beam, and the window is the ruled beam window)
         return run_ts_beam_window(ctx, 0, feed, ctx->beam_size, tr.n_max, &a.toks, fb ? &a.logprob_sum : nullptr,
@@ -3748,6 +3782,286 @@ int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &p
     return WMI_OK;
 }
 
+// ---- beam search in the batch (wmi_wide.hip; DESIGN.md "Beam search in the batch") ----
+// what the wide step asks of the model (checked at the call)
+int wide_unsupported(wmi_context *ctx) {
+    if (ctx->wf32)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "the wide decoder step runs the f16 MFMA GEMMs: this model's decoder matrices are f32");
+    if (ctx->hp.n_text_ctx > 512 || ctx->hp.n_text_state != ctx->hp.n_text_head * 64)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "the wide decoder step needs n_text_ctx <= 512 (%d) and 64-wide heads",
+                       ctx->hp.n_text_ctx);
+    return WMI_OK;
+}
+
+// the wide caches for R rows, the table, the logits, the partials of `chunks` key chunks and (WMI_LOGITS_ALL) the
+// capture of lg_steps steps of B x K rows; whatever moves drops the captured graphs
+int ensure_wide_buffers(wmi_context *ctx, int R, int B, int K, int chunks, int lg_steps) {
+    const wmi_hparams &hp = ctx->hp;
+    const size_t n = hp.n_text_state, tctx = hp.n_text_ctx, L = hp.n_text_layer, V = hp.n_vocab;
+    if (R > ctx->wd_rows) {
+        for (uint16_t **p : {&ctx->wd_k, &ctx->wd_v}) {
+            if (*p) HIPCHK(ctx, hipFree(*p));
+            *p = nullptr;
+        }
+        ctx->wd_rows = 0;
+        const size_t nb = L * (size_t)R * tctx * n * 2;
+        HIPCHK(ctx, hipMalloc(&ctx->wd_k, nb));
+        HIPCHK(ctx, hipMalloc(&ctx->wd_v, nb));
+        ctx->wd_rows = R;
+        ctx->clear_graphs();
+    }
+    if (!ctx->wd_tab) {
+        size_t off = 0;
+        auto take = [&](size_t nb) { const size_t o = off; off += (size_t)up((int64_t)nb, 16); return o; };
+        const size_t o_recs = take(DEC_ROWS * sizeof(WdRec)), o_bs = take(DEC_ROWS * sizeof(BeamState));
+        const size_t o_src = take((size_t)DEC_ROWS * BEAM_MAX * tctx * 4);
+        const size_t o_par = take((size_t)DEC_ROWS * tctx * BEAM_MAX * 4), o_tok = take((size_t)DEC_ROWS * tctx * BEAM_MAX * 4);
+        const size_t o_rec = take((size_t)DEC_ROWS * (tctx + 1) * BEAM_MAX * sizeof(TsRec));
+        const size_t o_parts = take((size_t)DEC_ROWS * BEAM_MAX * BEAM_NS * sizeof(TsBeamPart));
+        const size_t o_map = take(WD_ROWS * 4);
+        HIPCHK(ctx, hipMalloc(&ctx->wd_tab, off));
+        HIPCHK(ctx, hipMemset(ctx->wd_tab, 0, off));
+        char *p = (char *)ctx->wd_tab;
+        ctx->wd_tb.recs = (WdRec *)(p + o_recs); ctx->wd_tb.bs = (BeamState *)(p + o_bs);
+        ctx->wd_tb.kv_src = (int32_t *)(p + o_src);
+        ctx->wd_tb.hist_parent = (int32_t *)(p + o_par); ctx->wd_tb.hist_tok = (int32_t *)(p + o_tok);
+        ctx->wd_tb.hist_rec = (TsRec *)(p + o_rec); ctx->wd_tb.tparts = (TsBeamPart *)(p + o_parts);
+        ctx->wd_rowmap = (int32_t *)(p + o_map);
+    }
+    if (!ctx->wd_logits) HIPCHK(ctx, hipMalloc(&ctx->wd_logits, (size_t)WD_ROWS * V * 4));
+    const size_t part = (size_t)DEC_ROWS * hp.n_text_head * chunks * 16 * WD_PART;
+    if (part > ctx->wd_part_cap) {
+        if (ctx->wd_part) HIPCHK(ctx, hipFree(ctx->wd_part));
+        ctx->wd_part = nullptr;
+        ctx->wd_part_cap = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->wd_part, part * 4));
+        ctx->wd_part_cap = part;
+        ctx->clear_graphs();
+    }
+    if (ctx->d_lgall) {
+        const size_t need = (size_t)B * lg_steps * K * V;
+        if (need > ctx->wd_lgall_cap) {
+            if (ctx->wd_lgall) HIPCHK(ctx, hipFree(ctx->wd_lgall));
+            ctx->wd_lgall = nullptr;
+            ctx->wd_lgall_cap = 0;
+            HIPCHK(ctx, hipMalloc(&ctx->wd_lgall, need * 4));
+            ctx->wd_lgall_cap = need;
+        }
+        HIPCHK(ctx, hipMemsetAsync(ctx->wd_lgall, 0, need * 4, ctx->stream));
+        ctx->wd_lg_steps = lg_steps;
+    }
+    return WMI_OK;
+}
+
+// one wide step of B x K rows: the fixed launch sequence (nothing in it depends on the step)
+int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles) {
+    const wmi_hparams &hp = ctx->hp;
+    const int n = hp.n_text_state, H = hp.n_text_head, T = ctx->enc_T, Bt = ctx->enc_clips, tctx = hp.n_text_ctx, M = B * K;
+    hipStream_t s = ctx->stream;
+    const float qs = powf((float)n / (float)H, -0.25f);
+    HIPCHK(ctx, launch_wd_embed(s, ctx->wd_tb, B, K, ctx->te, ctx->d_pe, n, hp.n_vocab, tctx, ctx->pf_x, ctx->wd_rowmap));
+    auto gemm = [&](const uint16_t *A, int Kd, const uint16_t *W, const float *bias, int N) {
+        GemmArgs g{};
+        g.tune = &ctx->tune;
+        g.A = A; g.lda = Kd; g.B = W; g.bias = bias; g.M = M; g.N = N; g.K = Kd;
+        return g;
+    };
+    WdSelfArgs sa{};
+    sa.tb = ctx->wd_tb; sa.rowmap = ctx->wd_rowmap; sa.q = ctx->pf_q16; sa.out = ctx->pf_att16;
+    sa.n = n; sa.H = H; sa.tctx = tctx; sa.Kb = K;
+    WdCrossArgs ca{};
+    ca.tb = ctx->wd_tb; ca.rowmap = ctx->wd_rowmap; ca.q = ctx->pf_q16; ca.part = ctx->wd_part; ca.out = ctx->pf_att16;
+    ca.n = n; ca.H = H; ca.T = T; ca.Kb = K; ca.B = B; ca.chunks = chunks; ca.tiles = tiles;
+    for (int l = 0; l < ctx->dec_layers; ++l) {
+        const DecLayerDev &d = ctx->dec[l];
+        HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, d.ln1_w, d.ln1_b, ctx->pf_ln16, nullptr));
+        GemmArgs g = gemm(ctx->pf_ln16, n, d.wqkv, nullptr, 3 * n);
+        g.out32 = ctx->pf_qkv32; g.ldo = 3 * n;
+        HIPCHK(ctx, launch_gemm(s, EPI_F32, g));
+        PfQkvArgs qa{};
+        qa.acc = ctx->pf_qkv32; qa.bias = d.bqkv; qa.rowmap = ctx->wd_rowmap; qa.q = ctx->pf_q16;
+        qa.k = ctx->wd_k + (size_t)l * ctx->wd_rows * tctx * n;
+        qa.v = ctx->wd_v + (size_t)l * ctx->wd_rows * tctx * n;
+        qa.M = M; qa.N = 3 * n; qa.n = n; qa.qscale = qs;
+        HIPCHK(ctx, launch_wd_qkv_store(s, qa));
+        sa.K = qa.k; sa.V = qa.v;
+        HIPCHK(ctx, launch_wd_self_attn(s, sa, M));
+        g = gemm(ctx->pf_att16, n, d.wo, d.bo, n);
+        g.out32 = ctx->pf_x; g.ldo = n;
+        HIPCHK(ctx, launch_gemm(s, EPI_RESID, g));
+        HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, d.lnc_w, d.lnc_b, ctx->pf_ln16, nullptr));
+        g = gemm(ctx->pf_ln16, n, d.wcq, nullptr, n);
+        g.out32 = ctx->pf_qkv32; g.ldo = n;
+        HIPCHK(ctx, launch_gemm(s, EPI_F32, g));
+        qa.bias = d.bcq; qa.N = n;  // (the q part alone)
+        HIPCHK(ctx, launch_wd_qkv_store(s, qa));
+        ca.K = ctx->ck + (size_t)l * Bt * T * n; ca.V = ctx->cv + (size_t)l * Bt * T * n;
+        HIPCHK(ctx, launch_wd_cross_attn(s, ca));
+        g = gemm(ctx->pf_att16, n, d.wco, d.bco, n);
+        g.out32 = ctx->pf_x; g.ldo = n;
+        HIPCHK(ctx, launch_gemm(s, EPI_RESID, g));
+        HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, d.ln2_w, d.ln2_b, ctx->pf_ln16, nullptr));
+        g = gemm(ctx->pf_ln16, n, d.w0, d.b0, 4 * n);
+        g.out16 = ctx->pf_hid16; g.ldo = 4 * n; g.gelu_tab = ctx->gelu_tab; g.gelu_min = gelu_min_of(ctx);
+        HIPCHK(ctx, launch_gemm(s, EPI_GELU16, g));
+        g = gemm(ctx->pf_hid16, 4 * n, d.w1, d.b1, n);
+        g.out32 = ctx->pf_x; g.ldo = n;
+        HIPCHK(ctx, launch_gemm(s, EPI_RESID, g));
+    }
+    HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, ctx->dln_w, ctx->dln_b, ctx->pf_ln16, nullptr));
+    GemmArgs g = gemm(ctx->pf_ln16, n, ctx->te, nullptr, hp.n_vocab);
+    g.out32 = ctx->wd_logits; g.ldo = hp.n_vocab;
+    HIPCHK(ctx, launch_gemm(s, EPI_F32, g));
+    WdBeamArgs ba{};
+    ba.tb = ctx->wd_tb; ba.logits = ctx->wd_logits; ba.V = hp.n_vocab; ba.K = K; ba.B = B; ba.eot = ctx->sp.eot; ba.tctx = tctx;
+    ba.beg = ctx->sp.beg; ba.sot = ctx->sp.sot; ba.solm = ctx->sp.solm; ba.not_ = ctx->sp.not_;
+    ba.lg_all = ctx->d_lgall ? ctx->wd_lgall : nullptr; ba.lg_steps = ctx->wd_lg_steps;
+    HIPCHK(ctx, launch_wd_beam_step(s, ba));
+    return WMI_OK;
+}
+
+// One timestamped beam window for each of the B <= 8 encoded clips b0 .. b0 + B - 1, K hypotheses each, on the
+// wide step: clip b0 + c after prompts[c].  Per recording run_ts_beam_window's search (`ruled` false); recordings do
+// not interact, one whose search is done freezes while the others go on.  The prompts' positions 0 .. np_c - 2 go
+// through one prefill pass into wide-cache slot c K, which every hypothesis' history names; the steps follow in
+// chunks of 16 with a look at the done words.  out[c] = the chosen hypothesis' records, scores[c] its score.
+int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector<std::vector<int32_t>> &prompts, int max_tokens,
+                       std::vector<std::vector<TsRec>> *out, std::vector<double> *scores) {
+    const wmi_hparams &hp = ctx->hp;
+    const int tctx = hp.n_text_ctx;
+    if (ctx->enc_T <= 0 || ctx->enc_clips < 1) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
+    if (K < 1 || K > BEAM_MAX) return set_err(ctx, WMI_E_INVALID_ARG, "beam size %d outside [1, %d]", K, BEAM_MAX);
+    if (B < 1 || B > DEC_ROWS || (int)prompts.size() != B || b0 < 0 || b0 + B > ctx->enc_clips)
+        return set_err(ctx, WMI_E_INVALID_ARG, "rows [%d, %d) outside the %d encoded clips", b0, b0 + B, ctx->enc_clips);
+    int rc = wide_unsupported(ctx);
+    if (rc) return rc;
+    int pmax = 0;
+    for (const auto &p : prompts) {
+        const int np = (int)p.size();
+        if (np < 1 || max_tokens < 1 || np + max_tokens > tctx)
+            return set_err(ctx, WMI_E_INVALID_ARG, "prompt %d + max_tokens %d exceed n_text_ctx %d", np, max_tokens, tctx);
+        if (np - 1 > PF_MAX_KEYS)
+            return set_err(ctx, WMI_E_UNSUPPORTED, "a prefill pass holds at most %d positions (%d)", PF_MAX_KEYS, np - 1);
+        pmax = std::max(pmax, np);
+    }
+    const int R = B * K;
+    int cus = 256, chunks = 1, tiles = 1;
+    HIPCHK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    wd_cross_split(ctx->enc_T, B, hp.n_text_head, cus, &chunks, &tiles);
+    rc = ensure_decode_buffers(ctx, B * pmax, 1);
+    if (rc) return rc;
+    int pf_rows = R;
+    for (const auto &p : prompts) pf_rows = std::max(pf_rows, (int)p.size() - 1);  // (a lower bound: the pass grows it)
+    rc = ensure_pf_buffers(ctx, pf_rows, false);
+    if (rc) return rc;
+    rc = ensure_wide_buffers(ctx, R, B, K, chunks, max_tokens);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    // the prompts, the table and the prefill
+    std::vector<int32_t> feed((size_t)B * pmax, -1);
+    WdRec recs[DEC_ROWS] = {};
+    BeamState bs[DEC_ROWS] = {};
+    PfRecs pf{};
+    pf.n = B;
+    for (int c = 0; c < B; ++c) {
+        const int np = (int)prompts[c].size();
+        std::copy(prompts[c].begin(), prompts[c].end(), feed.begin() + (size_t)c * pmax);
+        recs[c].clip = b0 + c; recs[c].p = np - 1; recs[c].np = np; recs[c].max_tokens = max_tokens;
+        recs[c].last_tok = prompts[c].back();
+        bs[c].n_active = 1;
+        pf.r[c].slot = c * K; pf.r[c].clip = b0 + c; pf.r[c].lo = 0; pf.r[c].len = np - 1;
+    }
+    ctx->ts_prompt = feed;
+    memset(ctx->ts_lo, 0, sizeof ctx->ts_lo);  // (no row is right-aligned: every recording starts at its own position)
+    ctx->ts_lo[0] = B;
+    ctx->ts_lo[1] = pmax;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->dfeed, feed.data(), feed.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->wd_tb.recs, recs, sizeof recs, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->wd_tb.bs, bs, sizeof bs, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemsetAsync(ctx->wd_tb.kv_src, 0, (size_t)DEC_ROWS * BEAM_MAX * tctx * 4, s));  // (the prompt's keys: slot 0)
+    rc = prefill_pass(ctx, pf, pmax, false, ctx->wd_k, ctx->wd_v, ctx->wd_rows);
+    if (rc) return rc;
+    // The steps replay one captured graph.  Its key holds every address and capacity the launches carry (the pf_*
+    // buffers are offsets of pf_x by pf_cap, the cache layers of wd_k by wd_rows).  A configuration's very first step
+    // is enqueued as it is: the GEMM launchers may set a kernel's LDS attribute at their first launch, which a
+    // capture must not hold; from then on every step of every run, the first included, is a replay.
+    char key[224];
+    snprintf(key, sizeof key, "wide/%d/%d/%d/%d/%d/%d/%p/%d/%p/%d/%p/%p/%d", B, K, chunks, tiles, ctx->enc_T, ctx->enc_clips,
+             (void *)ctx->pf_x, ctx->pf_cap, (void *)ctx->wd_k, ctx->wd_rows, (void *)ctx->wd_part,
+             (void *)(ctx->d_lgall ? ctx->wd_lgall : nullptr), ctx->d_lgall ? ctx->wd_lg_steps : 0);
+    wmi_context::Graph *graph = nullptr;
+    if (ctx->use_graph) {
+        auto it = ctx->graphs.find(key);
+        if (it != ctx->graphs.end()) graph = &it->second;
+    }
+    int steps = 0;
+    for (int done = 0; done < max_tokens;) {
+        const int chunk = std::min(16, max_tokens - done);
+        for (int i = 0; i < chunk; ++i, ++steps) {
+            if (!ctx->use_graph || (!graph && steps == 0)) {
+                rc = enqueue_wide_step(ctx, B, K, chunks, tiles);
+                if (rc) return rc;
+                continue;
+            }
+            if (!graph) {
+                if (ctx->graphs.size() >= 32) ctx->clear_graphs();
+                HIPCHK(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+                rc = enqueue_wide_step(ctx, B, K, chunks, tiles);
+                hipGraph_t gr = nullptr;
+                hipError_t ce = hipStreamEndCapture(s, &gr);
+                if (rc) { if (gr) (void)hipGraphDestroy(gr); return rc; }
+                HIPCHK(ctx, ce);
+                wmi_context::Graph g;
+                g.graph = gr;
+                hipError_t ie = hipGraphInstantiate(&g.exec, gr, nullptr, nullptr, 0);
+                if (ie != hipSuccess) { (void)hipGraphDestroy(gr); HIPCHK(ctx, ie); }
+                graph = &ctx->graphs.emplace(key, g).first->second;
+            }
+            HIPCHK(ctx, hipGraphLaunch(graph->exec, s));
+        }
+        done += chunk;
+        if (done >= max_tokens) break;
+        HIPCHK(ctx, hipMemcpyAsync(bs, ctx->wd_tb.bs, (size_t)B * sizeof(BeamState), hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        bool all = true;
+        for (int c = 0; c < B; ++c) all = all && bs[c].done != 0;
+        if (all) break;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(bs, ctx->wd_tb.bs, (size_t)B * sizeof(BeamState), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(recs, ctx->wd_tb.recs, (size_t)B * sizeof(WdRec), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    ctx->last_run_steps = steps;
+    memset(ctx->wd_last, 0, sizeof ctx->wd_last);
+    ctx->wd_last[0] = B; ctx->wd_last[1] = K; ctx->wd_last[2] = steps;
+    for (int c = 0; c < B; ++c) ctx->wd_last[3 + c] = recs[c].p;
+    out->assign((size_t)B, {});
+    if (scores) scores->assign((size_t)B, 0.0);
+    for (int c = 0; c < B; ++c) {
+        const int ns = bs[c].n_steps;
+        if (ns < 1 || ns > max_tokens) return set_err(ctx, WMI_E_HIP, "beam search of row %d produced %d steps", c, ns);
+        std::vector<int32_t> hpar((size_t)ns * BEAM_MAX);
+        std::vector<TsRec> hrec((size_t)ns * BEAM_MAX), frec(BEAM_MAX);
+        const TsRec *drec = ctx->wd_tb.hist_rec + (size_t)c * (tctx + 1) * BEAM_MAX;
+        HIPCHK(ctx, hipMemcpy(hpar.data(), ctx->wd_tb.hist_parent + (size_t)c * tctx * BEAM_MAX, hpar.size() * 4,
+                              hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(hrec.data(), drec, hrec.size() * sizeof(TsRec), hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(frec.data(), drec + (size_t)tctx * BEAM_MAX, frec.size() * sizeof(TsRec), hipMemcpyDeviceToHost));
+        const BeamPick pk = pick_beam_hypothesis(bs[c], K, ns);
+        if (pk.src < 0) return set_err(ctx, WMI_E_HIP, "beam search of row %d left no hypothesis", c);
+        std::vector<TsRec> &o = (*out)[c];
+        if (pk.src == 0) {
+            const int t = bs[c].fin_t[pk.i];
+            if (t > 0) o = beam_backtrack(hpar, hrec, t - 1, bs[c].fin_beam[pk.i]);
+            o.push_back(frec[pk.i]);
+            if (scores) (*scores)[c] = bs[c].fin_score[pk.i];
+        } else {
+            o = beam_backtrack(hpar, hrec, ns - 1, pk.i);
+            if (scores) (*scores)[c] = bs[c].score[pk.i];
+        }
+    }
+    return WMI_OK;
+}
+
 }  // namespace
 
 // An exception (host allocation failure on a hostile file, an internal
@@ -3913,6 +4227,9 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->d_samp_rows) (void)hipFree(ctx->d_samp_rows);
     if (ctx->pf_x) (void)hipFree(ctx->pf_x);
     if (ctx->pf_logits) (void)hipFree(ctx->pf_logits);
+    for (void *p : {(void *)ctx->wd_k, (void *)ctx->wd_v, ctx->wd_tab, (void *)ctx->wd_logits, (void *)ctx->wd_part,
+                    (void *)ctx->wd_lgall})
+        if (p) (void)hipFree(p);
     if (ctx->d_rule_m0) (void)hipFree(ctx->d_rule_m0);
     if (ctx->d_rb_hist) (void)hipFree(ctx->d_rb_hist);
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
@@ -4227,6 +4544,58 @@ static int wmi_transcribe_impl(wmi_context *ctx, const float *pcm, size_t n_samp
     return WMI_OK;
 }
 
+// a batched transcription at a beam size under wmi_set_batch_beam: what the wide step does not carry
+static int batch_beam_unsupported(wmi_context *ctx) {
+    if (ctx->beam_size <= 1 || !ctx->batch_beam) return WMI_OK;
+    int rc = wide_unsupported(ctx);
+    if (rc) return rc;
+    if (ctx->rules_on)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "beam search in the batch does not carry the decoding rules "
+                       "(wmi_set_decode_rules(ctx, NULL), or wmi_transcribe per recording)");
+    if (ctx->fb_on)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "beam search in the batch does not carry the temperature fallback: a round "
+                       "would hold beam rows and sampled rows at once (wmi_set_fallback(ctx, NULL), or wmi_transcribe)");
+    return WMI_OK;
+}
+
+// One beam window per encoded clip on the wide step, in rounds of up to DEC_ROWS clips, clip b after its own prompt
+static int wmi_decode_timestamps_beam_rows_impl(wmi_context *ctx, int beam_size, const int32_t *prompts, int prompt_stride,
+                                                const int32_t *n_prompt, int max_tokens, wmi_token_data *out, int32_t *n_out,
+                                                double *score) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (!prompts || !n_prompt || prompt_stride < 1 || max_tokens < 1 || !out || !n_out)
+        return set_err(ctx, WMI_E_INVALID_ARG, "null prompts / n_prompt / out / n_out, or prompt_stride %d / max_tokens %d below 1",
+                       prompt_stride, max_tokens);
+    if (beam_size < 1 || beam_size > BEAM_MAX)
+        return set_err(ctx, WMI_E_INVALID_ARG, "beam size %d outside [1, %d]", beam_size, BEAM_MAX);
+    if (ctx->enc_T <= 0 || ctx->enc_clips < 1) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
+    const int Bt = ctx->enc_clips;
+    for (int b = 0; b < Bt; ++b) {
+        if (n_prompt[b] < 1 || n_prompt[b] > prompt_stride)
+            return set_err(ctx, WMI_E_INVALID_ARG, "n_prompt[%d] = %d outside [1, prompt_stride=%d]", b, n_prompt[b], prompt_stride);
+        int rc = check_ts_args(ctx, prompts + (size_t)b * prompt_stride, n_prompt[b], max_tokens, out, n_out);
+        if (rc) return rc;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    for (int b0 = 0; b0 < Bt; b0 += DEC_ROWS) {
+        const int B = std::min(DEC_ROWS, Bt - b0);
+        std::vector<std::vector<int32_t>> pr((size_t)B);
+        for (int b = 0; b < B; ++b) {
+            const int32_t *p = prompts + (size_t)(b0 + b) * prompt_stride;
+            pr[b].assign(p, p + n_prompt[b0 + b]);
+        }
+        std::vector<std::vector<TsRec>> rec;
+        std::vector<double> sc;
+        int rc = run_wide_beam_rows(ctx, b0, B, beam_size, pr, max_tokens, &rec, &sc);
+        if (rc) return rc;
+        for (int b = 0; b < B; ++b) {
+            copy_out_tokens(rec[b], out + (size_t)(b0 + b) * max_tokens, n_out + b0 + b);
+            if (score) score[b0 + b] = sc[b];
+        }
+    }
+    return WMI_OK;
+}
+
 static int wmi_decode_timestamps_batch_impl(wmi_context *ctx, const int32_t *prompt, int n_prompt, int max_tokens,
                                             wmi_token_data *out, int32_t *n_out) {
     int rc = check_ts_args(ctx, prompt, n_prompt, max_tokens, out, n_out);
@@ -4292,9 +4661,10 @@ static int wmi_transcribe_batch_impl(wmi_context *ctx, int n_clips, const float 
         return set_err(ctx, WMI_E_INVALID_ARG, "n_clips %d outside [1, max_clips=%d]", n_clips, ctx->max_clips);
     if (!pcm || !n_samples || !n_segments) return set_err(ctx, WMI_E_INVALID_ARG, "null pcm / n_samples / n_segments");
     if (max_tokens < 1) return set_err(ctx, WMI_E_INVALID_ARG, "max_tokens %d below 1", max_tokens);
-    if (ctx->beam_size > 1)  // (8 recordings x K hypotheses do not fit the 8 decoder rows; no silent greedy)
+    if (ctx->beam_size > 1 && !ctx->batch_beam)  // (8 recordings x K hypotheses do not fit the 8 decoder rows; no silent greedy)
         return set_err(ctx, WMI_E_UNSUPPORTED, "wmi_transcribe_batch decodes greedily only: beam size %d is set "
                        "(wmi_set_beam_size(ctx, 1), or wmi_transcribe per recording)", ctx->beam_size);
+    if (batch_beam_unsupported(ctx)) return WMI_E_UNSUPPORTED;
     if (best_of_unsupported(ctx, "wmi_transcribe_batch")) return WMI_E_UNSUPPORTED;
     for (int c = 0; c < n_clips; ++c)  // (wmi_set_language / wmi_set_task refuse these; checked where they are used)
         if (ctx->n_lang == 0 && (ctx->lang_set[c] != 0 || ctx->task != WMI_TASK_TRANSCRIBE))
@@ -4948,9 +5318,10 @@ static int wmi_transcribe_audio_batch_impl(wmi_context *ctx, int n_clips, const 
         return set_err(ctx, WMI_E_INVALID_ARG, "n_clips %d outside [1, max_clips=%d]", n_clips, ctx->max_clips);
     if (!clips || !n_segments) return set_err(ctx, WMI_E_INVALID_ARG, "null clips / n_segments");
     if (max_tokens < 1) return set_err(ctx, WMI_E_INVALID_ARG, "max_tokens %d below 1", max_tokens);
-    if (ctx->beam_size > 1)  // (as wmi_transcribe_batch)
+    if (ctx->beam_size > 1 && !ctx->batch_beam)  // (as wmi_transcribe_batch)
         return set_err(ctx, WMI_E_UNSUPPORTED, "wmi_transcribe_audio_batch decodes greedily only: beam size %d is set "
                        "(wmi_set_beam_size(ctx, 1), or wmi_transcribe_audio per recording)", ctx->beam_size);
+    if (batch_beam_unsupported(ctx)) return WMI_E_UNSUPPORTED;
     if (best_of_unsupported(ctx, "wmi_transcribe_audio_batch")) return WMI_E_UNSUPPORTED;
     for (int c = 0; c < n_clips; ++c)
         if (ctx->n_lang == 0 && (ctx->lang_set[c] != 0 || ctx->task != WMI_TASK_TRANSCRIBE))
@@ -5381,6 +5752,21 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
             memcpy(out, v, std::min(sizeof v, bytes));
             return WMI_OK;
         }
+        case 38: {  // host, int32 [11]: the last wide run's recordings B, hypotheses K, steps and each recording's position p_c
+            memcpy(out, ctx->wd_last, std::min(sizeof ctx->wd_last, bytes));
+            return WMI_OK;
+        }
+        case 39:  // WMI_LOGITS_ALL: the last wide run's logits, f32 [B][max_tokens][K][V] (row k of recording c's step t)
+            if (!ctx->wd_lgall || ctx->wd_last[0] < 1) return WMI_E_INVALID_ARG;
+            src = ctx->wd_lgall;
+            have = (size_t)ctx->wd_last[0] * ctx->wd_lg_steps * ctx->wd_last[1] * ctx->hp.n_vocab * 4;
+            break;
+        case 40:  // the last wide run's parent slots, int32 [8][n_text_ctx][BEAM_MAX] (recording, step, slot)
+        case 41:  // ... and the slots' tokens
+            if (!ctx->wd_tab) return WMI_E_INVALID_ARG;
+            src = which == 40 ? ctx->wd_tb.hist_parent : ctx->wd_tb.hist_tok;
+            have = (size_t)DEC_ROWS * ctx->hp.n_text_ctx * BEAM_MAX * 4;
+            break;
         case 11: {  // host: decodes re-run on the kernel chain after a persistent exchange timeout
             const int32_t v = ctx->n_fallbacks;
             memcpy(out, &v, std::min(sizeof v, bytes));
@@ -5565,6 +5951,21 @@ int wmi_set_rules_beam(wmi_context *ctx, int enable) {
     if (enable != 0 && enable != 1) return set_err(ctx, WMI_E_INVALID_ARG, "enable %d is neither 0 nor 1", enable);
     ctx->rules_beam = enable != 0;
     return WMI_OK;
+}
+
+int wmi_set_batch_beam(wmi_context *ctx, int enable) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    if (enable != 0 && enable != 1) return set_err(ctx, WMI_E_INVALID_ARG, "enable %d is neither 0 nor 1", enable);
+    ctx->batch_beam = enable != 0;
+    return WMI_OK;
+}
+
+int wmi_decode_timestamps_beam_rows(wmi_context *ctx, int beam_size, const int32_t *prompts, int prompt_stride,
+                                    const int32_t *n_prompt, int max_tokens, wmi_token_data *out, int32_t *n_out, double *score) {
+    return guarded(ctx, [&] {
+        return wmi_decode_timestamps_beam_rows_impl(ctx, beam_size, prompts, prompt_stride, n_prompt, max_tokens, out, n_out,
+                                                    score);
+    });
 }
 
 int wmi_decode_timestamps_beam(wmi_context *ctx, int beam_size, const int32_t *prompt, int n_prompt, int max_tokens,

@@ -560,6 +560,66 @@ hipError_t launch_pf_cross_attn(hipStream_t s, const PfAttnArgs &a);
 // cross-attention's arrival counters where pos steps leave them (cnt = pos * chunks; sync null: none)
 hipError_t launch_pf_start(hipStream_t s, DecState *st, int pos, XSync *sync, int n_sync, uint32_t cnt);
 
+// ---- beam search in the batch (wmi_wide.hip; DESIGN.md "Beam search in the batch"): one decoder step over
+// R = B * K rows, row r = c * K + k hypothesis k of recording c of the round.  Nothing that changes from step to
+// step is a kernel argument: positions, done words and histories live in the device table below, so the step's
+// launch sequence is one captured graph, replayed
+constexpr int WD_ROWS = DEC_ROWS * BEAM_MAX;  // 64
+struct WdRec {               // one recording of the round
+    int32_t clip;            // its encoder slot
+    int32_t p;               // position of the token its rows process at the next step (advanced by k_wd_beam_select)
+    int32_t np;              // its prompt's tokens: generated token t is fed at position np + t
+    int32_t max_tokens;
+    int32_t last_tok;        // the prompt's last token (fed at t = 0)
+    int32_t pad[3];
+};
+struct WdTable {             // device pointers, one block per recording each
+    WdRec *recs;             // [B]
+    BeamState *bs;           // [B]
+    int32_t *kv_src;         // [B][BEAM_MAX][tctx] slots local to the recording
+    int32_t *hist_parent, *hist_tok;  // [B][tctx][BEAM_MAX]
+    TsRec *hist_rec;         // [B][tctx + 1][BEAM_MAX]: per (step, slot), then per finished hypothesis
+    TsBeamPart *tparts;      // [B][BEAM_MAX][BEAM_NS]
+};
+// x[r] = te[tok] + pe[p_c] (zero for an idle row: its recording done, or k >= n_active) and rowmap[r] =
+// (c K + k) tctx + p_c, -1 for an idle row
+hipError_t launch_wd_embed(hipStream_t s, const WdTable &tb, int B, int K, const uint16_t *te, const float *pe, int n, int V,
+                           int tctx, float *x, int32_t *rowmap);
+// launch_pf_qkv_store that skips the cache stores of idle rows (rowmap < 0)
+hipError_t launch_wd_qkv_store(hipStream_t s, const PfQkvArgs &a);
+struct WdSelfArgs {
+    WdTable tb;
+    const int32_t *rowmap;   // [R]
+    const uint16_t *q;       // [R][n] f16, scaled
+    const uint16_t *K, *V;   // a layer's wide cache [R][tctx][n]
+    uint16_t *out;           // [R][n] f16
+    int n, H, tctx, Kb;      // Kb: hypotheses a recording
+};
+hipError_t launch_wd_self_attn(hipStream_t s, const WdSelfArgs &a, int R);
+struct WdCrossArgs {
+    WdTable tb;
+    const int32_t *rowmap;   // [R]
+    const uint16_t *q;       // [R][n] f16, scaled
+    const uint16_t *K, *V;   // a layer's cross K / V [Bt][T][n]
+    float *part;             // [B][H][chunks][16][WD_PART] f32 partials {m, l, o[64]}
+    uint16_t *out;           // [R][n] f16
+    int n, H, T, Kb, B;
+    int chunks, tiles;       // key chunks a (recording, head); 64-key tiles a chunk (chunks * tiles covers T)
+};
+constexpr int WD_PART = 66;
+// key chunks so that B * H * chunks covers `cus` workgroups (every chunk holds a key below T)
+void wd_cross_split(int T, int B, int H, int cus, int *chunks, int *tiles);
+hipError_t launch_wd_cross_attn(hipStream_t s, const WdCrossArgs &a);  // k_wd_cross_attn, then k_wd_cross_combine
+struct WdBeamArgs {
+    WdTable tb;
+    const float *logits;     // [R][V]
+    int V, K, B, eot, tctx, beg, sot, solm, not_;
+    float *lg_all;           // WMI_LOGITS_ALL: [B][lg_steps][K][V], row k of recording c's step t (null: not kept)
+    int lg_steps;
+};
+// (the logits capture,) k_wd_beam_part, k_wd_beam_select: wmi_tsbeam.hip's step for every recording of the round
+hipError_t launch_wd_beam_step(hipStream_t s, const WdBeamArgs &a);
+
 // ---- persistent decoder: one launch runs n_steps greedy decoder steps -------
 // (wmi_persist.hip).  Every decoder step is a fixed sequence of phases; the
 // workgroups of the launch (all co-resident, one per CU) hand each phase's

@@ -27,6 +27,8 @@ namespace wmi {
 // sot / solm / not, and each set's sum of exponentials against that set's own
 // split maximum (accumulated directly, never as a difference).  Splits without
 // a timestamp id (all but the last one or two) skip the timestamp work.
+// (k_wd_beam_part / k_wd_beam_select of wmi_wide.hip repeat the bodies of the two kernels below, per recording
+// of a round: a change to the statistics or to the rows' rule here is made there too)
 __global__ __launch_bounds__(256) void k_tsbeam_part(TsBeamArgs ta) {
     const BeamArgs &a = ta.b;
     const int sp = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;

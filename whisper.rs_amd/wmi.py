@@ -72,6 +72,7 @@ EXPORTS = (
     "wmi_set_rules_beam", "wmi_decode_timestamps_ruled_beam",
     "wmi_set_best_of", "wmi_decode_timestamps_best_of", "wmi_best_of_key", "wmi_get_window_candidate",
     "wmi_set_prefill", "wmi_prefill_logits",
+    "wmi_set_batch_beam", "wmi_decode_timestamps_beam_rows",
     "wmi_is_non_speech_token", "wmi_set_token_timestamps", "wmi_token_times",
     "wmi_set_dtw", "wmi_align_tokens", "wmi_dtw_path", "wmi_dtw_path_host", "wmi_get_segment_dtw_of",
     "wmi_audio_to_mel_batch", "wmi_stage_audio", "wmi_transcribe_audio", "wmi_transcribe_audio_batch", "wmi_get_pcm",
@@ -244,6 +245,9 @@ def lib():
         if hasattr(L, "wmi_set_prefill"):  # (as above: an older build has no prompt prefill)
             L.wmi_set_prefill.argtypes = [vp, C.c_int]
             L.wmi_prefill_logits.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+        if hasattr(L, "wmi_set_batch_beam"):  # (as above: an older build has no beam search in the batch)
+            L.wmi_set_batch_beam.argtypes = [vp, C.c_int]
+            L.wmi_decode_timestamps_beam_rows.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
         if hasattr(L, "wmi_set_token_timestamps"):  # (as above: an older build has no token-level timestamps)
             L.wmi_set_token_timestamps.argtypes = [vp, C.POINTER(TokenTsParams)]
             L.wmi_token_times.argtypes = [vp, vp, sz, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int]
@@ -572,7 +576,8 @@ class WhisperContext:
 
     def set_beam_size(self, k: int) -> None:
         """Hypotheses of every transcribe() window (1..8; 1, the default, is
-        the greedy sampler).  transcribe_batch() refuses a size above 1."""
+        the greedy sampler).  transcribe_batch() refuses a size above 1
+        unless set_batch_beam(1) is on."""
         _raise(lib().wmi_set_beam_size(self._h, int(k)), self._h)
 
     def decode_timestamps_batch(self, prompt, max_tokens: int):
@@ -608,6 +613,43 @@ class WhisperContext:
         _raise(lib().wmi_decode_timestamps_rows(self._h, _ptr(flat), _ptr(lens), stride, max_tokens, out, _ptr(n)),
                self._h)
         return [[out[c * max_tokens + i].as_dict() for i in range(n[c])] for c in range(self.n_clips)]
+
+    def set_batch_beam(self, enable=1) -> None:
+        """1: transcribe_batch() at a beam size above 1 decodes every round's
+        windows as beam windows on the wide decoder step; 0, the default: it
+        stays Unsupported.  Neither: InvalidArgument."""
+        _raise(lib().wmi_set_batch_beam(self._h, int(enable)), self._h)
+
+    def decode_timestamps_beam_rows(self, beam_size: int, prompts, max_tokens: int):
+        """decode_timestamps_beam() for every encoded clip at once, clip b
+        after prompts[b], on the wide decoder step: per clip ([WhisperTokenData
+        dict] of the chosen hypothesis, its summed log-probability)."""
+        rows = [np.ascontiguousarray(p, dtype=np.int32).ravel() for p in prompts]
+        if len(rows) != self.n_clips:
+            raise ValueError(f"{len(rows)} prompts for {self.n_clips} clips")
+        lens = np.array([r.size for r in rows], np.int32)
+        stride = max(1, int(lens.max()) if len(rows) else 1)
+        flat = np.zeros((max(1, len(rows)), stride), np.int32)
+        for b, r in enumerate(rows):
+            flat[b, :r.size] = r
+        out = (TokenData * (max(1, self.n_clips) * max_tokens))()
+        n = np.zeros(max(1, self.n_clips), np.int32)
+        sc = np.zeros(max(1, self.n_clips), np.float64)
+        _raise(lib().wmi_decode_timestamps_beam_rows(self._h, beam_size, _ptr(flat), stride, _ptr(lens), max_tokens, out,
+                                                     _ptr(n), _ptr(sc)), self._h)
+        return [([out[c * max_tokens + i].as_dict() for i in range(n[c])], float(sc[c])) for c in range(self.n_clips)]
+
+    def wide_run(self):
+        """Debug read 38: (B, K, steps, [p_c]) of the last wide run."""
+        v = np.frombuffer(self.debug_read(38, 11 * 4), np.int32)
+        return int(v[0]), int(v[1]), int(v[2]), v[3:3 + int(v[0])].tolist()
+
+    def wide_logits(self, max_tokens: int) -> np.ndarray:
+        """Debug read 39 (WMI_LOGITS_ALL): the last wide run's logits
+        [B][max_tokens][K][n_vocab]."""
+        B, K, _, _ = self.wide_run()
+        V = self.hparams["n_vocab"]
+        return np.frombuffer(self.debug_read(39, B * max_tokens * K * V * 4), np.float32).reshape(B, max_tokens, K, V)
 
     def segments_of(self, clip: int, n_segments: int):
         """Segments of recording `clip` of the last transcribe_batch."""
