@@ -341,12 +341,25 @@ int wmi_decode_timestamps_rows(wmi_context *ctx, const int32_t *prompts, const i
  * large-v3 take 4.7 GB. */
 int wmi_decode_timestamps_beam_rows(wmi_context *ctx, int beam_size, const int32_t *prompts, int prompt_stride,
                                     const int32_t *n_prompt, int max_tokens, wmi_token_data *out, int32_t *n_out, double *score);
+/* wmi_decode_timestamps_beam_rows under the context's decoding rules
+ * (wmi_set_decode_rules): the arguments and results of that call, every clip's
+ * window the search of wmi_decode_timestamps_ruled_beam, each hypothesis' rule
+ * history carried through its recording's parent selection on the device.
+ * Clip b yields what wmi_decode_timestamps_ruled_beam yields for it alone, up
+ * to the order of the floating-point sums; beam_size 1 is the ruled sampler's
+ * choice at temperature 0.  Needs no wmi_set_rules_beam.  No rules enabled:
+ * WMI_E_INVALID_ARG. */
+int wmi_decode_timestamps_ruled_beam_rows(wmi_context *ctx, int beam_size, const int32_t *prompts, int prompt_stride,
+                                          const int32_t *n_prompt, int max_tokens, wmi_token_data *out, int32_t *n_out,
+                                          double *score);
 /* enable 1: wmi_transcribe_batch / wmi_transcribe_audio_batch with a beam size
  * above 1 (wmi_set_beam_size) decode every round's windows as beam windows on
  * the wide step, with and without wmi_set_batch_context.  A round of one
  * recording takes wmi_transcribe's beam window.  With the opt-in and a beam size above 1
  * the batch calls are WMI_E_UNSUPPORTED, checked at the call, for an f32 file,
- * with the decoding rules on, with the fallback on (a round would hold beam
+ * with the decoding rules on unless wmi_set_rules_beam is set (then every
+ * window is the ruled beam window, and recording c yields the segments of
+ * wmi_transcribe of it alone), with the fallback on (a round would hold beam
  * rows and sampled rows at once) and with best_of above 1.  enable 0
  * (default): a beam size above 1 in the batch is WMI_E_UNSUPPORTED and every
  * call launches what it launched before.  Neither 0 nor 1:

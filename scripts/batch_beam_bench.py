@@ -13,13 +13,19 @@ size BEAMS.
     host time per wide step, steps from debug read 38.  With WMI_NO_GRAPH=1
     in the environment the same figure without graph replay, run separately.
 
-A library of an earlier commit (WMI_LIB) has no opt-in: the script then times
-the sequential side alone ("batch": null).
+With --rules both sides decode under the default decoding rules with
+wmi_set_rules_beam on (the ruled beam window; in the batch the ruled wide beam
+step), and part 2 times the ruled window (wmi_decode_timestamps_ruled_beam_rows)
+beside the unruled one.
+
+A library of an earlier commit (WMI_LIB) has no opt-in, or with --rules no
+ruled wide step: the script then times the sequential side alone ("batch":
+null).
 
 Prints one JSON line.
 
 Usage: batch_beam_bench.py [--model base] [--recs 8] [--seconds 30]
-       [--beams 5] [--reps 3] [--max-tokens 32]   (needs the GPU)"""
+       [--beams 5] [--reps 3] [--max-tokens 32] [--rules]   (needs the GPU)"""
 import argparse
 import json
 import os
@@ -39,15 +45,19 @@ def main():
     ap.add_argument("--beams", type=int, default=5)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--max-tokens", type=int, default=32)
+    ap.add_argument("--rules", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import synth
     import wmi
     recs = [synth.synth_pcm_tones(a.seconds, 4000 + i) for i in range(a.recs)]
     ctx = wmi.WhisperContext.new(synth.model_path(a.model), 0, max_clips=a.recs)
-    wide = hasattr(wmi.lib(), "wmi_set_batch_beam")
+    wide = hasattr(wmi.lib(), "wmi_decode_timestamps_ruled_beam_rows" if a.rules else "wmi_set_batch_beam")
     ctx.set_no_context(True)
     ctx.set_beam_size(a.beams)
+    if a.rules:
+        ctx.set_decode_rules()
+        ctx.set_rules_beam(True)
 
     def sequential():
         t = time.perf_counter()
@@ -73,7 +83,7 @@ def main():
         if wide:
             t_bat.append(batch()[0])
     res = {"model": a.model, "recs": a.recs, "seconds": a.seconds, "beams": a.beams, "max_tokens": a.max_tokens,
-           "reps": a.reps, "graph_replay": not os.environ.get("WMI_NO_GRAPH"),
+           "reps": a.reps, "rules": a.rules, "graph_replay": not os.environ.get("WMI_NO_GRAPH"),
            "sequential_s": [round(x, 4) for x in t_seq], "sequential_s_median": round(statistics.median(t_seq), 4),
            "sequential_audio_s_per_s": round(a.recs * a.seconds / statistics.median(t_seq), 1),
            "sequential_decoder_steps": seq_steps, "batch": None}
@@ -87,16 +97,20 @@ def main():
         init = [sp["sot"]] + ([sp["sot"] + 1, sp["transcribe"]] if sp["multilingual"] else [])
         ctx.pcm_to_mel_batch([r[:30 * 16000] for r in recs])
         ctx.encode(1, 0)
+        windows = {"wide": ctx.decode_timestamps_beam_rows}
+        if a.rules:
+            windows["ruled_wide"] = ctx.decode_timestamps_ruled_beam_rows
         for K in (5, 8):
-            ctx.decode_timestamps_beam_rows(K, [init] * a.recs, a.max_tokens)
-            ts = []
-            for _ in range(a.reps):
-                t = time.perf_counter()
-                ctx.decode_timestamps_beam_rows(K, [init] * a.recs, a.max_tokens)
-                ts.append(time.perf_counter() - t)
-            steps = ctx.wide_run()[2]
-            res[f"wide_step_us_R{a.recs * K}"] = round(statistics.median(ts) * 1e6 / max(1, steps), 1)
-            res[f"wide_steps_R{a.recs * K}"] = steps
+            for name, window in windows.items():
+                window(K, [init] * a.recs, a.max_tokens)
+                ts = []
+                for _ in range(a.reps):
+                    t = time.perf_counter()
+                    window(K, [init] * a.recs, a.max_tokens)
+                    ts.append(time.perf_counter() - t)
+                steps = ctx.wide_run()[2]
+                res[f"{name}_step_us_R{a.recs * K}"] = round(statistics.median(ts) * 1e6 / max(1, steps), 1)
+                res[f"{name}_steps_R{a.recs * K}"] = steps
     ctx.close()
     print(json.dumps(res))
 

@@ -176,6 +176,9 @@ struct wmi_context {
     size_t wd_part_cap = 0, wd_lgall_cap = 0;
     int wd_lg_steps = 0;
     int32_t wd_last[3 + DEC_ROWS] = {};  // the last wide run's B, K, steps and p_c[8] (debug read 38)
+    // the wide step under the decoding rules (wmi_wide_rules.hip): the rule block, an allocation of its own made with
+    // the first ruled wide window: the hypotheses' histories [8][8], then the parts [8][8][16]
+    WdRuleTable wd_rt{};
     // batched transcription: source recording [8], then mel offset [8] of each encoder slot, then (chunked calls) its end [8]
     int32_t *d_win = nullptr;
     int32_t win_host[3 * DEC_ROWS] = {};  // host copy of the last d_win upload (debug read 22: its first two columns)
@@ -3018,7 +3021,7 @@ std::vector<int32_t> ts_init_prompt(const wmi_context *ctx, int lang) {
 int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, int K, int max_tokens,
                        std::vector<TsRec> *out, double *score, float *p_nosp = nullptr, bool ruled = false);
 int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector<std::vector<int32_t>> &prompts, int max_tokens,
-                       std::vector<std::vector<TsRec>> *out, std::vector<double> *scores);
+                       std::vector<std::vector<TsRec>> *out, std::vector<double> *scores, bool ruled);
 
 // after attempt 0: probably silence (OpenAI's no_speech_threshold rule)
 bool fb_silence(const wmi_context *ctx, float p_nosp, const FbAttempt &att) {
@@ -3153,8 +3156,8 @@ int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows,
     if (ctx->beam_size > 1 && (*out)[0].T == 0.0f) {
         if (B != 1) {
             if (!ctx->batch_beam) return set_err(ctx, WMI_E_UNSUPPORTED, "a beam window decodes one recording (%d rows)", B);
-            // (wmi_set_batch_beam: every row's beam window on the wide step; the entry points have refused rules,
-            // the fallback and f32 files)
+            // (wmi_set_batch_beam: every row's beam window on the wide step, under the rules the ruled one; the entry
+            // points have refused rules without wmi_set_rules_beam, the fallback and f32 files)
             std::vector<std::vector<int32_t>> prompts((size_t)B);
             size_t at = 0;
             for (int b = 0; b < B; ++b) {
@@ -3163,7 +3166,7 @@ int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows,
                 at += len;
             }
             std::vector<std::vector<TsRec>> toks;
-            int rc = run_wide_beam_rows(ctx, 0, B, ctx->beam_size, prompts, tr.n_max, &toks, nullptr);
+            int rc = run_wide_beam_rows(ctx, 0, B, ctx->beam_size, prompts, tr.n_max, &toks, nullptr, ctx->rules_on);
             if (rc) return rc;
             for (int b = 0; b < B; ++b) (*out)[b].toks = std::move(toks[b]);
             return WMI_OK;
@@ -3853,8 +3856,9 @@ int ensure_wide_buffers(wmi_context *ctx, int R, int B, int K, int chunks, int l
     return WMI_OK;
 }
 
-// one wide step of B x K rows: the fixed launch sequence (nothing in it depends on the step)
-int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles) {
+// one wide step of B x K rows: the fixed launch sequence (nothing in it depends on the step); with `ruled` its beam
+// step is the one under the decoding rules (k_wd_rbeam_part / k_wd_rbeam_select)
+int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles, bool ruled) {
     const wmi_hparams &hp = ctx->hp;
     const int n = hp.n_text_state, H = hp.n_text_head, T = ctx->enc_T, Bt = ctx->enc_clips, tctx = hp.n_text_ctx, M = B * K;
     hipStream_t s = ctx->stream;
@@ -3916,19 +3920,26 @@ int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles) {
     ba.tb = ctx->wd_tb; ba.logits = ctx->wd_logits; ba.V = hp.n_vocab; ba.K = K; ba.B = B; ba.eot = ctx->sp.eot; ba.tctx = tctx;
     ba.beg = ctx->sp.beg; ba.sot = ctx->sp.sot; ba.solm = ctx->sp.solm; ba.not_ = ctx->sp.not_;
     ba.lg_all = ctx->d_lgall ? ctx->wd_lgall : nullptr; ba.lg_steps = ctx->wd_lg_steps;
+    if (ruled) {
+        WdRBeamArgs ra{};
+        ra.w = ba; ra.rt = ctx->wd_rt; ra.m0 = ctx->d_rule_m0; ra.max_initial_ts = ctx->max_initial_ts;
+        HIPCHK(ctx, launch_wd_rbeam_step(s, ra));
+        return WMI_OK;
+    }
     HIPCHK(ctx, launch_wd_beam_step(s, ba));
     return WMI_OK;
 }
 
 // One timestamped beam window for each of the B <= 8 encoded clips b0 .. b0 + B - 1, K hypotheses each, on the
-// wide step: clip b0 + c after prompts[c].  Per recording run_ts_beam_window's search (`ruled` false); recordings do
-// not interact, one whose search is done freezes while the others go on.  The prompts' positions 0 .. np_c - 2 go
+// wide step: clip b0 + c after prompts[c].  Per recording run_ts_beam_window's search, with `ruled` the one under the
+// decoding rules: every hypothesis' history starts empty with the table.  Recordings do not interact, one whose search is done freezes while the others go on.  The prompts' positions 0 .. np_c - 2 go
 // through one prefill pass into wide-cache slot c K, which every hypothesis' history names; the steps follow in
 // chunks of 16 with a look at the done words.  out[c] = the chosen hypothesis' records, scores[c] its score.
 int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector<std::vector<int32_t>> &prompts, int max_tokens,
-                       std::vector<std::vector<TsRec>> *out, std::vector<double> *scores) {
+                       std::vector<std::vector<TsRec>> *out, std::vector<double> *scores, bool ruled) {
     const wmi_hparams &hp = ctx->hp;
     const int tctx = hp.n_text_ctx;
+    if (ruled && (!ctx->rules_on || !ctx->d_rule_m0)) return set_err(ctx, WMI_E_INVALID_ARG, "no decoding rules are enabled");
     if (ctx->enc_T <= 0 || ctx->enc_clips < 1) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
     if (K < 1 || K > BEAM_MAX) return set_err(ctx, WMI_E_INVALID_ARG, "beam size %d outside [1, %d]", K, BEAM_MAX);
     if (B < 1 || B > DEC_ROWS || (int)prompts.size() != B || b0 < 0 || b0 + B > ctx->enc_clips)
@@ -3957,6 +3968,15 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
     rc = ensure_wide_buffers(ctx, R, B, K, chunks, max_tokens);
     if (rc) return rc;
     hipStream_t s = ctx->stream;
+    const size_t rt_hist = (size_t)DEC_ROWS * BEAM_MAX * sizeof(RuleHist);
+    if (ruled && !ctx->wd_rt.hist) {
+        const size_t rt_parts = (size_t)DEC_ROWS * BEAM_MAX * BEAM_NS * sizeof(RBeamPart);
+        char *p = nullptr;
+        HIPCHK(ctx, hipMalloc(&p, rt_hist + rt_parts));
+        ctx->wd_rt.hist = (RuleHist *)p;
+        ctx->wd_rt.rparts = (RBeamPart *)(p + rt_hist);
+        HIPCHK(ctx, hipMemsetAsync(ctx->wd_rt.rparts, 0, rt_parts, s));
+    }
     // the prompts, the table and the prefill
     std::vector<int32_t> feed((size_t)B * pmax, -1);
     WdRec recs[DEC_ROWS] = {};
@@ -3979,16 +3999,20 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
     HIPCHK(ctx, hipMemcpyAsync(ctx->wd_tb.recs, recs, sizeof recs, hipMemcpyHostToDevice, s));
     HIPCHK(ctx, hipMemcpyAsync(ctx->wd_tb.bs, bs, sizeof bs, hipMemcpyHostToDevice, s));
     HIPCHK(ctx, hipMemsetAsync(ctx->wd_tb.kv_src, 0, (size_t)DEC_ROWS * BEAM_MAX * tctx * 4, s));  // (the prompt's keys: slot 0)
+    if (ruled) HIPCHK(ctx, hipMemsetAsync(ctx->wd_rt.hist, 0, rt_hist, s));  // (no hypothesis has sampled anything)
     rc = prefill_pass(ctx, pf, pmax, false, ctx->wd_k, ctx->wd_v, ctx->wd_rows);
     if (rc) return rc;
     // The steps replay one captured graph.  Its key holds every address and capacity the launches carry (the pf_*
     // buffers are offsets of pf_x by pf_cap, the cache layers of wd_k by wd_rows).  A configuration's very first step
     // is enqueued as it is: the GEMM launchers may set a kernel's LDS attribute at their first launch, which a
     // capture must not hold; from then on every step of every run, the first included, is a replay.
-    char key[224];
-    snprintf(key, sizeof key, "wide/%d/%d/%d/%d/%d/%d/%p/%d/%p/%d/%p/%p/%d", B, K, chunks, tiles, ctx->enc_T, ctx->enc_clips,
-             (void *)ctx->pf_x, ctx->pf_cap, (void *)ctx->wd_k, ctx->wd_rows, (void *)ctx->wd_part,
-             (void *)(ctx->d_lgall ? ctx->wd_lgall : nullptr), ctx->d_lgall ? ctx->wd_lg_steps : 0);
+    // A ruled step has a key of its own, with the rule block's address (the mask and the cap of the first timestamp
+    // change only through wmi_set_decode_rules, which drops every graph).
+    char key[256];
+    int kl = snprintf(key, sizeof key, "wide/%d/%d/%d/%d/%d/%d/%p/%d/%p/%d/%p/%p/%d", B, K, chunks, tiles, ctx->enc_T, ctx->enc_clips,
+                      (void *)ctx->pf_x, ctx->pf_cap, (void *)ctx->wd_k, ctx->wd_rows, (void *)ctx->wd_part,
+                      (void *)(ctx->d_lgall ? ctx->wd_lgall : nullptr), ctx->d_lgall ? ctx->wd_lg_steps : 0);
+    if (ruled && kl > 0 && kl < (int)sizeof key) snprintf(key + kl, sizeof key - kl, "/ruled/%p", (void *)ctx->wd_rt.hist);
     wmi_context::Graph *graph = nullptr;
     if (ctx->use_graph) {
         auto it = ctx->graphs.find(key);
@@ -3999,14 +4023,14 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
         const int chunk = std::min(16, max_tokens - done);
         for (int i = 0; i < chunk; ++i, ++steps) {
             if (!ctx->use_graph || (!graph && steps == 0)) {
-                rc = enqueue_wide_step(ctx, B, K, chunks, tiles);
+                rc = enqueue_wide_step(ctx, B, K, chunks, tiles, ruled);
                 if (rc) return rc;
                 continue;
             }
             if (!graph) {
                 if (ctx->graphs.size() >= 32) ctx->clear_graphs();
                 HIPCHK(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                rc = enqueue_wide_step(ctx, B, K, chunks, tiles);
+                rc = enqueue_wide_step(ctx, B, K, chunks, tiles, ruled);
                 hipGraph_t gr = nullptr;
                 hipError_t ce = hipStreamEndCapture(s, &gr);
                 if (rc) { if (gr) (void)hipGraphDestroy(gr); return rc; }
@@ -4232,6 +4256,7 @@ void wmi_free(wmi_context *ctx) {
         if (p) (void)hipFree(p);
     if (ctx->d_rule_m0) (void)hipFree(ctx->d_rule_m0);
     if (ctx->d_rb_hist) (void)hipFree(ctx->d_rb_hist);
+    if (ctx->wd_rt.hist) (void)hipFree(ctx->wd_rt.hist);
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -4549,7 +4574,7 @@ static int batch_beam_unsupported(wmi_context *ctx) {
     if (ctx->beam_size <= 1 || !ctx->batch_beam) return WMI_OK;
     int rc = wide_unsupported(ctx);
     if (rc) return rc;
-    if (ctx->rules_on)
+    if (ctx->rules_on && !ctx->rules_beam)  // (with wmi_set_rules_beam: the ruled wide step, wmi_wide_rules.hip)
         return set_err(ctx, WMI_E_UNSUPPORTED, "beam search in the batch does not carry the decoding rules "
                        "(wmi_set_decode_rules(ctx, NULL), or wmi_transcribe per recording)");
     if (ctx->fb_on)
@@ -4558,11 +4583,13 @@ static int batch_beam_unsupported(wmi_context *ctx) {
     return WMI_OK;
 }
 
-// One beam window per encoded clip on the wide step, in rounds of up to DEC_ROWS clips, clip b after its own prompt
+// One beam window per encoded clip on the wide step, in rounds of up to DEC_ROWS clips, clip b after its own prompt;
+// `ruled`: wmi_decode_timestamps_ruled_beam_rows, every window under the context's decoding rules
 static int wmi_decode_timestamps_beam_rows_impl(wmi_context *ctx, int beam_size, const int32_t *prompts, int prompt_stride,
                                                 const int32_t *n_prompt, int max_tokens, wmi_token_data *out, int32_t *n_out,
-                                                double *score) {
+                                                double *score, bool ruled) {
     if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (ruled && !ctx->rules_on) return set_err(ctx, WMI_E_INVALID_ARG, "no decoding rules are enabled (wmi_set_decode_rules)");
     if (!prompts || !n_prompt || prompt_stride < 1 || max_tokens < 1 || !out || !n_out)
         return set_err(ctx, WMI_E_INVALID_ARG, "null prompts / n_prompt / out / n_out, or prompt_stride %d / max_tokens %d below 1",
                        prompt_stride, max_tokens);
@@ -4586,7 +4613,7 @@ static int wmi_decode_timestamps_beam_rows_impl(wmi_context *ctx, int beam_size,
         }
         std::vector<std::vector<TsRec>> rec;
         std::vector<double> sc;
-        int rc = run_wide_beam_rows(ctx, b0, B, beam_size, pr, max_tokens, &rec, &sc);
+        int rc = run_wide_beam_rows(ctx, b0, B, beam_size, pr, max_tokens, &rec, &sc, ruled);
         if (rc) return rc;
         for (int b = 0; b < B; ++b) {
             copy_out_tokens(rec[b], out + (size_t)(b0 + b) * max_tokens, n_out + b0 + b);
@@ -5964,7 +5991,16 @@ int wmi_decode_timestamps_beam_rows(wmi_context *ctx, int beam_size, const int32
                                     const int32_t *n_prompt, int max_tokens, wmi_token_data *out, int32_t *n_out, double *score) {
     return guarded(ctx, [&] {
         return wmi_decode_timestamps_beam_rows_impl(ctx, beam_size, prompts, prompt_stride, n_prompt, max_tokens, out, n_out,
-                                                    score);
+                                                    score, false);
+    });
+}
+
+int wmi_decode_timestamps_ruled_beam_rows(wmi_context *ctx, int beam_size, const int32_t *prompts, int prompt_stride,
+                                          const int32_t *n_prompt, int max_tokens, wmi_token_data *out, int32_t *n_out,
+                                          double *score) {
+    return guarded(ctx, [&] {
+        return wmi_decode_timestamps_beam_rows_impl(ctx, beam_size, prompts, prompt_stride, n_prompt, max_tokens, out, n_out,
+                                                    score, true);
     });
 }
 

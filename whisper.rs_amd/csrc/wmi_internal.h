@@ -619,6 +619,21 @@ struct WdBeamArgs {
 };
 // (the logits capture,) k_wd_beam_part, k_wd_beam_select: wmi_tsbeam.hip's step for every recording of the round
 hipError_t launch_wd_beam_step(hipStream_t s, const WdBeamArgs &a);
+hipError_t launch_wd_logits_capture(hipStream_t s, const WdBeamArgs &a);  // k_wd_logits_capture alone (a.lg_all set)
+// ---- the wide step's beam step under the decoding rules (wmi_wide_rules.hip): wmi_rbeam.hip's step for every
+// recording of the round, every hypothesis' rule history handed on through its recording's parent selection
+struct WdRuleTable {         // device pointers into the rule block, an allocation of its own beside the table's
+    RuleHist *hist;          // [DEC_ROWS][BEAM_MAX] history of the hypothesis in slot s of recording c
+    RBeamPart *rparts;       // [DEC_ROWS][BEAM_MAX][BEAM_NS]
+};
+struct WdRBeamArgs {
+    WdBeamArgs w;            // (sot, solm, not_ unused: M0 holds them)
+    WdRuleTable rt;
+    const uint32_t *m0;      // [ceil(V / 32)] bit i set: id i is masked always (M0), one mask for all recordings
+    int max_initial_ts;      // first timestamp <= beg + this (< 0: no cap)
+};
+// (the logits capture,) k_wd_rbeam_part, k_wd_rbeam_select
+hipError_t launch_wd_rbeam_step(hipStream_t s, const WdRBeamArgs &a);
 
 // ---- persistent decoder: one launch runs n_steps greedy decoder steps -------
 // (wmi_persist.hip).  Every decoder step is a fixed sequence of phases; the

@@ -575,4 +575,11 @@ hipError_t launch_wd_beam_step(hipStream_t s, const WdBeamArgs &a) {
     return hipGetLastError();
 }
 
+// the capture alone, in front of the ruled pair of wmi_wide_rules.hip
+hipError_t launch_wd_logits_capture(hipStream_t s, const WdBeamArgs &a) {
+    if (!a.lg_all || a.K < 1 || a.K > BEAM_MAX || a.B < 1 || a.B > DEC_ROWS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_wd_logits_capture, dim3(a.B * a.K), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace wmi

@@ -72,7 +72,7 @@ EXPORTS = (
     "wmi_set_rules_beam", "wmi_decode_timestamps_ruled_beam",
     "wmi_set_best_of", "wmi_decode_timestamps_best_of", "wmi_best_of_key", "wmi_get_window_candidate",
     "wmi_set_prefill", "wmi_prefill_logits",
-    "wmi_set_batch_beam", "wmi_decode_timestamps_beam_rows",
+    "wmi_set_batch_beam", "wmi_decode_timestamps_beam_rows", "wmi_decode_timestamps_ruled_beam_rows",
     "wmi_is_non_speech_token", "wmi_set_token_timestamps", "wmi_token_times",
     "wmi_set_dtw", "wmi_align_tokens", "wmi_dtw_path", "wmi_dtw_path_host", "wmi_get_segment_dtw_of",
     "wmi_audio_to_mel_batch", "wmi_stage_audio", "wmi_transcribe_audio", "wmi_transcribe_audio_batch", "wmi_get_pcm",
@@ -248,6 +248,8 @@ def lib():
         if hasattr(L, "wmi_set_batch_beam"):  # (as above: an older build has no beam search in the batch)
             L.wmi_set_batch_beam.argtypes = [vp, C.c_int]
             L.wmi_decode_timestamps_beam_rows.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+        if hasattr(L, "wmi_decode_timestamps_ruled_beam_rows"):  # (as above: an older build has no ruled wide step)
+            L.wmi_decode_timestamps_ruled_beam_rows.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
         if hasattr(L, "wmi_set_token_timestamps"):  # (as above: an older build has no token-level timestamps)
             L.wmi_set_token_timestamps.argtypes = [vp, C.POINTER(TokenTsParams)]
             L.wmi_token_times.argtypes = [vp, vp, sz, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int]
@@ -620,7 +622,13 @@ class WhisperContext:
         stays Unsupported.  Neither: InvalidArgument."""
         _raise(lib().wmi_set_batch_beam(self._h, int(enable)), self._h)
 
-    def decode_timestamps_beam_rows(self, beam_size: int, prompts, max_tokens: int):
+    def decode_timestamps_ruled_beam_rows(self, beam_size: int, prompts, max_tokens: int):
+        """decode_timestamps_beam_rows() under the decoding rules: per clip the
+        window of decode_timestamps_ruled_beam().  No rules enabled:
+        InvalidArgument."""
+        return self.decode_timestamps_beam_rows(beam_size, prompts, max_tokens, ruled=True)
+
+    def decode_timestamps_beam_rows(self, beam_size: int, prompts, max_tokens: int, ruled: bool = False):
         """decode_timestamps_beam() for every encoded clip at once, clip b
         after prompts[b], on the wide decoder step: per clip ([WhisperTokenData
         dict] of the chosen hypothesis, its summed log-probability)."""
@@ -635,8 +643,8 @@ class WhisperContext:
         out = (TokenData * (max(1, self.n_clips) * max_tokens))()
         n = np.zeros(max(1, self.n_clips), np.int32)
         sc = np.zeros(max(1, self.n_clips), np.float64)
-        _raise(lib().wmi_decode_timestamps_beam_rows(self._h, beam_size, _ptr(flat), stride, _ptr(lens), max_tokens, out,
-                                                     _ptr(n), _ptr(sc)), self._h)
+        fn = lib().wmi_decode_timestamps_ruled_beam_rows if ruled else lib().wmi_decode_timestamps_beam_rows
+        _raise(fn(self._h, beam_size, _ptr(flat), stride, _ptr(lens), max_tokens, out, _ptr(n), _ptr(sc)), self._h)
         return [([out[c * max_tokens + i].as_dict() for i in range(n[c])], float(sc[c])) for c in range(self.n_clips)]
 
     def wide_run(self):
