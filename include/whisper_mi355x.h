@@ -515,6 +515,36 @@ int wmi_get_window_candidate(const wmi_context *ctx, int clip, int i, int32_t *c
 int wmi_set_prefill(wmi_context *ctx, int min_prompt);
 int wmi_prefill_logits(wmi_context *ctx, int clip, const int32_t *tokens, int n_tokens, float *logits);
 
+/* Quantised-weight GEMM.  A quantised file (q4_0, q4_1, q5_0, q5_1, q8_0) is
+ * dequantised to f16 copies at load, and the prompt prefill pass and the wide
+ * beam step (wmi_set_batch_beam) read those copies: 2 bytes a weight where
+ * the file holds 0.56 to 1.06.  With wmi_set_quant_gemm(ctx, 1) their dense
+ * products (six a decoder layer and the vocabulary product) read the blocks
+ * instead, on an MFMA kernel of their own (wmi_gemm_q.hip) that dequantises
+ * each weight in registers to exactly the f16 value of the copy, w =
+ * f16(fma(q - off, d, m)) rounded once.  The kernel sums in an order of its
+ * own (four K parts added in a fixed order that depends on K alone), so the
+ * results differ from the f16 kernels' within the logit bar of the parity
+ * tests, and a row's result never depends on the other rows.  0 (the
+ * default): every call launches what it launched before this interface and
+ * the context holds no more device memory.  The first switch-on reads the
+ * decoder matrices' blocks from the context's file again and uploads them as
+ * aligned planes (about the decoder's share of the file in device memory; the
+ * f16 copies stay, the one-row decoder reads them); a file that mixes
+ * quantised and f16 matrices takes the kernel matrix by matrix, and on an f16
+ * or f32 file the call succeeds and changes nothing.  A product of more than
+ * 64 activation rows (a prefill pass of a longer prompt, or of several
+ * recordings' packed rows) stays on the f16 kernels, which reuse the weights
+ * across row tiles; what was measured is in DESIGN.md, "Quantised-weight
+ * GEMM".  A switch drops the cached wide-step graphs.
+ * enable outside {0, 1} or a null context: WMI_E_INVALID_ARG.  Debug read 42
+ * counts the kernel's launches.
+ * wmi_dequant_blocks: nel / 32 raw ggml blocks of `type` (2 q4_0, 3 q4_1, 6
+ * q5_0, 7 q5_1, 8 q8_0) expanded on the current device with the kernel's own
+ * device function into out_f16 [nel] (f16 bits); needs a device, no context. */
+int wmi_set_quant_gemm(wmi_context *ctx, int enable);
+int wmi_dequant_blocks(int type, const void *raw, int64_t nel, uint16_t *out_f16);
+
 /* OpenAI's decoding rules (SuppressTokens and ApplyTimestampRules restated)
  * for every window of wmi_transcribe / wmi_transcribe_batch and for
  * wmi_decode_timestamps_ruled, in the place of the whisper.cpp-1.0.3 rule.
@@ -1025,7 +1055,9 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * position p_c [8] when it ended.  39 = under WMI_LOGITS_ALL that run's logits,
  * f32 [B][max_tokens][K][n_vocab]: row k of recording c's step t (zero where
  * the row was idle).  40 / 41 = its parent slots and slot tokens, int32
- * [8][n_text_ctx][8] (recording, step, slot). */
+ * [8][n_text_ctx][8] (recording, step, slot).  42 = the launches of the
+ * quantised-weight GEMM since the context was created (int64, host; a replayed
+ * wide-step graph counts the launches it holds). */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <map>
 #include <memory>
 #include <set>
@@ -29,6 +30,7 @@
 #include "../../include/whisper_mi355x.h"
 #include "wmi_host.h"
 #include "wmi_internal.h"
+#include "wmi_gemm_q.h"
 
 #pragma clang fp contract(off)
 
@@ -167,6 +169,18 @@ struct wmi_context {
     // allocation for the recordings' table (wd_tb) with rowmap [64] behind it, the rows' logits [64][n_vocab], the
     // cross-attention partials, and under WMI_LOGITS_ALL every row's logits of every step [B][wd_lg_steps][K][V]
     bool batch_beam = false;
+    // the quantised-weight GEMM of the prefill pass and the wide step (wmi_set_quant_gemm; wmi_gemm_q.hip).  The planes
+    // come with the first switch-on, one allocation built from the file's blocks read again (model_path): per decoder
+    // layer the six products' matrices, then the token embedding for the logits (qtype 0: f16 in the file, no planes)
+    struct QMat { int qtype = 0; const uint8_t *qn = nullptr; const uint32_t *side = nullptr; };
+    struct QLayer { QMat wqkv, wo, wcq, wco, w0, w1; };
+    std::string model_path;
+    bool qgemm = false, qplanes_built = false;
+    void *d_qplanes = nullptr;
+    std::vector<QLayer> qdec;
+    QMat qte;
+    int64_t qgemm_launches = 0;  // launch_gemm_q launches since the context was created (debug read 42)
+    int qgemm_max_rows = 0;      // the launch rule's row count (QGEMM_MAX_ROWS, or WMI_QGEMM_MAX_ROWS)
     uint16_t *wd_k = nullptr, *wd_v = nullptr;
     int wd_rows = 0;
     void *wd_tab = nullptr;
@@ -315,7 +329,7 @@ struct wmi_context {
     hipEvent_t ev[8] = {};
     wmi_timings timings{};
     // decode graph cache
-    struct Graph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
+    struct Graph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int qlaunches = 0; /* launch_gemm_q nodes */ };
     std::map<std::string, Graph> graphs;  // captured decoder steps by configuration
     void clear_graphs() {
         for (auto &kv : graphs) {
@@ -2261,6 +2275,102 @@ int ensure_pf_buffers(wmi_context *ctx, int M, bool logits) {
     return WMI_OK;
 }
 
+// ---- the quantised-weight GEMM (wmi_set_quant_gemm; wmi_gemm_q.hip; DESIGN.md "Quantised-weight GEMM") ----
+// Above this many activation rows a product stays on launch_gemm: k_gemm_q reads and dequantises the weights once
+// per 64-row tile, the f16 tile kernels reuse them from LDS.  Measured (profiles/quant_gemm/quant_gemm_bench.json,
+// "rows_sweep_ms"): the kernel wins only in its first tile (the wide step at large-v3 shapes, 64 rows and below); a
+// pass of 64 to 256 rows is slower on it at base and at large-v3 shapes alike.  (The parity tests of the kernel's row
+// tiling raise the rule in their own contexts, WMI_QGEMM_MAX_ROWS, as the sweep itself does.)
+constexpr int QGEMM_MAX_ROWS = 64;
+
+// a dense product of the prefill pass or the wide step: on the matrix' blocks where the opt-in is on and the planes
+// are there, else launch_gemm as before
+hipError_t dense_product(wmi_context *ctx, hipStream_t s, int epi, const GemmArgs &g, const wmi_context::QMat *qm) {
+    if (!ctx->qgemm || !qm || !qm->qn || g.M > ctx->qgemm_max_rows) return launch_gemm(s, epi, g);
+    GemmQArgs q{};
+    q.g = g;
+    q.qtype = qm->qtype;
+    q.qn = qm->qn;
+    q.side = qm->side;
+    ++ctx->qgemm_launches;
+    return launch_gemm_q(s, epi, q);
+}
+const wmi_context::QLayer *qlayer_of(const wmi_context *ctx, int l) {
+    return ctx->qgemm && l < (int)ctx->qdec.size() ? &ctx->qdec[l] : nullptr;
+}
+
+// The planes of every decoder matrix the file holds quantised, from its blocks read again through the host-only
+// loader: one device allocation, every plane 256-byte aligned
+int build_qplanes(wmi_context *ctx) {
+    ParsedModel pm;
+    std::string err;
+    int rc = parse_file(ctx->model_path.c_str(), pm, err, true);  // (the decoder's blocks alone)
+    if (rc) return set_err(ctx, rc, "%s", err.c_str());
+    const int Lt = ctx->hp.n_text_layer;
+    std::vector<uint8_t> stage;
+    struct Off { int qtype; size_t qn, side; };
+    // the planes of `names` one behind the other (a [sum rows][K] matrix); qtype 0 unless all share one block format
+    auto add = [&](std::initializer_list<std::string> names) {
+        Off o{0, 0, 0};
+        int64_t nblocks = 0;
+        int t = -1;
+        for (const std::string &nm : names) {
+            const HostTensor &ht = pm.tensors.at(nm);
+            if (!ht.qtype || ht.qraw.empty() || (t >= 0 && ht.qtype != t)) return o;
+            t = ht.qtype;
+            nblocks += ht.nel() / 32;
+        }
+        const size_t QB = (size_t)qplane_qbytes(t), SW = (size_t)qplane_side_words(t);
+        o.qtype = t;
+        o.qn = (size_t)up((int64_t)stage.size(), 256);
+        o.side = (size_t)up((int64_t)(o.qn + nblocks * QB), 256);
+        stage.resize(o.side + nblocks * SW * 4, 0);
+        int64_t b0 = 0;
+        for (const std::string &nm : names) {
+            const HostTensor &ht = pm.tensors.at(nm);
+            repack_blocks(t, ht.qraw.data(), ht.nel() / 32, stage.data() + o.qn + b0 * QB,
+                          (uint32_t *)(stage.data() + o.side) + b0 * SW);
+            b0 += ht.nel() / 32;
+        }
+        return o;
+    };
+    std::vector<std::array<Off, 6>> lo(Lt);
+    char nm[128];
+    for (int i = 0; i < Lt; ++i) {
+        snprintf(nm, sizeof nm, "decoder.blocks.%d.", i);
+        const std::string p(nm);
+        lo[i] = {add({p + "attn.query.weight", p + "attn.key.weight", p + "attn.value.weight"}),
+                 add({p + "attn.out.weight"}), add({p + "cross_attn.query.weight"}), add({p + "cross_attn.out.weight"}),
+                 add({p + "mlp.0.weight"}), add({p + "mlp.2.weight"})};
+    }
+    const Off te = add({"decoder.token_embedding.weight"});
+    if (stage.empty()) {  // (an f16 / f32 file, or no decoder matrix quantised: nothing changes)
+        ctx->qplanes_built = true;
+        return WMI_OK;
+    }
+    void *planes = nullptr;
+    HIPCHK(ctx, hipMalloc(&planes, stage.size()));
+    ctx->d_qplanes = planes;  // (wmi_free's from here on; a failed upload leaves the planes unbuilt and the next switch-on
+                              // starts over)
+    if (hipMemcpy(planes, stage.data(), stage.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        ctx->d_qplanes = nullptr;
+        (void)hipFree(planes);
+        return set_err(ctx, WMI_E_HIP, "wmi_set_quant_gemm: the upload of the planes failed");
+    }
+    ctx->qplanes_built = true;
+    const uint8_t *base = (const uint8_t *)ctx->d_qplanes;
+    auto Q = [&](const Off &o) {
+        wmi_context::QMat m;
+        if (o.qtype) { m.qtype = o.qtype; m.qn = base + o.qn; m.side = (const uint32_t *)(base + o.side); }
+        return m;
+    };
+    ctx->qdec.resize(Lt);
+    for (int i = 0; i < Lt; ++i)
+        ctx->qdec[i] = {Q(lo[i][0]), Q(lo[i][1]), Q(lo[i][2]), Q(lo[i][3]), Q(lo[i][4]), Q(lo[i][5])};
+    ctx->qte = Q(te);
+    return WMI_OK;
+}
+
 // a timestamp run of np feed steps takes the prefill
 bool prefill_on(const wmi_context *ctx, int np) {
     return ctx->prefill_min >= 2 && np >= ctx->prefill_min && np - 1 <= PF_MAX_KEYS;
@@ -2299,10 +2409,11 @@ int prefill_pass(wmi_context *ctx, PfRecs recs, int feed_stride, bool logits, ui
     at.recs = recs; at.q = ctx->pf_q16; at.out = ctx->pf_att16; at.n = n; at.H = H; at.tctx = tctx; at.T = T;
     for (int l = 0; l < ctx->dec_layers; ++l) {
         const DecLayerDev &d = ctx->dec[l];
+        const wmi_context::QLayer *ql = qlayer_of(ctx, l);
         HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, d.ln1_w, d.ln1_b, ctx->pf_ln16, nullptr));
         GemmArgs g = gemm(ctx->pf_ln16, n, d.wqkv, nullptr, 3 * n);
         g.out32 = ctx->pf_qkv32; g.ldo = 3 * n;
-        HIPCHK(ctx, launch_gemm(s, EPI_F32, g));
+        HIPCHK(ctx, dense_product(ctx, s, EPI_F32, g, ql ? &ql->wqkv : nullptr));
         PfQkvArgs qa{};
         qa.acc = ctx->pf_qkv32; qa.bias = d.bqkv; qa.rowmap = ctx->pf_rowmap; qa.q = ctx->pf_q16;
         qa.k = (kbase ? kbase : ctx->kcache) + (size_t)l * cache_rows * tctx * n;
@@ -2314,31 +2425,31 @@ int prefill_pass(wmi_context *ctx, PfRecs recs, int feed_stride, bool logits, ui
         HIPCHK(ctx, launch_pf_self_attn(s, at));
         g = gemm(ctx->pf_att16, n, d.wo, d.bo, n);
         g.out32 = ctx->pf_x; g.ldo = n;
-        HIPCHK(ctx, launch_gemm(s, EPI_RESID, g));
+        HIPCHK(ctx, dense_product(ctx, s, EPI_RESID, g, ql ? &ql->wo : nullptr));
         HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, d.lnc_w, d.lnc_b, ctx->pf_ln16, nullptr));
         g = gemm(ctx->pf_ln16, n, d.wcq, nullptr, n);
         g.out32 = ctx->pf_qkv32; g.ldo = n;
-        HIPCHK(ctx, launch_gemm(s, EPI_F32, g));
+        HIPCHK(ctx, dense_product(ctx, s, EPI_F32, g, ql ? &ql->wcq : nullptr));
         qa.bias = d.bcq; qa.N = n;  // (the q part alone)
         HIPCHK(ctx, launch_pf_qkv_store(s, qa));
         at.K = ctx->ck + (size_t)l * Bt * T * n; at.V = ctx->cv + (size_t)l * Bt * T * n;
         HIPCHK(ctx, launch_pf_cross_attn(s, at));
         g = gemm(ctx->pf_att16, n, d.wco, d.bco, n);
         g.out32 = ctx->pf_x; g.ldo = n;
-        HIPCHK(ctx, launch_gemm(s, EPI_RESID, g));
+        HIPCHK(ctx, dense_product(ctx, s, EPI_RESID, g, ql ? &ql->wco : nullptr));
         HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, d.ln2_w, d.ln2_b, ctx->pf_ln16, nullptr));
         g = gemm(ctx->pf_ln16, n, d.w0, d.b0, 4 * n);
         g.out16 = ctx->pf_hid16; g.ldo = 4 * n; g.gelu_tab = ctx->gelu_tab; g.gelu_min = gelu_min_of(ctx);
-        HIPCHK(ctx, launch_gemm(s, EPI_GELU16, g));
+        HIPCHK(ctx, dense_product(ctx, s, EPI_GELU16, g, ql ? &ql->w0 : nullptr));
         g = gemm(ctx->pf_hid16, 4 * n, d.w1, d.b1, n);
         g.out32 = ctx->pf_x; g.ldo = n;
-        HIPCHK(ctx, launch_gemm(s, EPI_RESID, g));
+        HIPCHK(ctx, dense_product(ctx, s, EPI_RESID, g, ql ? &ql->w1 : nullptr));
     }
     if (logits) {
         HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, ctx->dln_w, ctx->dln_b, ctx->pf_ln16, nullptr));
         GemmArgs g = gemm(ctx->pf_ln16, n, ctx->te, nullptr, hp.n_vocab);
         g.out32 = ctx->pf_logits; g.ldo = hp.n_vocab;
-        HIPCHK(ctx, launch_gemm(s, EPI_F32, g));
+        HIPCHK(ctx, dense_product(ctx, s, EPI_F32, g, ctx->qgemm ? &ctx->qte : nullptr));
     }
     return WMI_OK;
 }
@@ -3878,10 +3989,11 @@ int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles, boo
     ca.n = n; ca.H = H; ca.T = T; ca.Kb = K; ca.B = B; ca.chunks = chunks; ca.tiles = tiles;
     for (int l = 0; l < ctx->dec_layers; ++l) {
         const DecLayerDev &d = ctx->dec[l];
+        const wmi_context::QLayer *ql = qlayer_of(ctx, l);
         HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, d.ln1_w, d.ln1_b, ctx->pf_ln16, nullptr));
         GemmArgs g = gemm(ctx->pf_ln16, n, d.wqkv, nullptr, 3 * n);
         g.out32 = ctx->pf_qkv32; g.ldo = 3 * n;
-        HIPCHK(ctx, launch_gemm(s, EPI_F32, g));
+        HIPCHK(ctx, dense_product(ctx, s, EPI_F32, g, ql ? &ql->wqkv : nullptr));
         PfQkvArgs qa{};
         qa.acc = ctx->pf_qkv32; qa.bias = d.bqkv; qa.rowmap = ctx->wd_rowmap; qa.q = ctx->pf_q16;
         qa.k = ctx->wd_k + (size_t)l * ctx->wd_rows * tctx * n;
@@ -3892,30 +4004,30 @@ int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles, boo
         HIPCHK(ctx, launch_wd_self_attn(s, sa, M));
         g = gemm(ctx->pf_att16, n, d.wo, d.bo, n);
         g.out32 = ctx->pf_x; g.ldo = n;
-        HIPCHK(ctx, launch_gemm(s, EPI_RESID, g));
+        HIPCHK(ctx, dense_product(ctx, s, EPI_RESID, g, ql ? &ql->wo : nullptr));
         HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, d.lnc_w, d.lnc_b, ctx->pf_ln16, nullptr));
         g = gemm(ctx->pf_ln16, n, d.wcq, nullptr, n);
         g.out32 = ctx->pf_qkv32; g.ldo = n;
-        HIPCHK(ctx, launch_gemm(s, EPI_F32, g));
+        HIPCHK(ctx, dense_product(ctx, s, EPI_F32, g, ql ? &ql->wcq : nullptr));
         qa.bias = d.bcq; qa.N = n;  // (the q part alone)
         HIPCHK(ctx, launch_wd_qkv_store(s, qa));
         ca.K = ctx->ck + (size_t)l * Bt * T * n; ca.V = ctx->cv + (size_t)l * Bt * T * n;
         HIPCHK(ctx, launch_wd_cross_attn(s, ca));
         g = gemm(ctx->pf_att16, n, d.wco, d.bco, n);
         g.out32 = ctx->pf_x; g.ldo = n;
-        HIPCHK(ctx, launch_gemm(s, EPI_RESID, g));
+        HIPCHK(ctx, dense_product(ctx, s, EPI_RESID, g, ql ? &ql->wco : nullptr));
         HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, d.ln2_w, d.ln2_b, ctx->pf_ln16, nullptr));
         g = gemm(ctx->pf_ln16, n, d.w0, d.b0, 4 * n);
         g.out16 = ctx->pf_hid16; g.ldo = 4 * n; g.gelu_tab = ctx->gelu_tab; g.gelu_min = gelu_min_of(ctx);
-        HIPCHK(ctx, launch_gemm(s, EPI_GELU16, g));
+        HIPCHK(ctx, dense_product(ctx, s, EPI_GELU16, g, ql ? &ql->w0 : nullptr));
         g = gemm(ctx->pf_hid16, 4 * n, d.w1, d.b1, n);
         g.out32 = ctx->pf_x; g.ldo = n;
-        HIPCHK(ctx, launch_gemm(s, EPI_RESID, g));
+        HIPCHK(ctx, dense_product(ctx, s, EPI_RESID, g, ql ? &ql->w1 : nullptr));
     }
     HIPCHK(ctx, launch_layernorm(s, ctx->pf_x, M, n, ctx->dln_w, ctx->dln_b, ctx->pf_ln16, nullptr));
     GemmArgs g = gemm(ctx->pf_ln16, n, ctx->te, nullptr, hp.n_vocab);
     g.out32 = ctx->wd_logits; g.ldo = hp.n_vocab;
-    HIPCHK(ctx, launch_gemm(s, EPI_F32, g));
+    HIPCHK(ctx, dense_product(ctx, s, EPI_F32, g, ctx->qgemm ? &ctx->qte : nullptr));
     WdBeamArgs ba{};
     ba.tb = ctx->wd_tb; ba.logits = ctx->wd_logits; ba.V = hp.n_vocab; ba.K = K; ba.B = B; ba.eot = ctx->sp.eot; ba.tctx = tctx;
     ba.beg = ctx->sp.beg; ba.sot = ctx->sp.sot; ba.solm = ctx->sp.solm; ba.not_ = ctx->sp.not_;
@@ -4030,18 +4142,23 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
             if (!graph) {
                 if (ctx->graphs.size() >= 32) ctx->clear_graphs();
                 HIPCHK(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+                const int64_t ql0 = ctx->qgemm_launches;
                 rc = enqueue_wide_step(ctx, B, K, chunks, tiles, ruled);
+                const int ql = (int)(ctx->qgemm_launches - ql0);  // (recorded, not launched: every replay counts them)
+                ctx->qgemm_launches = ql0;
                 hipGraph_t gr = nullptr;
                 hipError_t ce = hipStreamEndCapture(s, &gr);
                 if (rc) { if (gr) (void)hipGraphDestroy(gr); return rc; }
                 HIPCHK(ctx, ce);
                 wmi_context::Graph g;
                 g.graph = gr;
+                g.qlaunches = ql;
                 hipError_t ie = hipGraphInstantiate(&g.exec, gr, nullptr, nullptr, 0);
                 if (ie != hipSuccess) { (void)hipGraphDestroy(gr); HIPCHK(ctx, ie); }
                 graph = &ctx->graphs.emplace(key, g).first->second;
             }
             HIPCHK(ctx, hipGraphLaunch(graph->exec, s));
+            ctx->qgemm_launches += graph->qlaunches;
         }
         done += chunk;
         if (done >= max_tokens) break;
@@ -4126,6 +4243,7 @@ static int wmi_init_from_file_impl(const char *path, int device, int max_clips, 
     std::unique_ptr<wmi_context> ctx(new wmi_context());
     ctx->device = device;
     ctx->max_clips = max_clips;
+    ctx->model_path = path;
     ctx->hp = pm.hp;
     ctx->wf32 = pm.hp.f16 % 1000 == 0;
     init_specials(pm.hp.n_vocab, ctx->sp);
@@ -4168,6 +4286,8 @@ static int wmi_init_from_file_impl(const char *path, int device, int max_clips, 
     if (const char *c = getenv("WMI_EARLY_OPERANDS")) ctx->early_ops = atoi(c) != 0;
     if (const char *c = getenv("WMI_A_OFF_B")) ctx->a_off_b = atoi(c) != 0;
     if (const char *c = getenv("WMI_SPLIT_ROWS")) ctx->split_rows = atoi(c);
+    ctx->qgemm_max_rows = QGEMM_MAX_ROWS;
+    if (const char *c = getenv("WMI_QGEMM_MAX_ROWS")) ctx->qgemm_max_rows = std::max(0, atoi(c));
     if (const char *c = getenv("WMI_AUDIO_CHUNK")) ctx->au_chunk = std::max(1ll, std::min(atoll(c), AUDIO_CHUNK_MAX));
     ctx->dec_layers = ctx->hp.n_text_layer;
     if (const char *c = getenv("WMI_DEC_LAYERS")) ctx->dec_layers = std::max(1, std::min(atoi(c), ctx->hp.n_text_layer));
@@ -4251,6 +4371,7 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->d_samp_rows) (void)hipFree(ctx->d_samp_rows);
     if (ctx->pf_x) (void)hipFree(ctx->pf_x);
     if (ctx->pf_logits) (void)hipFree(ctx->pf_logits);
+    if (ctx->d_qplanes) (void)hipFree(ctx->d_qplanes);
     for (void *p : {(void *)ctx->wd_k, (void *)ctx->wd_v, ctx->wd_tab, (void *)ctx->wd_logits, (void *)ctx->wd_part,
                     (void *)ctx->wd_lgall})
         if (p) (void)hipFree(p);
@@ -5794,6 +5915,11 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
             src = which == 40 ? ctx->wd_tb.hist_parent : ctx->wd_tb.hist_tok;
             have = (size_t)DEC_ROWS * ctx->hp.n_text_ctx * BEAM_MAX * 4;
             break;
+        case 42: {  // host, int64: launch_gemm_q launches since the context was created
+            const int64_t v = ctx->qgemm_launches;
+            memcpy(out, &v, std::min(sizeof v, bytes));
+            return WMI_OK;
+        }
         case 11: {  // host: decodes re-run on the kernel chain after a persistent exchange timeout
             const int32_t v = ctx->n_fallbacks;
             memcpy(out, &v, std::min(sizeof v, bytes));
@@ -5985,6 +6111,47 @@ int wmi_set_batch_beam(wmi_context *ctx, int enable) {
     if (enable != 0 && enable != 1) return set_err(ctx, WMI_E_INVALID_ARG, "enable %d is neither 0 nor 1", enable);
     ctx->batch_beam = enable != 0;
     return WMI_OK;
+}
+
+static int wmi_set_quant_gemm_impl(wmi_context *ctx, int enable) {
+    if (enable != 0 && enable != 1) return set_err(ctx, WMI_E_INVALID_ARG, "enable %d is neither 0 nor 1", enable);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (enable && !ctx->qplanes_built && !ctx->wf32) {
+        const int rc = build_qplanes(ctx);
+        if (rc) return rc;
+    }
+    if (ctx->qgemm != (enable != 0)) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->clear_graphs();  // (a wide step's graph holds the products' kernels)
+    }
+    ctx->qgemm = enable != 0;
+    return WMI_OK;
+}
+
+int wmi_set_quant_gemm(wmi_context *ctx, int enable) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    return guarded(ctx, [&] { return wmi_set_quant_gemm_impl(ctx, enable); });
+}
+
+int wmi_dequant_blocks(int type, const void *raw, int64_t nel, uint16_t *out_f16) {
+    return guarded(nullptr, [&]() -> int {
+        if (!raw || !out_f16 || !qblock_bytes(type) || nel <= 0 || nel % 32 != 0 || nel > (int64_t)1 << 31)
+            return set_err(nullptr, WMI_E_INVALID_ARG, "wmi_dequant_blocks: type %d, %lld elements", type, (long long)nel);
+        const int64_t nblocks = nel / 32;
+        const size_t qb = (size_t)up(nblocks * qplane_qbytes(type), 256), sb = (size_t)nblocks * qplane_side_words(type) * 4;
+        std::vector<uint8_t> planes(qb + sb, 0);
+        repack_blocks(type, (const uint8_t *)raw, nblocks, planes.data(), (uint32_t *)(planes.data() + qb));
+        uint8_t *d = nullptr;
+        const size_t ob = (size_t)up((int64_t)(qb + sb), 256);
+        if (hipMalloc(&d, ob + (size_t)nel * 2) != hipSuccess)
+            return set_err(nullptr, WMI_E_HIP, "wmi_dequant_blocks: no device memory");
+        hipError_t e = hipMemcpy(d, planes.data(), planes.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = launch_dequant_q(nullptr, type, d, (const uint32_t *)(d + qb), nblocks, (uint16_t *)(d + ob));
+        if (e == hipSuccess) e = hipMemcpy(out_f16, d + ob, (size_t)nel * 2, hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        if (e != hipSuccess) return set_err(nullptr, WMI_E_HIP, "wmi_dequant_blocks: %s", hipGetErrorString(e));
+        return WMI_OK;
+    });
 }
 
 int wmi_decode_timestamps_beam_rows(wmi_context *ctx, int beam_size, const int32_t *prompts, int prompt_stride,

@@ -157,6 +157,35 @@ void dequant_f16(int t, const uint8_t *src, int64_t nel, uint16_t *dst) {
     }
 }
 
+// The planes of the quantised-weight GEMM (wmi_gemm_q.hip): block i's quants at qn + i * QB in natural k order
+// (nibble byte j = weights 2j, 2j + 1; q8_0: its 32 bytes), its side record at side + i * SIDE: {d | m << 16}
+// (m = +0 where the format has none), for q5_x {fifth bits (bit j = weight j), d | m << 16}
+int qplane_qbytes(int t) { return t == 8 ? 32 : qblock_bytes(t) ? 16 : 0; }
+int qplane_side_words(int t) { return t == 6 || t == 7 ? 2 : qblock_bytes(t) ? 1 : 0; }
+void repack_blocks(int t, const uint8_t *src, int64_t nblocks, uint8_t *qn, uint32_t *side) {
+    const int bs = qblock_bytes(t), QB = qplane_qbytes(t), SIDE = qplane_side_words(t);
+    const bool has_m = t == 3 || t == 7, has_h = t == 6 || t == 7;
+    for (int64_t i = 0; i < nblocks; ++i) {
+        const uint8_t *b = src + i * bs;
+        uint16_t d, m = 0;
+        memcpy(&d, b, 2);
+        if (has_m) memcpy(&m, b + 2, 2);
+        const uint8_t *qs = b + 2 + (has_m ? 2 : 0) + (has_h ? 4 : 0);
+        uint8_t *q = qn + i * QB;
+        if (t == 8) {
+            memcpy(q, qs, 32);
+        } else {
+            // the file's byte j holds weights j and j + 16
+            for (int j = 0; j < 8; ++j) {
+                q[j] = (uint8_t)((qs[2 * j] & 15) | ((qs[2 * j + 1] & 15) << 4));
+                q[j + 8] = (uint8_t)((qs[2 * j] >> 4) | ((qs[2 * j + 1] >> 4) << 4));
+            }
+        }
+        if (has_h) memcpy(&side[i * SIDE], b + 2 + (has_m ? 2 : 0), 4);  // (bit j = weight j in the file as well)
+        side[i * SIDE + SIDE - 1] = (uint32_t)d | ((uint32_t)m << 16);
+    }
+}
+
 // The model shapes the kernels implement; anything else is WMI_E_UNSUPPORTED.
 // Checked right after the header is parsed (before tensors are read and the
 // device is touched) and again by run_encode.
@@ -174,7 +203,7 @@ int check_shape(const wmi_hparams &hp, std::string &err) {
     return WMI_E_UNSUPPORTED;
 }
 
-int parse_file(const char *path, ParsedModel &pm, std::string &err) {
+int parse_file(const char *path, ParsedModel &pm, std::string &err, bool decoder_blocks) {
     FILE *f = fopen(path, "rb");
     if (!f) { err = std::string("Unexpected IO: cannot open '") + path + "'"; return WMI_E_IO; }
     std::unique_ptr<FILE, int (*)(FILE *)> guard(f, fclose);
@@ -290,7 +319,7 @@ int parse_file(const char *path, ParsedModel &pm, std::string &err) {
         t.dtype = kv.second.dtype;
         t.n_dims = kv.second.n_dims;
         for (int i = 0; i < 3; ++i) t.ne[i] = kv.second.ne[i];
-        t.data.assign((size_t)t.nel() * (t.dtype ? 2 : 4), 0);
+        if (!decoder_blocks) t.data.assign((size_t)t.nel() * (t.dtype ? 2 : 4), 0);
         pm.tensors[kv.first] = std::move(t);
     }
     // record loop (main.rs:1384-1475): until fewer than 12 bytes remain
@@ -339,6 +368,17 @@ int parse_file(const char *path, ParsedModel &pm, std::string &err) {
             }
         const int qb = (t.dtype == 1 && t.n_dims == 2 && ne[0] % 32 == 0) ? qblock_bytes(ftype) : 0;
         const int64_t file_bytes = qb ? nel / 32 * qb : nel * (ftype == 0 ? 4 : 2);
+        if (decoder_blocks) {  // the decoder's quantised matrices as read; every other record is stepped over
+            t.qtype = qb ? ftype : 0;
+            if (qb && name.compare(0, 8, "decoder.") == 0) {
+                t.qraw.resize((size_t)file_bytes);
+                if (!rd(t.qraw.data(), t.qraw.size())) { err = "Unexpected IO: short read (tensor data)"; return WMI_E_IO; }
+            } else if (fseek(f, (long)file_bytes, SEEK_CUR)) {
+                err = "Unexpected IO: seek (tensor data)";
+                return WMI_E_IO;
+            }
+            continue;
+        }
         if (!qb && file_bytes != (int64_t)t.data.size()) {
             snprintf(b, sizeof b, "tensor %s has wrong bytes in model file, got:%lld, expected:%lld", name.c_str(),
                      (long long)t.data.size(), (long long)file_bytes);

@@ -34,7 +34,7 @@ void build_tables(std::vector<uint16_t> &gelu, std::vector<uint16_t> &expt);
 struct HostTensor {
     int dtype = 0;  // 0 f32, 1 f16 (quantised matrices are dequantised to f16)
     int qtype = 0;  // ggml type of a quantised matrix in the file (7 = q5_1), else 0
-    std::vector<uint8_t> qraw;  // its blocks as read (q5_1 only: the decoder GEMVs read them)
+    std::vector<uint8_t> qraw;  // its blocks as read (q5_1: the decoder GEMVs read them; every format under decoder_blocks)
     int n_dims = 0;
     int64_t ne[3] = {1, 1, 1};
     std::vector<uint8_t> data;
@@ -60,7 +60,13 @@ struct ParsedModel {
 int qblock_bytes(int t);
 void dequant_f16(int t, const uint8_t *src, int64_t nel, uint16_t *dst);
 int check_shape(const wmi_hparams &hp, std::string &err);
-int parse_file(const char *path, ParsedModel &pm, std::string &err);
+// decoder_blocks: nothing but the blocks of the decoder's quantised matrices is read (qtype and qraw; no tensor holds
+// data and nothing is dequantised): wmi_set_quant_gemm reads the context's file again
+int parse_file(const char *path, ParsedModel &pm, std::string &err, bool decoder_blocks = false);
+// the aligned planes of the quantised-weight GEMM: bytes of a block's quants, words of its side record, the repack
+int qplane_qbytes(int t);
+int qplane_side_words(int t);
+void repack_blocks(int t, const uint8_t *src, int64_t nblocks, uint8_t *qn, uint32_t *side);
 void init_specials(int32_t n_vocab, wmi_special_tokens &sp);
 int read_wav(const char *path, int16_t *samples, size_t cap, size_t *n_samples, int32_t *sample_rate, int32_t *channels,
              std::string &err);

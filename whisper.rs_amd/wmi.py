@@ -71,7 +71,7 @@ EXPORTS = (
     "wmi_set_decode_rules", "wmi_non_speech_tokens", "wmi_decode_timestamps_ruled", "wmi_set_initial_prompt",
     "wmi_set_rules_beam", "wmi_decode_timestamps_ruled_beam",
     "wmi_set_best_of", "wmi_decode_timestamps_best_of", "wmi_best_of_key", "wmi_get_window_candidate",
-    "wmi_set_prefill", "wmi_prefill_logits",
+    "wmi_set_prefill", "wmi_prefill_logits", "wmi_set_quant_gemm", "wmi_dequant_blocks",
     "wmi_set_batch_beam", "wmi_decode_timestamps_beam_rows", "wmi_decode_timestamps_ruled_beam_rows",
     "wmi_is_non_speech_token", "wmi_set_token_timestamps", "wmi_token_times",
     "wmi_set_dtw", "wmi_align_tokens", "wmi_dtw_path", "wmi_dtw_path_host", "wmi_get_segment_dtw_of",
@@ -245,6 +245,9 @@ def lib():
         if hasattr(L, "wmi_set_prefill"):  # (as above: an older build has no prompt prefill)
             L.wmi_set_prefill.argtypes = [vp, C.c_int]
             L.wmi_prefill_logits.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+        if hasattr(L, "wmi_set_quant_gemm"):  # (as above: an older build has no quantised-weight GEMM)
+            L.wmi_set_quant_gemm.argtypes = [vp, C.c_int]
+            L.wmi_dequant_blocks.argtypes = [C.c_int, vp, C.c_int64, vp]
         if hasattr(L, "wmi_set_batch_beam"):  # (as above: an older build has no beam search in the batch)
             L.wmi_set_batch_beam.argtypes = [vp, C.c_int]
             L.wmi_decode_timestamps_beam_rows.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
@@ -1079,6 +1082,15 @@ class WhisperContext:
         _raise(lib().wmi_prefill_logits(self._h, clip, _ptr(tokens), tokens.size, _ptr(out)), self._h)
         return out
 
+    def set_quant_gemm(self, enable: bool) -> None:
+        """The dense products of the prefill pass and the wide beam step read the file's quantised blocks
+        (wmi_set_quant_gemm; off, the default: their f16 copies)."""
+        _raise(lib().wmi_set_quant_gemm(self._h, int(enable)), self._h)
+
+    def quant_gemm_launches(self) -> int:
+        """Debug read 42: launches of the quantised-weight GEMM since the context was created."""
+        return int(np.frombuffer(self.debug_read(42, 8), np.int64)[0])
+
     def prefill_counts(self):
         """Debug read 37: prefill passes since set_prefill, rows and tokens of the last pass, decoder steps saved."""
         return [int(v) for v in np.frombuffer(self.debug_read(37, 32), np.int64)]
@@ -1268,3 +1280,12 @@ def best_of_key(seed: int, n: int, c: int) -> int:
     if rc:
         _raise(rc, None)
     return k.value
+
+
+def dequant_blocks(qtype: int, raw: bytes, nel: int) -> np.ndarray:
+    """nel / 32 raw ggml blocks of type qtype expanded on the device by the quantised-weight GEMM's own
+    dequantisation (wmi_dequant_blocks): the f16 bits as uint16 [nel]."""
+    buf = np.frombuffer(raw, np.uint8).copy()
+    out = np.zeros(nel, np.uint16)
+    _raise(lib().wmi_dequant_blocks(int(qtype), _ptr(buf), nel, _ptr(out)), None)
+    return out
