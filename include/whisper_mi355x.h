@@ -365,6 +365,29 @@ int wmi_decode_timestamps_ruled_beam_rows(wmi_context *ctx, int beam_size, const
  * call launches what it launched before.  Neither 0 nor 1:
  * WMI_E_INVALID_ARG.  Holds until changed. */
 int wmi_set_batch_beam(wmi_context *ctx, int enable);
+/* Wide rounds: rows in [1, 64] puts the batch on the wide step at every beam
+ * size.  Every round of wmi_transcribe_batch / wmi_transcribe_audio_batch,
+ * with and without wmi_set_batch_context, then holds up to
+ * min(max(1, rows / beam size), max_clips) recordings and decodes as one
+ * round of beam windows of K = beam size hypotheses; at beam size 1 the
+ * window is the K = 1 beam window, which yields wmi_decode_timestamps' ids
+ * and tids, and under the decoding rules the ruled sampler's choice at
+ * temperature 0.  wmi_decode_timestamps_beam_rows and its ruled twin run
+ * rounds of up to max(1, rows / K) clips in place of eight.  Recording c
+ * yields the segments wmi_transcribe gives for it alone under the same
+ * settings, up to the order of the floating-point sums, however full its
+ * round is.  A round of one hypothesis a recording runs a cross-attention of
+ * its own (k_wd_cross_attn1: one query a recording and head, keys and values
+ * from global memory to registers); rounds of two and more keep the wide
+ * step's.  A round of more than eight recordings takes a prompt prefill pass
+ * per eight.  With the option on the batch calls are WMI_E_UNSUPPORTED,
+ * checked at the call, for an f32 file, with the decoding rules at a beam
+ * size above 1 unless wmi_set_rules_beam is set, and with the fallback on
+ * (with it best_of: the wide step has no sampled rows); a beam size above 1
+ * still needs wmi_set_batch_beam.  rows 0 (default): off, every call launches
+ * what it launched before.  Outside [0, 64]: WMI_E_INVALID_ARG.  Holds until
+ * changed.  Nothing is claimed for calls under wmi_set_chunking. */
+int wmi_set_wide_rounds(wmi_context *ctx, int rows);
 
 /* ---- temperature fallback, quality thresholds, no-speech ---------------- */
 

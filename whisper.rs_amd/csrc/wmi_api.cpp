@@ -189,11 +189,16 @@ struct wmi_context {
     float *wd_logits = nullptr, *wd_part = nullptr, *wd_lgall = nullptr;
     size_t wd_part_cap = 0, wd_lgall_cap = 0;
     int wd_lg_steps = 0;
-    int32_t wd_last[3 + DEC_ROWS] = {};  // the last wide run's B, K, steps and p_c[8] (debug read 38)
+    int32_t wd_last[3 + WD_ROWS] = {};  // the last wide run's B, K, steps and p_c[B] (debug read 38)
+    // wide rounds (wmi_set_wide_rounds; wmi_wide_rows.hip): rows a round of the batch holds on the wide step (0: off).
+    // The table's blocks and the rule block hold wd_tab_recs / wd_rt_recs recordings: 8 until a round asks for more
+    int wide_rows = 0;
+    int wd_tab_recs = 0, wd_rt_recs = 0;
     // the wide step under the decoding rules (wmi_wide_rules.hip): the rule block, an allocation of its own made with
-    // the first ruled wide window: the hypotheses' histories [8][8], then the parts [8][8][16]
+    // the first ruled wide window: the hypotheses' histories [recs][8], then the parts [recs][8][16]
     WdRuleTable wd_rt{};
-    // batched transcription: source recording [8], then mel offset [8] of each encoder slot, then (chunked calls) its end [8]
+    // batched transcription: source recording, then mel offset of each encoder slot, then (chunked calls) its end:
+    // three columns of 8, of 64 under wide rounds
     int32_t *d_win = nullptr;
     int32_t win_host[3 * DEC_ROWS] = {};  // host copy of the last d_win upload (debug read 22: its first two columns)
     int win_slots = 0;                    // and its slot count (0: no batched round yet)
@@ -2382,7 +2387,7 @@ bool prefill_on(const wmi_context *ctx, int np) {
 // and the vocabulary product follow, into pf_logits [M][n_vocab].
 // kbase / vbase: the cache the pass writes, [L][cache_rows][tctx][n] (null: the context's 8-row caches).
 int prefill_pass(wmi_context *ctx, PfRecs recs, int feed_stride, bool logits, uint16_t *kbase = nullptr,
-                 uint16_t *vbase = nullptr, int cache_rows = DEC_ROWS) {
+                 uint16_t *vbase = nullptr, int cache_rows = DEC_ROWS, const int32_t *feed = nullptr) {
     const wmi_hparams &hp = ctx->hp;
     const int n = hp.n_text_state, H = hp.n_text_head, T = ctx->enc_T, Bt = ctx->enc_clips, tctx = hp.n_text_ctx;
     int M = 0;
@@ -2397,7 +2402,7 @@ int prefill_pass(wmi_context *ctx, PfRecs recs, int feed_stride, bool logits, ui
     if (rc) return rc;
     hipStream_t s = ctx->stream;
     const float qs = powf((float)n / (float)H, -0.25f);
-    HIPCHK(ctx, launch_pf_embed(s, recs, ctx->te, ctx->d_pe, ctx->dfeed, feed_stride, n, hp.n_vocab, tctx, ctx->pf_x,
+    HIPCHK(ctx, launch_pf_embed(s, recs, ctx->te, ctx->d_pe, feed ? feed : ctx->dfeed, feed_stride, n, hp.n_vocab, tctx, ctx->pf_x,
                                 ctx->pf_rowmap));
     auto gemm = [&](const uint16_t *A, int K, const uint16_t *W, const float *bias, int N) {
         GemmArgs g{};
@@ -3133,6 +3138,7 @@ int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &p
                        std::vector<TsRec> *out, double *score, float *p_nosp = nullptr, bool ruled = false);
 int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector<std::vector<int32_t>> &prompts, int max_tokens,
                        std::vector<std::vector<TsRec>> *out, std::vector<double> *scores, bool ruled);
+int wide_round_clips(const wmi_context *ctx, int K);
 
 // after attempt 0: probably silence (OpenAI's no_speech_threshold rule)
 bool fb_silence(const wmi_context *ctx, float p_nosp, const FbAttempt &att) {
@@ -3200,8 +3206,8 @@ int tr_resolve_languages(wmi_context *ctx, TrRun &tr, const std::vector<int> &ro
     const int B = (int)rows.size();
     bool detect = false;
     for (int r : rows) detect = detect || (tr.recs[r].lang == WMI_LANG_AUTO && tr.recs[r].chunk == 0);
-    int32_t det[DEC_ROWS] = {};
-    float p[DEC_ROWS] = {};
+    int32_t det[WD_ROWS] = {};  // (a round holds up to 8 rows, under wide rounds up to 64)
+    float p[WD_ROWS] = {};
     if (detect) {
         int rc = run_lang_detect_sync(ctx);
         if (rc) return rc;
@@ -3264,9 +3270,12 @@ int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows,
     const bool fb = !tr.temps.empty();
     out->assign((size_t)B, {});
     for (int b = 0; b < B; ++b) (*out)[b].T = fb ? tr.temps[tr.recs[rows[b]].att] : 0.0f;
-    if (ctx->beam_size > 1 && (*out)[0].T == 0.0f) {
-        if (B != 1) {
-            if (!ctx->batch_beam) return set_err(ctx, WMI_E_UNSUPPORTED, "a beam window decodes one recording (%d rows)", B);
+    // (wmi_set_wide_rounds: every round of a batch call, `lens` given, is a round of beam windows on the wide step,
+    // the greedy window the K = 1 beam window; the entry points have refused the fallback)
+    const bool wide = lens && ctx->wide_rows > 0;
+    if ((ctx->beam_size > 1 || wide) && (*out)[0].T == 0.0f) {
+        if (B != 1 || wide) {
+            if (!ctx->batch_beam && !wide) return set_err(ctx, WMI_E_UNSUPPORTED, "a beam window decodes one recording (%d rows)", B);
             // (wmi_set_batch_beam: every row's beam window on the wide step, under the rules the ruled one; the entry
             // points have refused rules without wmi_set_rules_beam, the fallback and f32 files)
             std::vector<std::vector<int32_t>> prompts((size_t)B);
@@ -3591,7 +3600,11 @@ void ck_merge(wmi_context *ctx, int R, const std::vector<TrChunk> &chunks) {
 int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
     const int R = ctx->n_clips;
     const bool chunked = ctx->ck_par.enable != 0;
-    if (!ctx->d_win) HIPCHK(ctx, hipMalloc(&ctx->d_win, 3 * DEC_ROWS * 4));
+    if (!ctx->d_win) HIPCHK(ctx, hipMalloc(&ctx->d_win, 3 * WD_ROWS * 4));
+    // (wmi_set_wide_rounds: a round holds floor(rows / beam size) recordings on the wide step, and the columns of
+    // d_win are that long)
+    const bool wide = ctx->wide_rows > 0;
+    const int WS = wide ? WD_ROWS : DEC_ROWS;
     std::vector<TrChunk> chunks;
     if (chunked) {
         int rc = ck_build(ctx, R, &chunks);
@@ -3604,7 +3617,8 @@ int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
         ctx->lang_p[r] = -1.0f;
     }
     const int n_recs = (int)tr.recs.size();
-    const size_t max_rows = chunked ? (size_t)std::min(DEC_ROWS, ctx->max_clips) : (size_t)DEC_ROWS;
+    const int round = wide ? wide_round_clips(ctx, ctx->beam_size) : DEC_ROWS;
+    const size_t max_rows = chunked || wide ? (size_t)std::min(round, ctx->max_clips) : (size_t)DEC_ROWS;
     std::vector<int> rows;  // recording (chunk) of each decoder row
     int next = 0;
     for (;;) {
@@ -3616,16 +3630,17 @@ int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
             if (tr.recs[next].seek < tr.recs[next].n_len) rows.push_back(next);
         if (rows.empty()) break;
         const int B = (int)rows.size();
-        int32_t win[3 * DEC_ROWS] = {};
+        int32_t win[3 * WD_ROWS] = {};
         for (int b = 0; b < B; ++b) {
             win[b] = tr.recs[rows[b]].clip;
-            win[DEC_ROWS + b] = (int32_t)tr.recs[rows[b]].seek;
-            win[2 * DEC_ROWS + b] = (int32_t)tr.recs[rows[b]].n_len;
+            win[WS + b] = (int32_t)tr.recs[rows[b]].seek;
+            win[2 * WS + b] = (int32_t)tr.recs[rows[b]].n_len;
         }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_win, win, sizeof win, hipMemcpyHostToDevice, ctx->stream));
-        memcpy(ctx->win_host, win, sizeof win);
-        ctx->win_slots = B;
-        int rc = run_encode(ctx, 0, B, ctx->d_win, ctx->d_win + DEC_ROWS, chunked ? ctx->d_win + 2 * DEC_ROWS : nullptr);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_win, win, (size_t)3 * WS * 4, hipMemcpyHostToDevice, ctx->stream));
+        for (int col = 0; col < 3; ++col)  // (the host copy keeps its columns of 8: a wide round's first 8 slots)
+            memcpy(ctx->win_host + col * DEC_ROWS, win + col * WS, DEC_ROWS * 4);
+        ctx->win_slots = std::min(B, DEC_ROWS);
+        int rc = run_encode(ctx, 0, B, ctx->d_win, ctx->d_win + WS, chunked ? ctx->d_win + 2 * WS : nullptr);
         if (rc) return rc;
         rc = tr_resolve_languages(ctx, tr, rows);
         if (rc) return rc;
@@ -3642,7 +3657,7 @@ int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
         rc = tr_decode_attempt(ctx, tr, rows, feed, np, &att, &lens);
         if (rc) return rc;
         ++ctx->trb_count[0];
-        for (int b = 0; b < B; ++b)
+        for (int b = 0; b < std::min(B, DEC_ROWS); ++b)  // (a wide round right-aligns no row)
             if (ctx->ts_lo[2 + b] > 0) { ++ctx->trb_count[1]; break; }
         ctx->trb_count[2] += ctx->ts_lo[1];
         for (int v : lens) ctx->trb_count[3] += v;
@@ -3897,6 +3912,11 @@ int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &p
 }
 
 // ---- beam search in the batch (wmi_wide.hip; DESIGN.md "Beam search in the batch") ----
+// recordings a round of the wide step holds at K hypotheses each: eight, under wmi_set_wide_rounds floor(rows / K)
+int wide_round_clips(const wmi_context *ctx, int K) {
+    return ctx->wide_rows > 0 ? std::max(1, ctx->wide_rows / std::max(K, 1)) : DEC_ROWS;
+}
+
 // what the wide step asks of the model (checked at the call)
 int wide_unsupported(wmi_context *ctx) {
     if (ctx->wf32)
@@ -3924,16 +3944,25 @@ int ensure_wide_buffers(wmi_context *ctx, int R, int B, int K, int chunks, int l
         ctx->wd_rows = R;
         ctx->clear_graphs();
     }
-    if (!ctx->wd_tab) {
+    if (B > ctx->wd_tab_recs) {  // (the table's blocks hold NB recordings: 8, or a wide round's)
+        if (ctx->wd_tab) {
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            HIPCHK(ctx, hipFree(ctx->wd_tab));
+            ctx->wd_tab = nullptr;
+            ctx->wd_tab_recs = 0;
+            ctx->clear_graphs();
+        }
+        const size_t NB = (size_t)std::max(B, DEC_ROWS);
         size_t off = 0;
         auto take = [&](size_t nb) { const size_t o = off; off += (size_t)up((int64_t)nb, 16); return o; };
-        const size_t o_recs = take(DEC_ROWS * sizeof(WdRec)), o_bs = take(DEC_ROWS * sizeof(BeamState));
-        const size_t o_src = take((size_t)DEC_ROWS * BEAM_MAX * tctx * 4);
-        const size_t o_par = take((size_t)DEC_ROWS * tctx * BEAM_MAX * 4), o_tok = take((size_t)DEC_ROWS * tctx * BEAM_MAX * 4);
-        const size_t o_rec = take((size_t)DEC_ROWS * (tctx + 1) * BEAM_MAX * sizeof(TsRec));
-        const size_t o_parts = take((size_t)DEC_ROWS * BEAM_MAX * BEAM_NS * sizeof(TsBeamPart));
+        const size_t o_recs = take(NB * sizeof(WdRec)), o_bs = take(NB * sizeof(BeamState));
+        const size_t o_src = take(NB * BEAM_MAX * tctx * 4);
+        const size_t o_par = take(NB * tctx * BEAM_MAX * 4), o_tok = take(NB * tctx * BEAM_MAX * 4);
+        const size_t o_rec = take(NB * (tctx + 1) * BEAM_MAX * sizeof(TsRec));
+        const size_t o_parts = take(NB * BEAM_MAX * BEAM_NS * sizeof(TsBeamPart));
         const size_t o_map = take(WD_ROWS * 4);
         HIPCHK(ctx, hipMalloc(&ctx->wd_tab, off));
+        ctx->wd_tab_recs = (int)NB;
         HIPCHK(ctx, hipMemset(ctx->wd_tab, 0, off));
         char *p = (char *)ctx->wd_tab;
         ctx->wd_tb.recs = (WdRec *)(p + o_recs); ctx->wd_tb.bs = (BeamState *)(p + o_bs);
@@ -3943,7 +3972,7 @@ int ensure_wide_buffers(wmi_context *ctx, int R, int B, int K, int chunks, int l
         ctx->wd_rowmap = (int32_t *)(p + o_map);
     }
     if (!ctx->wd_logits) HIPCHK(ctx, hipMalloc(&ctx->wd_logits, (size_t)WD_ROWS * V * 4));
-    const size_t part = (size_t)DEC_ROWS * hp.n_text_head * chunks * 16 * WD_PART;
+    const size_t part = (size_t)std::max(B, DEC_ROWS) * hp.n_text_head * chunks * 16 * WD_PART;
     if (part > ctx->wd_part_cap) {
         if (ctx->wd_part) HIPCHK(ctx, hipFree(ctx->wd_part));
         ctx->wd_part = nullptr;
@@ -3968,8 +3997,9 @@ int ensure_wide_buffers(wmi_context *ctx, int R, int B, int K, int chunks, int l
 }
 
 // one wide step of B x K rows: the fixed launch sequence (nothing in it depends on the step); with `ruled` its beam
-// step is the one under the decoding rules (k_wd_rbeam_part / k_wd_rbeam_select)
-int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles, bool ruled) {
+// step is the one under the decoding rules (k_wd_rbeam_part / k_wd_rbeam_select), with `rows1` (K = 1 under
+// wmi_set_wide_rounds) its cross-attention k_wd_cross_attn1
+int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles, bool ruled, bool rows1) {
     const wmi_hparams &hp = ctx->hp;
     const int n = hp.n_text_state, H = hp.n_text_head, T = ctx->enc_T, Bt = ctx->enc_clips, tctx = hp.n_text_ctx, M = B * K;
     hipStream_t s = ctx->stream;
@@ -4012,7 +4042,7 @@ int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles, boo
         qa.bias = d.bcq; qa.N = n;  // (the q part alone)
         HIPCHK(ctx, launch_wd_qkv_store(s, qa));
         ca.K = ctx->ck + (size_t)l * Bt * T * n; ca.V = ctx->cv + (size_t)l * Bt * T * n;
-        HIPCHK(ctx, launch_wd_cross_attn(s, ca));
+        HIPCHK(ctx, rows1 ? launch_wd_cross_attn1(s, ca) : launch_wd_cross_attn(s, ca));
         g = gemm(ctx->pf_att16, n, d.wco, d.bco, n);
         g.out32 = ctx->pf_x; g.ldo = n;
         HIPCHK(ctx, dense_product(ctx, s, EPI_RESID, g, ql ? &ql->wco : nullptr));
@@ -4042,10 +4072,10 @@ int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles, boo
     return WMI_OK;
 }
 
-// One timestamped beam window for each of the B <= 8 encoded clips b0 .. b0 + B - 1, K hypotheses each, on the
+// One timestamped beam window for each of the B <= wide_round_clips encoded clips b0 .. b0 + B - 1, K hypotheses each, on the
 // wide step: clip b0 + c after prompts[c].  Per recording run_ts_beam_window's search, with `ruled` the one under the
 // decoding rules: every hypothesis' history starts empty with the table.  Recordings do not interact, one whose search is done freezes while the others go on.  The prompts' positions 0 .. np_c - 2 go
-// through one prefill pass into wide-cache slot c K, which every hypothesis' history names; the steps follow in
+// through a prefill pass (eight recordings a pass) into wide-cache slot c K, which every hypothesis' history names; the steps follow in
 // chunks of 16 with a look at the done words.  out[c] = the chosen hypothesis' records, scores[c] its score.
 int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector<std::vector<int32_t>> &prompts, int max_tokens,
                        std::vector<std::vector<TsRec>> *out, std::vector<double> *scores, bool ruled) {
@@ -4054,7 +4084,7 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
     if (ruled && (!ctx->rules_on || !ctx->d_rule_m0)) return set_err(ctx, WMI_E_INVALID_ARG, "no decoding rules are enabled");
     if (ctx->enc_T <= 0 || ctx->enc_clips < 1) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
     if (K < 1 || K > BEAM_MAX) return set_err(ctx, WMI_E_INVALID_ARG, "beam size %d outside [1, %d]", K, BEAM_MAX);
-    if (B < 1 || B > DEC_ROWS || (int)prompts.size() != B || b0 < 0 || b0 + B > ctx->enc_clips)
+    if (B < 1 || B > wide_round_clips(ctx, K) || (int)prompts.size() != B || b0 < 0 || b0 + B > ctx->enc_clips)
         return set_err(ctx, WMI_E_INVALID_ARG, "rows [%d, %d) outside the %d encoded clips", b0, b0 + B, ctx->enc_clips);
     int rc = wide_unsupported(ctx);
     if (rc) return rc;
@@ -4068,52 +4098,70 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
         pmax = std::max(pmax, np);
     }
     const int R = B * K;
+    const bool rows1 = ctx->wide_rows > 0 && K == 1;  // (the launch rule: never without the option, never at K >= 2)
     int cus = 256, chunks = 1, tiles = 1;
     HIPCHK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
     wd_cross_split(ctx->enc_T, B, hp.n_text_head, cus, &chunks, &tiles);
     rc = ensure_decode_buffers(ctx, B * pmax, 1);
     if (rc) return rc;
     int pf_rows = R;
-    for (const auto &p : prompts) pf_rows = std::max(pf_rows, (int)p.size() - 1);  // (a lower bound: the pass grows it)
+    for (int c0 = 0; c0 < B; c0 += DEC_ROWS) {  // (the packed rows of each prefill pass: no pass grows the buffers)
+        int rows = 0;
+        for (int c = c0; c < std::min(B, c0 + DEC_ROWS); ++c) rows += (int)prompts[c].size() - 1;
+        pf_rows = std::max(pf_rows, rows);
+    }
     rc = ensure_pf_buffers(ctx, pf_rows, false);
     if (rc) return rc;
     rc = ensure_wide_buffers(ctx, R, B, K, chunks, max_tokens);
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    const size_t rt_hist = (size_t)DEC_ROWS * BEAM_MAX * sizeof(RuleHist);
-    if (ruled && !ctx->wd_rt.hist) {
-        const size_t rt_parts = (size_t)DEC_ROWS * BEAM_MAX * BEAM_NS * sizeof(RBeamPart);
+    if (ruled && B > ctx->wd_rt_recs) {
+        if (ctx->wd_rt.hist) {
+            HIPCHK(ctx, hipStreamSynchronize(s));
+            HIPCHK(ctx, hipFree(ctx->wd_rt.hist));
+            ctx->wd_rt = WdRuleTable{};
+            ctx->wd_rt_recs = 0;
+            ctx->clear_graphs();
+        }
+        const size_t NB = (size_t)std::max(B, DEC_ROWS);
+        const size_t rt_hist = NB * BEAM_MAX * sizeof(RuleHist), rt_parts = NB * BEAM_MAX * BEAM_NS * sizeof(RBeamPart);
         char *p = nullptr;
         HIPCHK(ctx, hipMalloc(&p, rt_hist + rt_parts));
         ctx->wd_rt.hist = (RuleHist *)p;
         ctx->wd_rt.rparts = (RBeamPart *)(p + rt_hist);
         HIPCHK(ctx, hipMemsetAsync(ctx->wd_rt.rparts, 0, rt_parts, s));
+        ctx->wd_rt_recs = (int)NB;
     }
     // the prompts, the table and the prefill
     std::vector<int32_t> feed((size_t)B * pmax, -1);
-    WdRec recs[DEC_ROWS] = {};
-    BeamState bs[DEC_ROWS] = {};
-    PfRecs pf{};
-    pf.n = B;
+    const int NB = std::max(B, DEC_ROWS);  // (a round of up to 8 uploads 8 records, as it always has)
+    std::vector<WdRec> recs((size_t)NB, WdRec{});
+    std::vector<BeamState> bs((size_t)NB, BeamState{});
+    std::vector<PfRecs> pfs((size_t)(B + DEC_ROWS - 1) / DEC_ROWS, PfRecs{});  // a prefill pass holds 8 recordings
     for (int c = 0; c < B; ++c) {
+        PfRecs &pf = pfs[(size_t)c / DEC_ROWS];
+        PfRec &pr = pf.r[pf.n++];
         const int np = (int)prompts[c].size();
         std::copy(prompts[c].begin(), prompts[c].end(), feed.begin() + (size_t)c * pmax);
         recs[c].clip = b0 + c; recs[c].p = np - 1; recs[c].np = np; recs[c].max_tokens = max_tokens;
         recs[c].last_tok = prompts[c].back();
         bs[c].n_active = 1;
-        pf.r[c].slot = c * K; pf.r[c].clip = b0 + c; pf.r[c].lo = 0; pf.r[c].len = np - 1;
+        pr.slot = c * K; pr.clip = b0 + c; pr.lo = 0; pr.len = np - 1;
     }
     ctx->ts_prompt = feed;
     memset(ctx->ts_lo, 0, sizeof ctx->ts_lo);  // (no row is right-aligned: every recording starts at its own position)
     ctx->ts_lo[0] = B;
     ctx->ts_lo[1] = pmax;
     HIPCHK(ctx, hipMemcpyAsync(ctx->dfeed, feed.data(), feed.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->wd_tb.recs, recs, sizeof recs, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->wd_tb.bs, bs, sizeof bs, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemsetAsync(ctx->wd_tb.kv_src, 0, (size_t)DEC_ROWS * BEAM_MAX * tctx * 4, s));  // (the prompt's keys: slot 0)
-    if (ruled) HIPCHK(ctx, hipMemsetAsync(ctx->wd_rt.hist, 0, rt_hist, s));  // (no hypothesis has sampled anything)
-    rc = prefill_pass(ctx, pf, pmax, false, ctx->wd_k, ctx->wd_v, ctx->wd_rows);
-    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->wd_tb.recs, recs.data(), (size_t)NB * sizeof(WdRec), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->wd_tb.bs, bs.data(), (size_t)NB * sizeof(BeamState), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemsetAsync(ctx->wd_tb.kv_src, 0, (size_t)NB * BEAM_MAX * tctx * 4, s));  // (the prompt's keys: slot 0)
+    if (ruled)  // (no hypothesis has sampled anything)
+        HIPCHK(ctx, hipMemsetAsync(ctx->wd_rt.hist, 0, (size_t)NB * BEAM_MAX * sizeof(RuleHist), s));
+    for (size_t i = 0; i < pfs.size(); ++i) {  // (pass i: feed rows 8 i ..)
+        rc = prefill_pass(ctx, pfs[i], pmax, false, ctx->wd_k, ctx->wd_v, ctx->wd_rows, ctx->dfeed + i * DEC_ROWS * pmax);
+        if (rc) return rc;
+    }
     // The steps replay one captured graph.  Its key holds every address and capacity the launches carry (the pf_*
     // buffers are offsets of pf_x by pf_cap, the cache layers of wd_k by wd_rows).  A configuration's very first step
     // is enqueued as it is: the GEMM launchers may set a kernel's LDS attribute at their first launch, which a
@@ -4124,7 +4172,8 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
     int kl = snprintf(key, sizeof key, "wide/%d/%d/%d/%d/%d/%d/%p/%d/%p/%d/%p/%p/%d", B, K, chunks, tiles, ctx->enc_T, ctx->enc_clips,
                       (void *)ctx->pf_x, ctx->pf_cap, (void *)ctx->wd_k, ctx->wd_rows, (void *)ctx->wd_part,
                       (void *)(ctx->d_lgall ? ctx->wd_lgall : nullptr), ctx->d_lgall ? ctx->wd_lg_steps : 0);
-    if (ruled && kl > 0 && kl < (int)sizeof key) snprintf(key + kl, sizeof key - kl, "/ruled/%p", (void *)ctx->wd_rt.hist);
+    if (ruled && kl > 0 && kl < (int)sizeof key) kl += snprintf(key + kl, sizeof key - kl, "/ruled/%p", (void *)ctx->wd_rt.hist);
+    if (rows1 && kl > 0 && kl < (int)sizeof key) snprintf(key + kl, sizeof key - kl, "/rows1");
     wmi_context::Graph *graph = nullptr;
     if (ctx->use_graph) {
         auto it = ctx->graphs.find(key);
@@ -4135,7 +4184,7 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
         const int chunk = std::min(16, max_tokens - done);
         for (int i = 0; i < chunk; ++i, ++steps) {
             if (!ctx->use_graph || (!graph && steps == 0)) {
-                rc = enqueue_wide_step(ctx, B, K, chunks, tiles, ruled);
+                rc = enqueue_wide_step(ctx, B, K, chunks, tiles, ruled, rows1);
                 if (rc) return rc;
                 continue;
             }
@@ -4143,7 +4192,7 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
                 if (ctx->graphs.size() >= 32) ctx->clear_graphs();
                 HIPCHK(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
                 const int64_t ql0 = ctx->qgemm_launches;
-                rc = enqueue_wide_step(ctx, B, K, chunks, tiles, ruled);
+                rc = enqueue_wide_step(ctx, B, K, chunks, tiles, ruled, rows1);
                 const int ql = (int)(ctx->qgemm_launches - ql0);  // (recorded, not launched: every replay counts them)
                 ctx->qgemm_launches = ql0;
                 hipGraph_t gr = nullptr;
@@ -4162,14 +4211,14 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
         }
         done += chunk;
         if (done >= max_tokens) break;
-        HIPCHK(ctx, hipMemcpyAsync(bs, ctx->wd_tb.bs, (size_t)B * sizeof(BeamState), hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(bs.data(), ctx->wd_tb.bs, (size_t)B * sizeof(BeamState), hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipStreamSynchronize(s));
         bool all = true;
         for (int c = 0; c < B; ++c) all = all && bs[c].done != 0;
         if (all) break;
     }
-    HIPCHK(ctx, hipMemcpyAsync(bs, ctx->wd_tb.bs, (size_t)B * sizeof(BeamState), hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(recs, ctx->wd_tb.recs, (size_t)B * sizeof(WdRec), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(bs.data(), ctx->wd_tb.bs, (size_t)B * sizeof(BeamState), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(recs.data(), ctx->wd_tb.recs, (size_t)B * sizeof(WdRec), hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     ctx->last_run_steps = steps;
     memset(ctx->wd_last, 0, sizeof ctx->wd_last);
@@ -4704,7 +4753,21 @@ static int batch_beam_unsupported(wmi_context *ctx) {
     return WMI_OK;
 }
 
-// One beam window per encoded clip on the wide step, in rounds of up to DEC_ROWS clips, clip b after its own prompt;
+// a batched transcription under wmi_set_wide_rounds, at every beam size: what the wide step does not carry
+static int wide_rounds_unsupported(wmi_context *ctx) {
+    if (ctx->wide_rows <= 0) return WMI_OK;
+    int rc = wide_unsupported(ctx);
+    if (rc) return rc;
+    if (ctx->rules_on && ctx->beam_size > 1 && !ctx->rules_beam)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "wide rounds at a beam size above 1 carry the decoding rules only under "
+                       "wmi_set_rules_beam");
+    if (ctx->fb_on)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "wide rounds do not carry the temperature fallback or best_of: the wide step "
+                       "has no sampled rows (wmi_set_fallback(ctx, NULL), or wmi_set_wide_rounds(ctx, 0))");
+    return WMI_OK;
+}
+
+// One beam window per encoded clip on the wide step, in rounds of up to wide_round_clips clips, clip b after its own prompt;
 // `ruled`: wmi_decode_timestamps_ruled_beam_rows, every window under the context's decoding rules
 static int wmi_decode_timestamps_beam_rows_impl(wmi_context *ctx, int beam_size, const int32_t *prompts, int prompt_stride,
                                                 const int32_t *n_prompt, int max_tokens, wmi_token_data *out, int32_t *n_out,
@@ -4725,8 +4788,9 @@ static int wmi_decode_timestamps_beam_rows_impl(wmi_context *ctx, int beam_size,
         if (rc) return rc;
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    for (int b0 = 0; b0 < Bt; b0 += DEC_ROWS) {
-        const int B = std::min(DEC_ROWS, Bt - b0);
+    const int round = wide_round_clips(ctx, beam_size);
+    for (int b0 = 0; b0 < Bt; b0 += round) {
+        const int B = std::min(round, Bt - b0);
         std::vector<std::vector<int32_t>> pr((size_t)B);
         for (int b = 0; b < B; ++b) {
             const int32_t *p = prompts + (size_t)(b0 + b) * prompt_stride;
@@ -4813,6 +4877,7 @@ static int wmi_transcribe_batch_impl(wmi_context *ctx, int n_clips, const float 
         return set_err(ctx, WMI_E_UNSUPPORTED, "wmi_transcribe_batch decodes greedily only: beam size %d is set "
                        "(wmi_set_beam_size(ctx, 1), or wmi_transcribe per recording)", ctx->beam_size);
     if (batch_beam_unsupported(ctx)) return WMI_E_UNSUPPORTED;
+    if (wide_rounds_unsupported(ctx)) return WMI_E_UNSUPPORTED;
     if (best_of_unsupported(ctx, "wmi_transcribe_batch")) return WMI_E_UNSUPPORTED;
     for (int c = 0; c < n_clips; ++c)  // (wmi_set_language / wmi_set_task refuse these; checked where they are used)
         if (ctx->n_lang == 0 && (ctx->lang_set[c] != 0 || ctx->task != WMI_TASK_TRANSCRIBE))
@@ -5470,6 +5535,7 @@ static int wmi_transcribe_audio_batch_impl(wmi_context *ctx, int n_clips, const 
         return set_err(ctx, WMI_E_UNSUPPORTED, "wmi_transcribe_audio_batch decodes greedily only: beam size %d is set "
                        "(wmi_set_beam_size(ctx, 1), or wmi_transcribe_audio per recording)", ctx->beam_size);
     if (batch_beam_unsupported(ctx)) return WMI_E_UNSUPPORTED;
+    if (wide_rounds_unsupported(ctx)) return WMI_E_UNSUPPORTED;
     if (best_of_unsupported(ctx, "wmi_transcribe_audio_batch")) return WMI_E_UNSUPPORTED;
     for (int c = 0; c < n_clips; ++c)
         if (ctx->n_lang == 0 && (ctx->lang_set[c] != 0 || ctx->task != WMI_TASK_TRANSCRIBE))
@@ -5900,7 +5966,7 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
             memcpy(out, v, std::min(sizeof v, bytes));
             return WMI_OK;
         }
-        case 38: {  // host, int32 [11]: the last wide run's recordings B, hypotheses K, steps and each recording's position p_c
+        case 38: {  // host, int32 [3 + 64] (a round of eight: the first 11): the last wide run's recordings B, hypotheses K, steps and each recording's position p_c
             memcpy(out, ctx->wd_last, std::min(sizeof ctx->wd_last, bytes));
             return WMI_OK;
         }
@@ -5913,7 +5979,7 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
         case 41:  // ... and the slots' tokens
             if (!ctx->wd_tab) return WMI_E_INVALID_ARG;
             src = which == 40 ? ctx->wd_tb.hist_parent : ctx->wd_tb.hist_tok;
-            have = (size_t)DEC_ROWS * ctx->hp.n_text_ctx * BEAM_MAX * 4;
+            have = (size_t)ctx->wd_tab_recs * ctx->hp.n_text_ctx * BEAM_MAX * 4;  // (8 recordings, or a wide round's)
             break;
         case 42: {  // host, int64: launch_gemm_q launches since the context was created
             const int64_t v = ctx->qgemm_launches;
@@ -6110,6 +6176,13 @@ int wmi_set_batch_beam(wmi_context *ctx, int enable) {
     if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
     if (enable != 0 && enable != 1) return set_err(ctx, WMI_E_INVALID_ARG, "enable %d is neither 0 nor 1", enable);
     ctx->batch_beam = enable != 0;
+    return WMI_OK;
+}
+
+int wmi_set_wide_rounds(wmi_context *ctx, int rows) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    if (rows < 0 || rows > WD_ROWS) return set_err(ctx, WMI_E_INVALID_ARG, "rows %d outside [0, %d]", rows, WD_ROWS);
+    ctx->wide_rows = rows;  // (a step graph's key names its cross-attention kernel: none is dropped)
     return WMI_OK;
 }
 

@@ -610,6 +610,10 @@ constexpr int WD_PART = 66;
 // key chunks so that B * H * chunks covers `cus` workgroups (every chunk holds a key below T)
 void wd_cross_split(int T, int B, int H, int cus, int *chunks, int *tiles);
 hipError_t launch_wd_cross_attn(hipStream_t s, const WdCrossArgs &a);  // k_wd_cross_attn, then k_wd_cross_combine
+hipError_t launch_wd_cross_combine(hipStream_t s, const WdCrossArgs &a);
+// wmi_wide_rows.hip (wmi_set_wide_rounds): Kb = 1, one query a (recording, head); k_wd_cross_attn1 writes row 0 of a
+// chunk's 16 partial rows, then k_wd_cross_combine
+hipError_t launch_wd_cross_attn1(hipStream_t s, const WdCrossArgs &a);
 struct WdBeamArgs {
     WdTable tb;
     const float *logits;     // [R][V]
@@ -623,8 +627,8 @@ hipError_t launch_wd_logits_capture(hipStream_t s, const WdBeamArgs &a);  // k_w
 // ---- the wide step's beam step under the decoding rules (wmi_wide_rules.hip): wmi_rbeam.hip's step for every
 // recording of the round, every hypothesis' rule history handed on through its recording's parent selection
 struct WdRuleTable {         // device pointers into the rule block, an allocation of its own beside the table's
-    RuleHist *hist;          // [DEC_ROWS][BEAM_MAX] history of the hypothesis in slot s of recording c
-    RBeamPart *rparts;       // [DEC_ROWS][BEAM_MAX][BEAM_NS]
+    RuleHist *hist;          // [B][BEAM_MAX] history of the hypothesis in slot s of recording c
+    RBeamPart *rparts;       // [B][BEAM_MAX][BEAM_NS]
 };
 struct WdRBeamArgs {
     WdBeamArgs w;            // (sot, solm, not_ unused: M0 holds them)

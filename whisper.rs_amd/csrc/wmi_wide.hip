@@ -89,7 +89,7 @@ __global__ __launch_bounds__(64) void k_wd_embed(WdTable tb, int K, const uint16
 
 hipError_t launch_wd_embed(hipStream_t s, const WdTable &tb, int B, int K, const uint16_t *te, const float *pe, int n, int V,
                            int tctx, float *x, int32_t *rowmap) {
-    if (B < 1 || B > DEC_ROWS || K < 1 || K > BEAM_MAX || n % 4) return hipErrorInvalidValue;
+    if (B < 1 || K < 1 || K > BEAM_MAX || B * K > WD_ROWS || n % 4) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_wd_embed, dim3(B * K), dim3(64), 0, s, tb, K, te, pe, n, V, tctx, x, rowmap);
     return hipGetLastError();
 }
@@ -359,12 +359,16 @@ __global__ __launch_bounds__(64) void k_wd_cross_combine(WdCrossArgs a) {
 }
 
 hipError_t launch_wd_cross_attn(hipStream_t s, const WdCrossArgs &a) {
-    if (a.B < 1 || a.B > DEC_ROWS || a.Kb < 1 || a.Kb > BEAM_MAX || a.T < 1 || a.n != a.H * 64 || a.chunks < 1 || a.tiles < 1 ||
+    if (a.B < 1 || a.Kb < 1 || a.Kb > BEAM_MAX || a.B * a.Kb > WD_ROWS || a.T < 1 || a.n != a.H * 64 || a.chunks < 1 || a.tiles < 1 ||
         (int64_t)a.chunks * a.tiles * WD_CK < a.T || (int64_t)(a.chunks - 1) * a.tiles * WD_CK >= a.T)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_wd_cross_attn, dim3(a.chunks, a.H, a.B), dim3(128), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return launch_wd_cross_combine(s, a);
+}
+
+hipError_t launch_wd_cross_combine(hipStream_t s, const WdCrossArgs &a) {
     hipLaunchKernelGGL(k_wd_cross_combine, dim3(a.B * a.Kb, a.H), dim3(64), 0, s, a);
     return hipGetLastError();
 }
@@ -561,7 +565,7 @@ __global__ __launch_bounds__(256) void k_wd_beam_select(WdBeamArgs wa) {
 }
 
 hipError_t launch_wd_beam_step(hipStream_t s, const WdBeamArgs &a) {
-    if (a.K < 1 || a.K > BEAM_MAX || a.B < 1 || a.B > DEC_ROWS || a.tctx > 512 || (a.V + BEAM_NS - 1) / BEAM_NS > 4096 ||
+    if (a.K < 1 || a.K > BEAM_MAX || a.B < 1 || a.B * a.K > WD_ROWS || a.tctx > 512 || (a.V + BEAM_NS - 1) / BEAM_NS > 4096 ||
         a.beg < 1 || a.V < a.beg + 2)
         return hipErrorInvalidValue;
     hipError_t e;
@@ -577,7 +581,7 @@ hipError_t launch_wd_beam_step(hipStream_t s, const WdBeamArgs &a) {
 
 // the capture alone, in front of the ruled pair of wmi_wide_rules.hip
 hipError_t launch_wd_logits_capture(hipStream_t s, const WdBeamArgs &a) {
-    if (!a.lg_all || a.K < 1 || a.K > BEAM_MAX || a.B < 1 || a.B > DEC_ROWS) return hipErrorInvalidValue;
+    if (!a.lg_all || a.K < 1 || a.K > BEAM_MAX || a.B < 1 || a.B * a.K > WD_ROWS) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_wd_logits_capture, dim3(a.B * a.K), dim3(256), 0, s, a);
     return hipGetLastError();
 }

@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256) void k_wd_rbeam_select(WdRBeamArgs ra) {
 hipError_t launch_wd_rbeam_step(hipStream_t s, const WdRBeamArgs &ra) {
     const WdBeamArgs &a = ra.w;
     // (launch_wd_beam_step's conditions and launch_rbeam_step's: 16 splits of at most 4096 ids, the specials below beg)
-    if (a.K < 1 || a.K > BEAM_MAX || a.B < 1 || a.B > DEC_ROWS || a.tctx > 512 || a.V > 65536 ||
+    if (a.K < 1 || a.K > BEAM_MAX || a.B < 1 || a.B * a.K > WD_ROWS || a.tctx > 512 || a.V > 65536 ||
         (a.V + BEAM_NS - 1) / BEAM_NS > 4096 || a.beg < 1 || a.V < a.beg + 2 || a.eot < 0 || a.eot >= a.beg || !ra.m0 ||
         !ra.rt.hist || !ra.rt.rparts)
         return hipErrorInvalidValue;

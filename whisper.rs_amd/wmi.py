@@ -73,6 +73,7 @@ EXPORTS = (
     "wmi_set_best_of", "wmi_decode_timestamps_best_of", "wmi_best_of_key", "wmi_get_window_candidate",
     "wmi_set_prefill", "wmi_prefill_logits", "wmi_set_quant_gemm", "wmi_dequant_blocks",
     "wmi_set_batch_beam", "wmi_decode_timestamps_beam_rows", "wmi_decode_timestamps_ruled_beam_rows",
+    "wmi_set_wide_rounds",
     "wmi_is_non_speech_token", "wmi_set_token_timestamps", "wmi_token_times",
     "wmi_set_dtw", "wmi_align_tokens", "wmi_dtw_path", "wmi_dtw_path_host", "wmi_get_segment_dtw_of",
     "wmi_audio_to_mel_batch", "wmi_stage_audio", "wmi_transcribe_audio", "wmi_transcribe_audio_batch", "wmi_get_pcm",
@@ -251,6 +252,8 @@ def lib():
         if hasattr(L, "wmi_set_batch_beam"):  # (as above: an older build has no beam search in the batch)
             L.wmi_set_batch_beam.argtypes = [vp, C.c_int]
             L.wmi_decode_timestamps_beam_rows.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+        if hasattr(L, "wmi_set_wide_rounds"):  # (as above: an older build has no wide rounds)
+            L.wmi_set_wide_rounds.argtypes = [vp, C.c_int]
         if hasattr(L, "wmi_decode_timestamps_ruled_beam_rows"):  # (as above: an older build has no ruled wide step)
             L.wmi_decode_timestamps_ruled_beam_rows.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
         if hasattr(L, "wmi_set_token_timestamps"):  # (as above: an older build has no token-level timestamps)
@@ -625,6 +628,14 @@ class WhisperContext:
         stays Unsupported.  Neither: InvalidArgument."""
         _raise(lib().wmi_set_batch_beam(self._h, int(enable)), self._h)
 
+    def set_wide_rounds(self, rows=64) -> None:
+        """rows in [1, 64]: every round of transcribe_batch(), at every beam
+        size, decodes on the wide decoder step and holds up to rows // beam
+        size recordings (decode_timestamps_beam_rows() likewise); at one
+        hypothesis a recording the step's cross-attention is k_wd_cross_attn1.
+        0, the default: off.  Anything else: InvalidArgument."""
+        _raise(lib().wmi_set_wide_rounds(self._h, int(rows)), self._h)
+
     def decode_timestamps_ruled_beam_rows(self, beam_size: int, prompts, max_tokens: int):
         """decode_timestamps_beam_rows() under the decoding rules: per clip the
         window of decode_timestamps_ruled_beam().  No rules enabled:
@@ -652,7 +663,7 @@ class WhisperContext:
 
     def wide_run(self):
         """Debug read 38: (B, K, steps, [p_c]) of the last wide run."""
-        v = np.frombuffer(self.debug_read(38, 11 * 4), np.int32)
+        v = np.frombuffer(self.debug_read(38, (3 + 64) * 4), np.int32)
         return int(v[0]), int(v[1]), int(v[2]), v[3:3 + int(v[0])].tolist()
 
     def wide_logits(self, max_tokens: int) -> np.ndarray:
