@@ -360,7 +360,8 @@ int wmi_decode_timestamps_ruled_beam_rows(wmi_context *ctx, int beam_size, const
  * with the decoding rules on unless wmi_set_rules_beam is set (then every
  * window is the ruled beam window, and recording c yields the segments of
  * wmi_transcribe of it alone), with the fallback on (a round would hold beam
- * rows and sampled rows at once) and with best_of above 1.  enable 0
+ * rows and sampled rows at once) and with best_of above 1, the last two unless
+ * wmi_set_wide_fallback is on.  enable 0
  * (default): a beam size above 1 in the batch is WMI_E_UNSUPPORTED and every
  * call launches what it launched before.  Neither 0 nor 1:
  * WMI_E_INVALID_ARG.  Holds until changed. */
@@ -383,11 +384,61 @@ int wmi_set_batch_beam(wmi_context *ctx, int enable);
  * per eight.  With the option on the batch calls are WMI_E_UNSUPPORTED,
  * checked at the call, for an f32 file, with the decoding rules at a beam
  * size above 1 unless wmi_set_rules_beam is set, and with the fallback on
- * (with it best_of: the wide step has no sampled rows); a beam size above 1
+ * (with it best_of) unless wmi_set_wide_fallback is on; a beam size above 1
  * still needs wmi_set_batch_beam.  rows 0 (default): off, every call launches
  * what it launched before.  Outside [0, 64]: WMI_E_INVALID_ARG.  Holds until
  * changed.  Nothing is claimed for calls under wmi_set_chunking. */
 int wmi_set_wide_rounds(wmi_context *ctx, int rows);
+/* Sampled rows on the wide step: one sampled window for every encoded clip,
+ * best_of row slots a clip, in rounds of 64 / best_of clips (64 / 12 / 8 clips
+ * at best_of 1 / 5 / 8), whatever wmi_set_wide_rounds says.  Clip b decodes
+ * after prompts[b * prompt_stride .. + n_prompt[b]) at temperature[b] as
+ * attempt ordinal n[b] of `seed`: at temperature[b] > 0 best_of candidates with
+ * the stream keys of wmi_best_of_key(seed, n[b], c), at 0 one candidate (the
+ * most probable allowed token; the clip's other row slots stay idle).  The
+ * context's decoding rules are applied if enabled, as in
+ * wmi_decode_timestamps_best_of.  The candidates of a clip share its prompt's
+ * keys and draw their first token from the one row of its prompt's last step;
+ * a candidate that drew EOT feeds EOT while the others go on; a clip is done
+ * when all its candidates are, or at max_tokens, and then idles.  The
+ * candidate with the largest mean log-probability is returned (ties: the
+ * lowest index).  Clip b yields what wmi_decode_timestamps_best_of yields for
+ * it alone with the same arguments (at temperature 0 what
+ * wmi_decode_timestamps_sampled / _ruled yields), up to the order of the
+ * floating-point sums of the decoder step: from equal logits the sampler
+ * writes the same bits.  out is [n_clips][max_tokens], n_out [n_clips]; plog
+ * [n_clips][max_tokens] (the chosen candidate's log-probabilities), p_nosp
+ * [n_clips] and chosen [n_clips] may be NULL.  The prompt goes through the
+ * prefill pass: a prompt above 257 tokens and an f32 file are
+ * WMI_E_UNSUPPORTED.  best_of outside [1, 8], a temperature outside [0, 1] or
+ * an ordinal below 0: WMI_E_INVALID_ARG.  The batch calls take this window
+ * under wmi_set_wide_fallback (below). */
+int wmi_decode_timestamps_sampled_rows(wmi_context *ctx, int best_of, const int32_t *prompts, int prompt_stride,
+                                       const int32_t *n_prompt, int max_tokens, const float *temperature, uint64_t seed,
+                                       const int32_t *n, wmi_token_data *out, int32_t *n_out, float *plog, float *p_nosp,
+                                       int32_t *chosen);
+/* enable 1: wmi_transcribe_batch / wmi_transcribe_audio_batch on the wide step
+ * (under wmi_set_wide_rounds, or under wmi_set_batch_beam at a beam size above
+ * 1) accept wmi_set_fallback parameters and wmi_set_best_of, which they refuse
+ * there otherwise.  A round then holds rows / max(beam size, best_of)
+ * recordings (eight without wmi_set_wide_rounds).  The recordings whose next
+ * attempt is a beam window (temperature 0 at a beam size above 1) are placed
+ * in the first encoder slots and decode as one beam window of K rows a
+ * recording, ruled under wmi_set_rules_beam, with each recording's no-speech
+ * probability taken from its first step (k_wd_no_speech); all others decode as
+ * one sampled window of best_of row slots a recording (the window of
+ * wmi_decode_timestamps_sampled_rows; at beam size 1 the temperature-0
+ * attempts too).  Each recording's attempt ordinal advances as in
+ * wmi_transcribe, and recording c yields the segments, window infos and
+ * wmi_get_window_candidate values that wmi_transcribe yields for it alone
+ * under the same settings, up to the order of the floating-point sums.  Still
+ * WMI_E_UNSUPPORTED: an f32 file, and the decoding rules at a beam size above
+ * 1 without wmi_set_rules_beam.  With the fallback off the opt-in changes
+ * nothing.  enable 0 (default): every call launches and refuses what it did
+ * before.  Neither 0 nor 1: WMI_E_INVALID_ARG.  Holds until changed.  Nothing
+ * is claimed for calls under wmi_set_chunking: there the opt-in has no effect
+ * and the fallback and best_of stay refused on the wide step. */
+int wmi_set_wide_fallback(wmi_context *ctx, int enable);
 
 /* ---- temperature fallback, quality thresholds, no-speech ---------------- */
 

@@ -197,6 +197,12 @@ struct wmi_context {
     // the wide step under the decoding rules (wmi_wide_rules.hip): the rule block, an allocation of its own made with
     // the first ruled wide window: the hypotheses' histories [recs][8], then the parts [recs][8][16]
     WdRuleTable wd_rt{};
+    // sampled rows on the wide step (wmi_wide_sample.hip): the sample block, an allocation of its own made with the
+    // first sampled wide window, for the 64 row slots a window can hold
+    WdSampTable wd_st{};
+    // wmi_set_wide_fallback: the batch calls on the wide step take the fallback and best_of (a beam window and a
+    // sampled window a round)
+    bool wide_fallback = false;
     // batched transcription: source recording, then mel offset of each encoder slot, then (chunked calls) its end:
     // three columns of 8, of 64 under wide rounds
     int32_t *d_win = nullptr;
@@ -3136,9 +3142,26 @@ std::vector<int32_t> ts_init_prompt(const wmi_context *ctx, int lang) {
 
 int run_ts_beam_window(wmi_context *ctx, int clip, const std::vector<int32_t> &prompt, int K, int max_tokens,
                        std::vector<TsRec> *out, double *score, float *p_nosp = nullptr, bool ruled = false);
+// a sampled wide window (run_wide_beam_rows with `samp`): per recording its temperature and candidates' keys in, records out
+struct WideSamp {
+    std::vector<float> T;                                  // [B]
+    std::vector<std::array<uint64_t, BEAM_MAX>> key;       // [B][K]
+    std::vector<std::vector<std::vector<TsRec>>> recs;     // [B][candidates of c]
+    std::vector<std::vector<std::vector<float>>> plog;
+    std::vector<float> p_nosp;                             // [B]
+};
 int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector<std::vector<int32_t>> &prompts, int max_tokens,
-                       std::vector<std::vector<TsRec>> *out, std::vector<double> *scores, bool ruled);
+                       std::vector<std::vector<TsRec>> *out, std::vector<double> *scores, bool ruled,
+                       WideSamp *samp = nullptr, std::vector<float> *p_nosp = nullptr);
 int wide_round_clips(const wmi_context *ctx, int K);
+// the batch on the wide step under the fallback (wmi_set_wide_fallback): a round is a beam window and a sampled window
+static bool wide_fb_on(const wmi_context *ctx) {
+    // (not under wmi_set_chunking: nothing is claimed there, and the entry points refuse the fallback as before)
+    return ctx->wide_fallback && ctx->fb_on && !ctx->ck_par.enable &&
+           (ctx->wide_rows > 0 || (ctx->batch_beam && ctx->beam_size > 1));
+}
+// row slots a recording of such a round takes
+static int wide_fb_slots(const wmi_context *ctx) { return std::max(ctx->beam_size, ctx->best_of); }
 
 // after attempt 0: probably silence (OpenAI's no_speech_threshold rule)
 bool fb_silence(const wmi_context *ctx, float p_nosp, const FbAttempt &att) {
@@ -3253,6 +3276,13 @@ struct TrAttempt {
     float p_nosp, T;
     int chosen = -1, n_cand = 0;  // a best-of attempt: the candidate that became toks, and their number
 };
+// whether the recording's next attempt is a beam window: a T = 0 attempt at a beam size above 1
+static bool tr_beam_attempt(const wmi_context *ctx, const TrRun &tr, const TrRec &rec) {
+    return ctx->beam_size > 1 && (tr.temps.empty() || tr.temps[rec.att] == 0.0f);
+}
+int tr_decode_attempt_wide(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows, const std::vector<int32_t> &feed,
+                           const std::vector<int> &lens, std::vector<TrAttempt> *out);
+
 // The recordings `rows` sit in the encoded rows 0..B-1 and row b is fed the np
 // tokens feed[b * np ..): each row's attempt at its recording's temperature.
 // Fallback off: the plain sampler (k_ts_sample), or with a beam size the beam
@@ -3273,6 +3303,7 @@ int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows,
     // (wmi_set_wide_rounds: every round of a batch call, `lens` given, is a round of beam windows on the wide step,
     // the greedy window the K = 1 beam window; the entry points have refused the fallback)
     const bool wide = lens && ctx->wide_rows > 0;
+    if (lens && wide_fb_on(ctx)) return tr_decode_attempt_wide(ctx, tr, rows, feed, *lens, out);
     if ((ctx->beam_size > 1 || wide) && (*out)[0].T == 0.0f) {
         if (B != 1 || wide) {
             if (!ctx->batch_beam && !wide) return set_err(ctx, WMI_E_UNSUPPORTED, "a beam window decodes one recording (%d rows)", B);
@@ -3330,6 +3361,71 @@ int tr_decode_attempt(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows,
         for (float v : sp.plog[b]) a.logprob_sum += (double)v;
         a.p_nosp = sp.p_nosp[b];
     }
+    return WMI_OK;
+}
+
+// tr_decode_attempt of a batch round under wmi_set_wide_fallback: at most two wide windows over contiguous encoder
+// slots.  The rows whose attempt is a beam window come first (run_transcribe_batch orders them so): one beam window of
+// K rows a recording, ruled under the rules, k_wd_no_speech in its step, the score its logprob_sum as
+// run_ts_beam_window reports it.  Everything else is one sampled window of best_of row slots a recording: T = 0 rows
+// one candidate, rows above it best_of candidates of the recording's next attempt ordinal.
+int tr_decode_attempt_wide(wmi_context *ctx, TrRun &tr, const std::vector<int> &rows, const std::vector<int32_t> &feed,
+                           const std::vector<int> &lens, std::vector<TrAttempt> *out) {
+    const int B = (int)rows.size();
+    std::vector<std::vector<int32_t>> prompts((size_t)B);
+    size_t at = 0;
+    int nb = 0;
+    for (int b = 0; b < B; ++b) {
+        prompts[b].assign(feed.begin() + at, feed.begin() + at + lens[b]);
+        at += (size_t)lens[b];
+        if (tr_beam_attempt(ctx, tr, tr.recs[rows[b]])) {
+            if (nb != b) return set_err(ctx, WMI_E_UNEXPECTED, "internal: beam row %d behind a sampled row", b);
+            ++nb;
+        }
+    }
+    int steps = 0;
+    if (nb > 0) {
+        std::vector<std::vector<TsRec>> toks;
+        std::vector<double> sc;
+        std::vector<float> nosp;
+        int rc = run_wide_beam_rows(ctx, 0, nb, ctx->beam_size, {prompts.begin(), prompts.begin() + nb}, tr.n_max, &toks, &sc,
+                                    ctx->rules_on, nullptr, &nosp);
+        if (rc) return rc;
+        steps += ctx->last_run_steps;
+        for (int b = 0; b < nb; ++b) {
+            TrAttempt &a = (*out)[b];
+            a.toks = std::move(toks[b]);
+            a.logprob_sum = sc[b];
+            a.p_nosp = nosp[b];
+        }
+    }
+    if (nb < B) {
+        const int W = ctx->best_of, Bs = B - nb;
+        WideSamp ws;
+        ws.key.assign((size_t)Bs, {});
+        for (int b = nb; b < B; ++b) {
+            const float T = (*out)[b].T;
+            ws.T.push_back(T);
+            if (T > 0.0f) {
+                const uint64_t n = tr.recs[rows[b]].n_samp++;  // (one attempt, one ordinal)
+                for (int k = 0; k < W; ++k) ws.key[(size_t)(b - nb)][k] = best_of_key(ctx->fb.seed, n, k);
+            }
+        }
+        int rc = run_wide_beam_rows(ctx, nb, Bs, W, {prompts.begin() + nb, prompts.end()}, tr.n_max, nullptr, nullptr,
+                                    ctx->rules_on, &ws);
+        if (rc) return rc;
+        steps += ctx->last_run_steps;
+        for (int b = nb; b < B; ++b) {
+            TrAttempt &a = (*out)[b];
+            const size_t i = (size_t)(b - nb);
+            const int best = best_of_choose(ws.plog[i], nullptr);
+            if (W > 1 && a.T > 0.0f) { a.chosen = best; a.n_cand = W; }
+            a.toks = std::move(ws.recs[i][best]);
+            for (float v : ws.plog[i][best]) a.logprob_sum += (double)v;
+            a.p_nosp = ws.p_nosp[i];
+        }
+    }
+    ctx->last_run_steps = steps;
     return WMI_OK;
 }
 
@@ -3617,7 +3713,9 @@ int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
         ctx->lang_p[r] = -1.0f;
     }
     const int n_recs = (int)tr.recs.size();
-    const int round = wide ? wide_round_clips(ctx, ctx->beam_size) : DEC_ROWS;
+    // (wmi_set_wide_fallback: a recording takes max(beam size, best_of) row slots)
+    const bool wfb = wide_fb_on(ctx);
+    const int round = wide ? wide_round_clips(ctx, wfb ? wide_fb_slots(ctx) : ctx->beam_size) : DEC_ROWS;
     const size_t max_rows = chunked || wide ? (size_t)std::min(round, ctx->max_clips) : (size_t)DEC_ROWS;
     std::vector<int> rows;  // recording (chunk) of each decoder row
     int next = 0;
@@ -3629,6 +3727,8 @@ int run_transcribe_batch(wmi_context *ctx, int max_tokens) {
         for (; next < n_recs && rows.size() < max_rows; ++next)
             if (tr.recs[next].seek < tr.recs[next].n_len) rows.push_back(next);
         if (rows.empty()) break;
+        if (wfb)  // (the recordings whose next attempt is a beam window first: each window's encoder slots are contiguous)
+            std::stable_partition(rows.begin(), rows.end(), [&](int r) { return tr_beam_attempt(ctx, tr, tr.recs[r]); });
         const int B = (int)rows.size();
         int32_t win[3 * WD_ROWS] = {};
         for (int b = 0; b < B; ++b) {
@@ -3998,8 +4098,10 @@ int ensure_wide_buffers(wmi_context *ctx, int R, int B, int K, int chunks, int l
 
 // one wide step of B x K rows: the fixed launch sequence (nothing in it depends on the step); with `ruled` its beam
 // step is the one under the decoding rules (k_wd_rbeam_part / k_wd_rbeam_select), with `rows1` (K = 1 under
-// wmi_set_wide_rounds) its cross-attention k_wd_cross_attn1
-int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles, bool ruled, bool rows1) {
+// wmi_set_wide_rounds) its cross-attention k_wd_cross_attn1; with `sampled` the tail is the samplers of K row slots a
+// recording (wmi_wide_sample.hip), under the rules with `ruled`
+int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles, bool ruled, bool rows1, bool sampled = false,
+                      bool nosp = false) {
     const wmi_hparams &hp = ctx->hp;
     const int n = hp.n_text_state, H = hp.n_text_head, T = ctx->enc_T, Bt = ctx->enc_clips, tctx = hp.n_text_ctx, M = B * K;
     hipStream_t s = ctx->stream;
@@ -4058,6 +4160,22 @@ int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles, boo
     GemmArgs g = gemm(ctx->pf_ln16, n, ctx->te, nullptr, hp.n_vocab);
     g.out32 = ctx->wd_logits; g.ldo = hp.n_vocab;
     HIPCHK(ctx, dense_product(ctx, s, EPI_F32, g, ctx->qgemm ? &ctx->qte : nullptr));
+    if (sampled) {
+        WdSampArgs sa{};
+        sa.tb = ctx->wd_tb; sa.st = ctx->wd_st; sa.logits = ctx->wd_logits; sa.V = hp.n_vocab; sa.W = K; sa.B = B;
+        sa.eot = ctx->sp.eot; sa.tctx = tctx; sa.beg = ctx->sp.beg; sa.sot = ctx->sp.sot; sa.solm = ctx->sp.solm;
+        sa.not_ = ctx->sp.not_; sa.max_rec = tctx; sa.m0 = ctx->d_rule_m0; sa.max_initial_ts = ctx->max_initial_ts;
+        if (ctx->d_lgall) {  // WMI_LOGITS_ALL: every live row's logits, ahead of the tail that advances p_c
+            WdBeamArgs la{};
+            la.tb = ctx->wd_tb; la.logits = ctx->wd_logits; la.V = hp.n_vocab; la.K = K; la.B = B;
+            la.lg_all = ctx->wd_lgall; la.lg_steps = ctx->wd_lg_steps;
+            HIPCHK(ctx, launch_wd_logits_capture(s, la));
+        }
+        HIPCHK(ctx, launch_wd_sample_step(s, sa, ruled));
+        return WMI_OK;
+    }
+    if (nosp)  // (ahead of the beam step, which advances p_c)
+        HIPCHK(ctx, launch_wd_no_speech(s, ctx->wd_tb, ctx->wd_logits, B, K, hp.n_vocab, ctx->sp.solm, ctx->wd_st.p_nosp));
     WdBeamArgs ba{};
     ba.tb = ctx->wd_tb; ba.logits = ctx->wd_logits; ba.V = hp.n_vocab; ba.K = K; ba.B = B; ba.eot = ctx->sp.eot; ba.tctx = tctx;
     ba.beg = ctx->sp.beg; ba.sot = ctx->sp.sot; ba.solm = ctx->sp.solm; ba.not_ = ctx->sp.not_;
@@ -4077,17 +4195,24 @@ int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles, boo
 // decoding rules: every hypothesis' history starts empty with the table.  Recordings do not interact, one whose search is done freezes while the others go on.  The prompts' positions 0 .. np_c - 2 go
 // through a prefill pass (eight recordings a pass) into wide-cache slot c K, which every hypothesis' history names; the steps follow in
 // chunks of 16 with a look at the done words.  out[c] = the chosen hypothesis' records, scores[c] its score.
+// With `samp` the window is a sampled one on the same set-up (out and scores unused): K row slots a recording,
+// recording c at temperature samp->T[c] with one candidate at 0 and K above it, candidate k's stream key
+// samp->key[c][k]; every candidate's history names slot 0 for the prompt and its own slot behind it, the step's tail
+// is the samplers', and samp takes every candidate's records and log-probabilities.
 int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector<std::vector<int32_t>> &prompts, int max_tokens,
-                       std::vector<std::vector<TsRec>> *out, std::vector<double> *scores, bool ruled) {
+                       std::vector<std::vector<TsRec>> *out, std::vector<double> *scores, bool ruled, WideSamp *samp,
+                       std::vector<float> *p_nosp) {
     const wmi_hparams &hp = ctx->hp;
     const int tctx = hp.n_text_ctx;
     if (ruled && (!ctx->rules_on || !ctx->d_rule_m0)) return set_err(ctx, WMI_E_INVALID_ARG, "no decoding rules are enabled");
     if (ctx->enc_T <= 0 || ctx->enc_clips < 1) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
     if (K < 1 || K > BEAM_MAX) return set_err(ctx, WMI_E_INVALID_ARG, "beam size %d outside [1, %d]", K, BEAM_MAX);
-    if (B < 1 || B > wide_round_clips(ctx, K) || (int)prompts.size() != B || b0 < 0 || b0 + B > ctx->enc_clips)
+    if (B < 1 || B > (samp ? WD_ROWS / K : wide_round_clips(ctx, K)) || (int)prompts.size() != B || b0 < 0 ||
+        b0 + B > ctx->enc_clips || (samp && ((int)samp->T.size() != B || (int)samp->key.size() != B)))
         return set_err(ctx, WMI_E_INVALID_ARG, "rows [%d, %d) outside the %d encoded clips", b0, b0 + B, ctx->enc_clips);
     int rc = wide_unsupported(ctx);
     if (rc) return rc;
+    if (samp && (rc = samp_supported(ctx))) return rc;
     int pmax = 0;
     for (const auto &p : prompts) {
         const int np = (int)p.size();
@@ -4115,7 +4240,21 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
     rc = ensure_wide_buffers(ctx, R, B, K, chunks, max_tokens);
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    if (ruled && B > ctx->wd_rt_recs) {
+    if ((samp || p_nosp) && !ctx->wd_st.rows) {  // (B K <= 64 row slots whatever the window: never regrown)
+        size_t off = 0;
+        auto take = [&](size_t nb) { const size_t o = off; off += (size_t)up((int64_t)nb, 16); return o; };
+        const size_t o_rows = take(WD_ROWS * sizeof(SampRow)), o_done = take(WD_ROWS * 4), o_nc = take(WD_ROWS * 4);
+        const size_t o_nosp = take(WD_ROWS * 4), o_hist = take(WD_ROWS * sizeof(RuleHist));
+        const size_t o_rec = take((size_t)WD_ROWS * tctx * sizeof(TsRec)), o_plog = take((size_t)WD_ROWS * tctx * 4);
+        char *p = nullptr;
+        HIPCHK(ctx, hipMalloc(&p, off));
+        ctx->wd_st.rows = (SampRow *)(p + o_rows);  // (o_rows is 0: the context owns the block from here on)
+        HIPCHK(ctx, hipMemset(p, 0, off)); ctx->wd_st.done = (int32_t *)(p + o_done);
+        ctx->wd_st.ncand = (int32_t *)(p + o_nc); ctx->wd_st.p_nosp = (float *)(p + o_nosp);
+        ctx->wd_st.hist = (RuleHist *)(p + o_hist); ctx->wd_st.rec = (TsRec *)(p + o_rec);
+        ctx->wd_st.plog = (float *)(p + o_plog);
+    }
+    if (ruled && !samp && B > ctx->wd_rt_recs) {
         if (ctx->wd_rt.hist) {
             HIPCHK(ctx, hipStreamSynchronize(s));
             HIPCHK(ctx, hipFree(ctx->wd_rt.hist));
@@ -4156,7 +4295,27 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
     HIPCHK(ctx, hipMemcpyAsync(ctx->wd_tb.recs, recs.data(), (size_t)NB * sizeof(WdRec), hipMemcpyHostToDevice, s));
     HIPCHK(ctx, hipMemcpyAsync(ctx->wd_tb.bs, bs.data(), (size_t)NB * sizeof(BeamState), hipMemcpyHostToDevice, s));
     HIPCHK(ctx, hipMemsetAsync(ctx->wd_tb.kv_src, 0, (size_t)NB * BEAM_MAX * tctx * 4, s));  // (the prompt's keys: slot 0)
-    if (ruled)  // (no hypothesis has sampled anything)
+    std::vector<int32_t> src, ncand;
+    std::vector<SampRow> srows;
+    if (samp) {
+        // candidate k's keys: the prompt's from slot 0 (its last position is processed on row 0 at t = 0), its own behind
+        src.assign((size_t)B * BEAM_MAX * tctx, 0);
+        ncand.assign(WD_ROWS, 0);
+        srows.assign(WD_ROWS, SampRow{});
+        for (int c = 0; c < B; ++c) {
+            ncand[c] = samp->T[c] > 0.0f ? K : 1;
+            for (int k = 0; k < K; ++k) {
+                srows[(size_t)c * K + k].T = samp->T[c];
+                srows[(size_t)c * K + k].key = samp->key[c][k];
+                for (int j = (int)prompts[c].size(); j < tctx; ++j) src[((size_t)c * BEAM_MAX + k) * tctx + j] = k;
+            }
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->wd_tb.kv_src, src.data(), src.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->wd_st.rows, srows.data(), WD_ROWS * sizeof(SampRow), hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->wd_st.ncand, ncand.data(), WD_ROWS * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemsetAsync(ctx->wd_st.done, 0, WD_ROWS * 4, s));
+        HIPCHK(ctx, hipMemsetAsync(ctx->wd_st.hist, 0, WD_ROWS * sizeof(RuleHist), s));
+    } else if (ruled)  // (no hypothesis has sampled anything)
         HIPCHK(ctx, hipMemsetAsync(ctx->wd_rt.hist, 0, (size_t)NB * BEAM_MAX * sizeof(RuleHist), s));
     for (size_t i = 0; i < pfs.size(); ++i) {  // (pass i: feed rows 8 i ..)
         rc = prefill_pass(ctx, pfs[i], pmax, false, ctx->wd_k, ctx->wd_v, ctx->wd_rows, ctx->dfeed + i * DEC_ROWS * pmax);
@@ -4172,7 +4331,11 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
     int kl = snprintf(key, sizeof key, "wide/%d/%d/%d/%d/%d/%d/%p/%d/%p/%d/%p/%p/%d", B, K, chunks, tiles, ctx->enc_T, ctx->enc_clips,
                       (void *)ctx->pf_x, ctx->pf_cap, (void *)ctx->wd_k, ctx->wd_rows, (void *)ctx->wd_part,
                       (void *)(ctx->d_lgall ? ctx->wd_lgall : nullptr), ctx->d_lgall ? ctx->wd_lg_steps : 0);
-    if (ruled && kl > 0 && kl < (int)sizeof key) kl += snprintf(key + kl, sizeof key - kl, "/ruled/%p", (void *)ctx->wd_rt.hist);
+    if (samp && kl > 0 && kl < (int)sizeof key)  // (the tail and its block; K, the row slots, is named above)
+        kl += snprintf(key + kl, sizeof key - kl, "/%s/%p", ruled ? "rsamp" : "samp", (void *)ctx->wd_st.rows);
+    else if (ruled && kl > 0 && kl < (int)sizeof key)
+        kl += snprintf(key + kl, sizeof key - kl, "/ruled/%p", (void *)ctx->wd_rt.hist);
+    if (p_nosp && !samp && kl > 0 && kl < (int)sizeof key) kl += snprintf(key + kl, sizeof key - kl, "/nosp/%p", (void *)ctx->wd_st.p_nosp);
     if (rows1 && kl > 0 && kl < (int)sizeof key) snprintf(key + kl, sizeof key - kl, "/rows1");
     wmi_context::Graph *graph = nullptr;
     if (ctx->use_graph) {
@@ -4184,7 +4347,7 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
         const int chunk = std::min(16, max_tokens - done);
         for (int i = 0; i < chunk; ++i, ++steps) {
             if (!ctx->use_graph || (!graph && steps == 0)) {
-                rc = enqueue_wide_step(ctx, B, K, chunks, tiles, ruled, rows1);
+                rc = enqueue_wide_step(ctx, B, K, chunks, tiles, ruled, rows1, samp != nullptr, p_nosp != nullptr);
                 if (rc) return rc;
                 continue;
             }
@@ -4192,7 +4355,7 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
                 if (ctx->graphs.size() >= 32) ctx->clear_graphs();
                 HIPCHK(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
                 const int64_t ql0 = ctx->qgemm_launches;
-                rc = enqueue_wide_step(ctx, B, K, chunks, tiles, ruled, rows1);
+                rc = enqueue_wide_step(ctx, B, K, chunks, tiles, ruled, rows1, samp != nullptr, p_nosp != nullptr);
                 const int ql = (int)(ctx->qgemm_launches - ql0);  // (recorded, not launched: every replay counts them)
                 ctx->qgemm_launches = ql0;
                 hipGraph_t gr = nullptr;
@@ -4224,6 +4387,37 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
     memset(ctx->wd_last, 0, sizeof ctx->wd_last);
     ctx->wd_last[0] = B; ctx->wd_last[1] = K; ctx->wd_last[2] = steps;
     for (int c = 0; c < B; ++c) ctx->wd_last[3 + c] = recs[c].p;
+    if (samp) {
+        samp->recs.assign((size_t)B, {});
+        samp->plog.assign((size_t)B, {});
+        samp->p_nosp.assign((size_t)B, 0.0f);
+        HIPCHK(ctx, hipMemcpy(samp->p_nosp.data(), ctx->wd_st.p_nosp, (size_t)B * 4, hipMemcpyDeviceToHost));
+        std::vector<TsRec> hrec((size_t)B * K * tctx);  // (the blocks are contiguous: one copy each)
+        std::vector<float> hplog((size_t)B * K * tctx);
+        HIPCHK(ctx, hipMemcpy(hrec.data(), ctx->wd_st.rec, hrec.size() * sizeof(TsRec), hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(hplog.data(), ctx->wd_st.plog, hplog.size() * 4, hipMemcpyDeviceToHost));
+        for (int c = 0; c < B; ++c) {
+            const int have = bs[c].n_steps;  // records written so far (per candidate that has not met EOT)
+            if (have < 1 || have > max_tokens) return set_err(ctx, WMI_E_HIP, "sampled row %d produced %d steps", c, have);
+            samp->recs[c].assign((size_t)ncand[c], {});
+            samp->plog[c].assign((size_t)ncand[c], {});
+            for (int k = 0; k < ncand[c]; ++k) {
+                auto &r = samp->recs[c][k];
+                const size_t at = ((size_t)c * K + k) * tctx;
+                r.assign(hrec.begin() + at, hrec.begin() + at + have);
+                samp->plog[c][k].assign(hplog.begin() + at, hplog.begin() + at + have);
+                // (a candidate that met EOT wrote nothing behind it: what lies there is stale)
+                for (size_t i = 0; i < r.size(); ++i)
+                    if (r[i].id == ctx->sp.eot) { r.resize(i + 1); break; }
+                samp->plog[c][k].resize(r.size());
+            }
+        }
+        return WMI_OK;
+    }
+    if (p_nosp) {
+        p_nosp->assign((size_t)B, 0.0f);
+        HIPCHK(ctx, hipMemcpy(p_nosp->data(), ctx->wd_st.p_nosp, (size_t)B * 4, hipMemcpyDeviceToHost));
+    }
     out->assign((size_t)B, {});
     if (scores) scores->assign((size_t)B, 0.0);
     for (int c = 0; c < B; ++c) {
@@ -4427,6 +4621,7 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->d_rule_m0) (void)hipFree(ctx->d_rule_m0);
     if (ctx->d_rb_hist) (void)hipFree(ctx->d_rb_hist);
     if (ctx->wd_rt.hist) (void)hipFree(ctx->wd_rt.hist);
+    if (ctx->wd_st.rows) (void)hipFree(ctx->wd_st.rows);
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -4667,6 +4862,7 @@ static int wmi_decode_timestamps_ruled_beam_impl(wmi_context *ctx, int beam_size
 // A best-of window puts N candidates of one recording on the decoder rows: as for a beam size, the rows of a batch
 // (and the chunks of a chunked call) do not fit beside them.  Refused only where a temperature above 0 can be reached.
 static int best_of_unsupported(wmi_context *ctx, const char *what) {
+    if (wide_fb_on(ctx)) return WMI_OK;  // (a sampled wide window holds best_of row slots a recording)
     if (ctx->best_of > 1 && ctx->fb_on && (ctx->fb.temperature > 0.0f || ctx->fb.temperature_inc > 0.0f))
         return set_err(ctx, WMI_E_UNSUPPORTED, "%s draws one sample an attempt: best_of %d is set and a temperature above 0 "
                        "can be reached (wmi_set_best_of(ctx, 1), or wmi_transcribe per recording)", what, ctx->best_of);
@@ -4747,7 +4943,7 @@ static int batch_beam_unsupported(wmi_context *ctx) {
     if (ctx->rules_on && !ctx->rules_beam)  // (with wmi_set_rules_beam: the ruled wide step, wmi_wide_rules.hip)
         return set_err(ctx, WMI_E_UNSUPPORTED, "beam search in the batch does not carry the decoding rules "
                        "(wmi_set_decode_rules(ctx, NULL), or wmi_transcribe per recording)");
-    if (ctx->fb_on)
+    if (ctx->fb_on && !wide_fb_on(ctx))  // (wmi_set_wide_fallback: a beam window and a sampled window a round)
         return set_err(ctx, WMI_E_UNSUPPORTED, "beam search in the batch does not carry the temperature fallback: a round "
                        "would hold beam rows and sampled rows at once (wmi_set_fallback(ctx, NULL), or wmi_transcribe)");
     return WMI_OK;
@@ -4761,7 +4957,7 @@ static int wide_rounds_unsupported(wmi_context *ctx) {
     if (ctx->rules_on && ctx->beam_size > 1 && !ctx->rules_beam)
         return set_err(ctx, WMI_E_UNSUPPORTED, "wide rounds at a beam size above 1 carry the decoding rules only under "
                        "wmi_set_rules_beam");
-    if (ctx->fb_on)
+    if (ctx->fb_on && !wide_fb_on(ctx))
         return set_err(ctx, WMI_E_UNSUPPORTED, "wide rounds do not carry the temperature fallback or best_of: the wide step "
                        "has no sampled rows (wmi_set_fallback(ctx, NULL), or wmi_set_wide_rounds(ctx, 0))");
     return WMI_OK;
@@ -4803,6 +4999,55 @@ static int wmi_decode_timestamps_beam_rows_impl(wmi_context *ctx, int beam_size,
         for (int b = 0; b < B; ++b) {
             copy_out_tokens(rec[b], out + (size_t)(b0 + b) * max_tokens, n_out + b0 + b);
             if (score) score[b0 + b] = sc[b];
+        }
+    }
+    return WMI_OK;
+}
+
+// One sampled window per encoded clip on the wide step, best_of row slots a clip, in rounds of 64 / best_of clips:
+// clip b at temperature[b] as attempt ordinal n[b] of `seed`, one candidate at temperature 0 and best_of above it
+static int wmi_decode_timestamps_sampled_rows_impl(wmi_context *ctx, int best_of, const int32_t *prompts, int prompt_stride,
+                                                   const int32_t *n_prompt, int max_tokens, const float *temperature,
+                                                   uint64_t seed, const int32_t *n, wmi_token_data *out, int32_t *n_out,
+                                                   float *plog, float *p_nosp, int32_t *chosen) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (!prompts || !n_prompt || prompt_stride < 1 || max_tokens < 1 || !out || !n_out || !temperature || !n)
+        return set_err(ctx, WMI_E_INVALID_ARG, "null prompts / n_prompt / temperature / n / out / n_out, or prompt_stride %d / "
+                       "max_tokens %d below 1", prompt_stride, max_tokens);
+    if (best_of < 1 || best_of > BEAM_MAX) return set_err(ctx, WMI_E_INVALID_ARG, "best_of %d outside [1, %d]", best_of, BEAM_MAX);
+    if (ctx->enc_T <= 0 || ctx->enc_clips < 1) return set_err(ctx, WMI_E_INVALID_ARG, "decode before encode");
+    const int Bt = ctx->enc_clips;
+    for (int b = 0; b < Bt; ++b) {
+        if (n_prompt[b] < 1 || n_prompt[b] > prompt_stride)
+            return set_err(ctx, WMI_E_INVALID_ARG, "n_prompt[%d] = %d outside [1, prompt_stride=%d]", b, n_prompt[b], prompt_stride);
+        if (!(temperature[b] >= 0.0f && temperature[b] <= 1.0f) || n[b] < 0)
+            return set_err(ctx, WMI_E_INVALID_ARG, "temperature[%d] %g outside [0, 1], or attempt ordinal %d below 0", b,
+                           (double)temperature[b], n[b]);
+        int rc = check_ts_args(ctx, prompts + (size_t)b * prompt_stride, n_prompt[b], max_tokens, out, n_out);
+        if (rc) return rc;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int round = WD_ROWS / best_of;
+    for (int b0 = 0; b0 < Bt; b0 += round) {
+        const int B = std::min(round, Bt - b0);
+        std::vector<std::vector<int32_t>> pr((size_t)B);
+        WideSamp ws;
+        ws.T.assign(temperature + b0, temperature + b0 + B);
+        ws.key.assign((size_t)B, {});
+        for (int b = 0; b < B; ++b) {
+            const int32_t *p = prompts + (size_t)(b0 + b) * prompt_stride;
+            pr[b].assign(p, p + n_prompt[b0 + b]);
+            if (ws.T[b] > 0.0f)
+                for (int k = 0; k < best_of; ++k) ws.key[b][k] = best_of_key(seed, (uint64_t)n[b0 + b], k);
+        }
+        int rc = run_wide_beam_rows(ctx, b0, B, best_of, pr, max_tokens, nullptr, nullptr, ctx->rules_on, &ws);
+        if (rc) return rc;
+        for (int b = 0; b < B; ++b) {
+            const int best = best_of_choose(ws.plog[b], nullptr);
+            copy_out_tokens(ws.recs[b][best], out + (size_t)(b0 + b) * max_tokens, n_out + b0 + b);
+            if (plog) std::copy(ws.plog[b][best].begin(), ws.plog[b][best].end(), plog + (size_t)(b0 + b) * max_tokens);
+            if (p_nosp) p_nosp[b0 + b] = ws.p_nosp[b];
+            if (chosen) chosen[b0 + b] = best;
         }
     }
     return WMI_OK;
@@ -6179,6 +6424,13 @@ int wmi_set_batch_beam(wmi_context *ctx, int enable) {
     return WMI_OK;
 }
 
+int wmi_set_wide_fallback(wmi_context *ctx, int enable) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    if (enable != 0 && enable != 1) return set_err(ctx, WMI_E_INVALID_ARG, "enable %d is neither 0 nor 1", enable);
+    ctx->wide_fallback = enable != 0;
+    return WMI_OK;
+}
+
 int wmi_set_wide_rounds(wmi_context *ctx, int rows) {
     if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
     if (rows < 0 || rows > WD_ROWS) return set_err(ctx, WMI_E_INVALID_ARG, "rows %d outside [0, %d]", rows, WD_ROWS);
@@ -6241,6 +6493,16 @@ int wmi_decode_timestamps_ruled_beam_rows(wmi_context *ctx, int beam_size, const
     return guarded(ctx, [&] {
         return wmi_decode_timestamps_beam_rows_impl(ctx, beam_size, prompts, prompt_stride, n_prompt, max_tokens, out, n_out,
                                                     score, true);
+    });
+}
+
+int wmi_decode_timestamps_sampled_rows(wmi_context *ctx, int best_of, const int32_t *prompts, int prompt_stride,
+                                       const int32_t *n_prompt, int max_tokens, const float *temperature, uint64_t seed,
+                                       const int32_t *n, wmi_token_data *out, int32_t *n_out, float *plog, float *p_nosp,
+                                       int32_t *chosen) {
+    return guarded(ctx, [&] {
+        return wmi_decode_timestamps_sampled_rows_impl(ctx, best_of, prompts, prompt_stride, n_prompt, max_tokens, temperature,
+                                                       seed, n, out, n_out, plog, p_nosp, chosen);
     });
 }
 

@@ -638,6 +638,33 @@ struct WdRBeamArgs {
 };
 // (the logits capture,) k_wd_rbeam_part, k_wd_rbeam_select
 hipError_t launch_wd_rbeam_step(hipStream_t s, const WdRBeamArgs &a);
+// ---- sampled rows on the wide step (wmi_wide_sample.hip; DESIGN.md "Sampled rows on the wide step"): the step's tail
+// of a window of B recordings x W row slots, row c W + k candidate k of recording c.  The table keeps recs, bs
+// (tok[k], n_active, done) and kv_src; what a sampled row adds is a block of its own beside it
+struct WdSampTable {         // device pointers into the sample block
+    SampRow *rows;           // [B][W] candidate k's temperature and stream key
+    int32_t *done;           // [B][W] != 0 once candidate k drew EOT
+    int32_t *ncand;          // [B] candidates of recording c: 1 at temperature 0, else N <= W
+    float *p_nosp;           // [B] P(solm) under the unmasked softmax of the first generated step
+    RuleHist *hist;          // [B][W] (ruled) history of candidate k
+    TsRec *rec;              // [B][W][max_rec]
+    float *plog;             // [B][W][max_rec]
+};
+struct WdSampArgs {
+    WdTable tb;
+    WdSampTable st;
+    const float *logits;     // [B W][V]
+    int V, W, B, eot, tctx, beg, sot, solm, not_, max_rec;
+    const uint32_t *m0;      // (ruled) [ceil(V / 32)] bit i set: id i is masked always (M0)
+    int max_initial_ts;      // (ruled) first timestamp <= beg + this (< 0: no cap)
+};
+// k_wd_sample<ruled>, one workgroup per (candidate, recording), then k_wd_sample_advance, one wave per recording
+hipError_t launch_wd_sample_step(hipStream_t s, const WdSampArgs &a, bool ruled);
+// k_wd_no_speech, one workgroup per recording: k_no_speech for every recording of a beam window of B x K rows.  At the
+// recording's first generated step (p_c = np_c - 1, not done) it reads row c K of the logits (step 0 expands
+// hypothesis 0 only) and writes p_nosp[c]; launched ahead of the beam step, which advances p_c
+hipError_t launch_wd_no_speech(hipStream_t s, const WdTable &tb, const float *logits, int B, int K, int V, int solm,
+                               float *p_nosp);
 
 // ---- persistent decoder: one launch runs n_steps greedy decoder steps -------
 // (wmi_persist.hip).  Every decoder step is a fixed sequence of phases; the

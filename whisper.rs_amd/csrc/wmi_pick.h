@@ -263,6 +263,138 @@ __device__ __forceinline__ float draw_plog(const DrawLds &d, float l, float m_a)
     return (float)((double)l - ((double)m_a + log(SE)));
 }
 
+// the bits of the ids base .. base + 31 that lie in [a, b] (the range_bits of wmi_rules.hip)
+__device__ __forceinline__ uint32_t pick_range_bits(int base, int a, int b) {
+    const int lo = a > base ? a - base : 0, hi = b - base < 31 ? b - base : 31;
+    if (lo > hi) return 0u;
+    return (0xffffffffu >> (31 - hi)) & (0xffffffffu << lo);
+}
+
+// The pick under the decoding rules, k_ts_sample_r's body behind its prologue as a function (k_wd_sample<true> in
+// wmi_wide_sample.hip; wmi_rules.hip keeps its own copy word for word until it calls this one).  One workgroup of
+// 1024 threads, blockIdx.x the row of a.rec; record t, plog[t] and at t = 0 *p_nosp (null: not wanted) are written by
+// thread 0, which advances the row's history *hist; returns the id (thread 0's)
+__device__ __forceinline__ int pick_ruled(const TsArgs &a, const float *lg, int t, const SampRow row, float *plog,
+                                         float *p_nosp, const uint32_t *m0, int max_initial_ts, RuleHist *hist) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    // the row's history and the scalars of the mask
+    const RuleHist h = *hist;
+    const bool last = t >= 1 && h.last != 0;
+    const bool penult = t < 2 || h.pen != 0;
+    const int x = t >= 1 ? h.lts1 - 1 : -1;  // the last timestamp sampled in this window (-1: none)
+    const int tx_lo = t == 0 ? a.beg : last && !penult ? a.eot : 0;
+    int lo = a.beg, hi = a.V - 1;
+    if (x >= 0) lo = last && !penult ? x : x + 1;
+    if (last && penult) lo = a.V;
+    if (t == 0 && max_initial_ts >= 0 && max_initial_ts < hi - a.beg) hi = a.beg + max_initial_ts;
+    __shared__ uint32_t s_ap[2048];
+    for (int j = tid; j < (a.V + 31) >> 5; j += 1024)
+        s_ap[j] = ~m0[j] & (pick_range_bits(32 * j, tx_lo, a.beg - 1) | pick_range_bits(32 * j, lo, hi));
+    __syncthreads();
+    auto in_ap = [&](int i) { return ((s_ap[i >> 5] >> (i & 31)) & 1u) != 0; };
+    __shared__ float smax[16];
+    __shared__ double ssum[16], sts[16];
+    __shared__ unsigned long long sk[3][16];
+    __shared__ DrawLds dl;
+    float mx = -INFINITY;
+    unsigned long long k_ts = 0, k_tx = 0, k_tsall = 0;
+    for (int i = tid; i < a.V; i += 1024) {
+        const float l = lg[i];
+        mx = fmaxf(mx, l);
+        const unsigned long long k = pick_key(l, i);
+        if (i >= a.beg) k_tsall = k > k_tsall ? k : k_tsall;
+        if (in_ap(i)) {
+            if (i >= a.beg) k_ts = k > k_ts ? k : k_ts;
+            else k_tx = k > k_tx ? k : k_tx;
+        }
+    }
+    mx = wave_max(mx);
+    k_ts = wave_max_u64(k_ts);
+    k_tx = wave_max_u64(k_tx);
+    k_tsall = wave_max_u64(k_tsall);
+    if (lane == 0) { smax[w] = mx; sk[0][w] = k_ts; sk[1][w] = k_tx; sk[2][w] = k_tsall; }
+    dl.tsum[tid] = 0.0;  // (ahead of pass 1's barrier)
+    __syncthreads();
+    mx = smax[0];
+    k_ts = sk[0][0]; k_tx = sk[1][0]; k_tsall = sk[2][0];
+    for (int i = 1; i < 16; ++i) {
+        mx = fmaxf(mx, smax[i]);
+        k_ts = sk[0][i] > k_ts ? sk[0][i] : k_ts;
+        k_tx = sk[1][i] > k_tx ? sk[1][i] : k_tx;
+        k_tsall = sk[2][i] > k_tsall ? sk[2][i] : k_tsall;
+    }
+    // (A' is never empty: EOT and the timestamps are in no suppress list)
+    const unsigned long long k_ap = k_ts > k_tx ? k_ts : k_tx;
+    const float m_p = pick_key_val(k_ap);
+    double s = 0.0, st = 0.0;
+    for (int i = tid; i < a.V; i += 1024) {
+        if (!in_ap(i)) continue;
+        const double e = exp((double)lg[i] - (double)m_p);
+        s += e;
+        if (i >= a.beg) st += e;
+    }
+    s = wave_sum(s);
+    st = wave_sum(st);
+    if (lane == 0) { ssum[w] = s; sts[w] = st; }
+    __syncthreads();
+    double Z = 0.0, TS = 0.0;
+    for (int i = 0; i < 16; ++i) { Z += ssum[i]; TS += sts[i]; }
+    const double sum_ts = TS / Z;
+    const double p_maxtx = k_tx ? exp((double)pick_key_val(k_tx) - (double)m_p) / Z : 0.0;
+    const bool ts_only = sum_ts > p_maxtx;
+    const unsigned long long k_a = ts_only ? k_ts : k_ap;
+    const float m_a = pick_key_val(k_a);
+    const float T = row.T;
+    auto in_a = [&](int i) { return (!ts_only || i >= a.beg) && in_ap(i); };
+    double Zu = 0.0;
+    if (t == 0) {  // the unmasked softmax's sum, for p_nosp
+        __syncthreads();  // (ssum is read above)
+        double su = 0.0;
+        for (int i = tid; i < a.V; i += 1024) su += exp((double)lg[i] - (double)mx);
+        su = wave_sum(su);
+        if (lane == 0) ssum[w] = su;
+        __syncthreads();
+        for (int i = 0; i < 16; ++i) Zu += ssum[i];
+    }
+    tile_sums(dl, lg, a.V, in_a, m_a, T);
+    int id = pick_key_id(k_a);
+    if (T > 0.0f) {
+        const double target = draw_tile(dl, row.key + (unsigned long long)t, [&](int &J, double &c) {
+            // (rounding left no group past the target: the last tile with any weight, its last such id)
+            #pragma unroll 1
+            for (int j = 0; j < 1024; ++j)
+                if (dl.tsum[j] > 0.0) J = j;
+            c = -INFINITY;
+        });
+        // (a tile there is: A holds m_A's id, whose weight is 1; the argmax stands in for none)
+        id = draw_id(dl, target, lg, a.V, in_a, m_a, T, id);
+    }
+    if (tid != 0) return id;
+    RuleHist hn;
+    hn.last = id >= a.beg;
+    hn.pen = t >= 1 ? h.last : 0;
+    hn.lts1 = id >= a.beg ? id + 1 : t >= 1 ? h.lts1 : 0;
+    hn.pad = 0;
+    *hist = hn;
+    if (p_nosp) *p_nosp = (float)(exp((double)lg[a.solm] - (double)mx) / Zu);
+    if (t < a.max_rec) {
+        // tid: the id itself if a timestamp, else the best timestamp of A', else (A' holds none) of all
+        const bool tid_in = id >= a.beg || k_ts != 0;
+        const int id_t = id >= a.beg ? id : pick_key_id(k_ts ? k_ts : k_tsall);
+        TsRec r;
+        r.id = id;
+        r.tid = id_t;
+        r.p = (float)(exp((double)lg[id] - (double)m_p) / Z);
+        r.pt = tid_in ? (float)((exp((double)lg[id_t] - (double)m_p) / Z) / (sum_ts + 1e-10)) : 0.0f;
+        r.ptsum = (float)sum_ts;
+        r.pad = 0;
+        a.rec[(size_t)blockIdx.x * a.max_rec + t] = r;
+        plog[t] = draw_plog(dl, lg[id], m_a);
+    }
+    return id;
+}
+
+
 // ---- beam step: the split kernels (256 threads, 16 logits a thread) ---------
 constexpr int SPLIT_U = 16;  // split length <= 4096
 

@@ -73,7 +73,7 @@ EXPORTS = (
     "wmi_set_best_of", "wmi_decode_timestamps_best_of", "wmi_best_of_key", "wmi_get_window_candidate",
     "wmi_set_prefill", "wmi_prefill_logits", "wmi_set_quant_gemm", "wmi_dequant_blocks",
     "wmi_set_batch_beam", "wmi_decode_timestamps_beam_rows", "wmi_decode_timestamps_ruled_beam_rows",
-    "wmi_set_wide_rounds",
+    "wmi_set_wide_rounds", "wmi_decode_timestamps_sampled_rows", "wmi_set_wide_fallback",
     "wmi_is_non_speech_token", "wmi_set_token_timestamps", "wmi_token_times",
     "wmi_set_dtw", "wmi_align_tokens", "wmi_dtw_path", "wmi_dtw_path_host", "wmi_get_segment_dtw_of",
     "wmi_audio_to_mel_batch", "wmi_stage_audio", "wmi_transcribe_audio", "wmi_transcribe_audio_batch", "wmi_get_pcm",
@@ -256,6 +256,10 @@ def lib():
             L.wmi_set_wide_rounds.argtypes = [vp, C.c_int]
         if hasattr(L, "wmi_decode_timestamps_ruled_beam_rows"):  # (as above: an older build has no ruled wide step)
             L.wmi_decode_timestamps_ruled_beam_rows.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+        if hasattr(L, "wmi_decode_timestamps_sampled_rows"):  # (as above: an older build has no sampled wide rows)
+            L.wmi_decode_timestamps_sampled_rows.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_uint64, vp,
+                                                             vp, vp, vp, vp, vp]
+            L.wmi_set_wide_fallback.argtypes = [vp, C.c_int]
         if hasattr(L, "wmi_set_token_timestamps"):  # (as above: an older build has no token-level timestamps)
             L.wmi_set_token_timestamps.argtypes = [vp, C.POINTER(TokenTsParams)]
             L.wmi_token_times.argtypes = [vp, vp, sz, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int]
@@ -660,6 +664,40 @@ class WhisperContext:
         fn = lib().wmi_decode_timestamps_ruled_beam_rows if ruled else lib().wmi_decode_timestamps_beam_rows
         _raise(fn(self._h, beam_size, _ptr(flat), stride, _ptr(lens), max_tokens, out, _ptr(n), _ptr(sc)), self._h)
         return [([out[c * max_tokens + i].as_dict() for i in range(n[c])], float(sc[c])) for c in range(self.n_clips)]
+
+    def set_wide_fallback(self, enable=1) -> None:
+        """1: transcribe_batch() on the wide decoder step (set_wide_rounds(), or
+        set_batch_beam(1) at a beam size above 1) takes the fallback and
+        best_of: a round is one beam window and one sampled window.  0, the
+        default: it refuses them there.  Neither: InvalidArgument."""
+        _raise(lib().wmi_set_wide_fallback(self._h, int(enable)), self._h)
+
+    def decode_timestamps_sampled_rows(self, best_of: int, prompts, max_tokens: int, temperatures, seed: int = 0,
+                                       n=None):
+        """decode_timestamps_best_of() for every encoded clip at once on the
+        wide decoder step, best_of row slots a clip: clip b after prompts[b] at
+        temperatures[b] (0: one candidate) as attempt ordinal n[b] of seed.
+        Per clip ([WhisperTokenData dict] of the chosen candidate, its
+        log-probabilities, no-speech probability, chosen index)."""
+        rows = [np.ascontiguousarray(p, dtype=np.int32).ravel() for p in prompts]
+        if len(rows) != self.n_clips or len(temperatures) != self.n_clips:
+            raise ValueError(f"{len(rows)} prompts / {len(temperatures)} temperatures for {self.n_clips} clips")
+        lens = np.array([r.size for r in rows], np.int32)
+        stride = max(1, int(lens.max()) if len(rows) else 1)
+        flat = np.zeros((max(1, len(rows)), stride), np.int32)
+        for b, r in enumerate(rows):
+            flat[b, :r.size] = r
+        nc = max(1, self.n_clips)
+        tt = np.ascontiguousarray(temperatures, dtype=np.float32)
+        nn = np.zeros(nc, np.int32) if n is None else np.ascontiguousarray(n, dtype=np.int32)
+        out = (TokenData * (nc * max_tokens))()
+        cnt, ch = np.zeros(nc, np.int32), np.zeros(nc, np.int32)
+        pl, ns = np.zeros((nc, max_tokens), np.float32), np.zeros(nc, np.float32)
+        _raise(lib().wmi_decode_timestamps_sampled_rows(self._h, best_of, _ptr(flat), stride, _ptr(lens), max_tokens,
+                                                        _ptr(tt), seed, _ptr(nn), out, _ptr(cnt), _ptr(pl), _ptr(ns),
+                                                        _ptr(ch)), self._h)
+        return [([out[c * max_tokens + i].as_dict() for i in range(cnt[c])], pl[c, :cnt[c]].copy(), float(ns[c]),
+                 int(ch[c])) for c in range(self.n_clips)]
 
     def wide_run(self):
         """Debug read 38: (B, K, steps, [p_c]) of the last wide run."""
