@@ -847,6 +847,32 @@ int wmi_set_dtw(wmi_context *ctx, const wmi_dtw_params *params);
  * pass overwrites the decoder's self-attention cache and step state. */
 int wmi_align_tokens(wmi_context *ctx, int clip, const int32_t *prompt, int n_prompt, const int32_t *text, int n_text,
                      int n_frames, int32_t *frames /* [n_text + 1] */);
+/* How an aligned pass feeds F.  mode 0 (default): one decoder step a position
+ * on the kernel chain, as stated above; every call runs exactly the kernels
+ * and code objects it ran before.  mode 1: the forced pass.  The windows of
+ * wmi_transcribe* under wmi_set_dtw and wmi_align_tokens send all p + n
+ * positions through the decoder layers at once (the MFMA pass of
+ * wmi_set_prefill, whatever that switch says, up to the last selected layer's
+ * cross-attention query), and a kernel of its own computes the selected heads'
+ * scores, whenever the file's decoder matrices are f16 or quantised (not f32)
+ * and p + n <= 256; otherwise the chain pass runs as under mode 0, silently.
+ * S1 under mode 1: s[a][i][j] is the f32 dot product, over the head's 64
+ * dims, of the pass's f16 query of position i (scaled, as the chain's) and the
+ * f16 key j, summed by four v_mfma_f32_32x32x16_f16 in ascending dims from
+ * zero.  These are NOT the chain's bits: the pass's activations differ from
+ * the step kernels' in the last places, as wmi_prefill_logits' do from
+ * wmi_decode_logits'.  S2 - S7 are unchanged and apply to that s.  The pass
+ * leaves the step state alone and overwrites rows of the self-attention
+ * cache.  Another mode: WMI_E_INVALID_ARG.  Holds until changed. */
+int wmi_set_dtw_pass(wmi_context *ctx, int mode);
+/* wmi_align_tokens for encoded clips clip0 .. clip0 + n_clips - 1 (n_clips <=
+ * 8) in one forced pass, in either mode: prompts and texts hold the clips' ids
+ * one behind the other (n_prompt[c], n_text[c] of clip c), frames the clips'
+ * f likewise ([sum(n_text[c] + 1)]).  wmi_align_tokens' errors apply per clip;
+ * WMI_E_UNSUPPORTED if a clip would need the chain pass (an f32 file, more
+ * than 256 positions). */
+int wmi_align_tokens_rows(wmi_context *ctx, int clip0, int n_clips, const int32_t *prompts, const int32_t *n_prompt,
+                          const int32_t *texts, const int32_t *n_text, const int32_t *n_frames, int32_t *frames);
 /* S6 alone, on the device and on the host (no context, no device): first[r] =
  * f[r].  rows or cols < 1, rows > 513 or cols > 1500: WMI_E_INVALID_ARG. */
 int wmi_dtw_path(wmi_context *ctx, const int32_t *cost, int rows, int cols, int32_t *first /* [rows] */);
@@ -1131,7 +1157,13 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * the row was idle).  40 / 41 = its parent slots and slot tokens, int32
  * [8][n_text_ctx][8] (recording, step, slot).  42 = the launches of the
  * quantised-weight GEMM since the context was created (int64, host; a replayed
- * wide-step graph counts the launches it holds). */
+ * wide-step graph counts the launches it holds).  25 / 26 / 27 after a pass of
+ * several recordings (wmi_align_tokens_rows) are its last recording's.  43 =
+ * with WMI_ALIGN_KEEP=1 in the environment when the context was created, the
+ * operands of the last forced pass (wmi_set_dtw_pass) for its last recording as
+ * the score kernel read them: f16 [A][p + n][64] query rows, then f16
+ * [A][T][64] key rows (WMI_E_INVALID_ARG without the variable, or when the
+ * last aligned pass was a chain pass). */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

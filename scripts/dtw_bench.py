@@ -15,9 +15,11 @@ host clock around calls that end synchronised.
     matrix (upload, k_dtw, the path's copy, one synchronise), against
     wmi_dtw_path_host.
 
+ 4. With --pass: the chain pass against the forced pass (forced_pass below).
+
 Prints one JSON line.
 
-Usage: dtw_bench.py [--model base] [--seconds 60] [--reps 5] [--max-tokens 220] [--n-top 2]   (needs the GPU)"""
+Usage: dtw_bench.py [--model base] [--seconds 60] [--reps 5] [--max-tokens 220] [--n-top 2] [--pass]   (needs the GPU)"""
 import argparse
 import json
 import os
@@ -36,6 +38,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--max-tokens", type=int, default=220)
     ap.add_argument("--n-top", type=int, default=2)
+    ap.add_argument("--pass", dest="forced_pass", action="store_true", help="also compare wmi_set_dtw_pass 0 and 1")
     a = ap.parse_args()
     import numpy as np
     import synth
@@ -112,7 +115,88 @@ def main():
         out[f"dtw_{name}_device_us_median"] = round(med(dev) * 1e6, 1)
         out[f"dtw_{name}_host_us_median"] = round(med(host) * 1e6, 1)
     ctx.close()
+    if a.forced_pass:
+        out["pass"] = forced_pass(a, rec, open_ctx, timed)
     print(json.dumps(out))
+
+
+def forced_pass(a, rec, open_ctx, timed):
+    """--pass: the chain pass (wmi_set_dtw_pass 0) against the forced pass (1),
+    alternated in one process: wmi_transcribe off / mode 0 / mode 1, the three
+    hipEvent intervals of either mode (a context with WMI_ALIGN_TIMING=1), the
+    windows' times in both modes, and wmi_align_tokens_rows at 8 clips against
+    8 wmi_align_tokens calls under mode 1, at 14 and at 60 positions a clip."""
+    import numpy as np
+    med = statistics.median
+    spread = lambda v: [round(min(v), 4), round(med(v), 4), round(max(v), 4)]
+    res = {}
+    ctx = open_ctx()
+
+    def transcribe(mode):
+        if mode is None:
+            ctx.set_dtw(default=True)
+        else:
+            ctx.set_dtw(n_top=a.n_top, medfilt_width=7)
+            ctx.set_dtw_pass(mode)
+        t, segs = timed(lambda: ctx.transcribe(rec, max_tokens=a.max_tokens))
+        return t, segs, [ctx.segment_dtw_of(0, i) for i in range(len(segs))]
+
+    first = {m: transcribe(m) for m in (None, 0, 1)}          # warm-up
+    windows = int(np.frombuffer(ctx.debug_read(20, 24), np.int64)[0])
+    tt = {None: [], 0: [], 1: []}
+    for _ in range(a.reps):
+        for m in (None, 0, 1):
+            tt[m].append(transcribe(m)[0] * 1e3)
+    ctx.close()
+    res["windows"] = windows
+    res["segments_equal"] = first[0][1] == first[1][1] == first[None][1]
+    t0, t1 = ([tm for sg in first[m][2] for tm in sg if tm != (-1, -1)] for m in (0, 1))
+    res["token_times"] = len(t0)
+    res["token_times_equal"] = sum(x == y for x, y in zip(t0, t1))
+    res["token_times_max_diff_10ms"] = max([abs(x[k] - y[k]) for x, y in zip(t0, t1) for k in (0, 1)], default=0)
+    for m, name in ((None, "off"), (0, "mode0"), (1, "mode1")):
+        res[f"transcribe_{name}_ms_min_med_max"] = spread(tt[m])
+    for m in (0, 1):
+        res[f"added_ms_per_window_mode{m}"] = round((med(tt[m]) - med(tt[None])) / max(1, windows), 3)
+
+    os.environ["WMI_ALIGN_TIMING"] = "1"
+    ctx = open_ctx()
+    del os.environ["WMI_ALIGN_TIMING"]
+    ctx.set_dtw(n_top=a.n_top, medfilt_width=7)
+    ms = {0: np.zeros(4), 1: np.zeros(4)}
+    for k in range(a.reps + 1):
+        for m in (0, 1):
+            ctx.set_dtw_pass(m)
+            before = np.frombuffer(ctx.debug_read(28, 32), np.float64).copy()
+            ctx.transcribe(rec, max_tokens=a.max_tokens)
+            if k:          # (k = 0: warm-up)
+                ms[m] += np.frombuffer(ctx.debug_read(28, 32), np.float64) - before
+    for m in (0, 1):
+        res[f"pass_forced_matrix_dtw_ms_mode{m}"] = [round(float(v) / max(1.0, float(ms[m][3])), 4) for v in ms[m][:3]]
+
+    ctx.close()
+    import synth
+    import wmi
+    ctx = wmi.WhisperContext.new(synth.model_path(a.model), 0, max_clips=8)
+    ctx.pcm_to_mel_batch([synth.synth_pcm_tones(30.0, 4000 + c) for c in range(8)])
+    ctx.encode(1, 0)
+    ctx.set_dtw(enable=False, n_top=a.n_top, medfilt_width=7)
+    ctx.set_dtw_pass(1)
+    sp, T = ctx.special, ctx.n_ctx
+    prompt = [sp["sot"], sp["sot"] + 1, sp["transcribe"], sp["not"]] if sp["multilingual"] else [sp["sot"], sp["not"]]
+    for n in (14 - len(prompt), 60 - len(prompt)):
+        texts = [[int(v) for v in np.random.default_rng(c).integers(300, 40000, n)] for c in range(8)]
+        single = lambda: [ctx.align_tokens(prompt, texts[c], T, clip=c) for c in range(8)]
+        rows = lambda: ctx.align_tokens_rows([prompt] * 8, texts, [T] * 8)
+        assert all(np.array_equal(x, y) for x, y in zip(single(), rows()))
+        ts, tr = [], []
+        for _ in range(a.reps):
+            ts.append(timed(single)[0] * 1e3)
+            tr.append(timed(rows)[0] * 1e3)
+        res[f"align_8_clips_{n + len(prompt)}_positions_single_calls_ms_min_med_max"] = spread(ts)
+        res[f"align_8_clips_{n + len(prompt)}_positions_rows_ms_min_med_max"] = spread(tr)
+    ctx.close()
+    return res
 
 
 if __name__ == "__main__":

@@ -31,6 +31,7 @@
 #include "wmi_host.h"
 #include "wmi_internal.h"
 #include "wmi_gemm_q.h"
+#include "wmi_align_pass.h"
 
 #pragma clang fp contract(off)
 
@@ -281,6 +282,15 @@ struct wmi_context {
     int al_last[5] = {0, 0, 0, 0, 0};   // A, p + n, T, n, M of the last pass (debug reads 25 - 27)
     hipEvent_t al_ev[4] = {};           // WMI_ALIGN_TIMING=1: around a pass's steps, matrix kernels and DTW
     double al_ms[4] = {0, 0, 0, 0};     // their summed ms and the passes counted (debug read 28)
+    // the forced pass (wmi_set_dtw_pass, wmi_align_tokens_rows; wmi_align_pass.hip): its recordings' blocks of s, w,
+    // Cq and the trace lie one behind the other in the buffers above, their paths in al_rows_f [DEC_ROWS][AL_ROWS_MAX]
+    int al_pass_mode = 0;
+    int32_t *al_rows_f = nullptr;
+    const float *al_last_s = nullptr;   // the last recording of the last pass (debug reads 25 - 27)
+    const int32_t *al_last_cq = nullptr, *al_last_f = nullptr;
+    bool al_keep_on = false;            // WMI_ALIGN_KEEP=1: the last forced pass's operands (debug read 43)
+    uint16_t *al_keep = nullptr;
+    size_t al_keep_cap = 0, al_keep_have = 0;  // halfs
     // per recording of the last transcribe (one) / transcribe_batch
     std::vector<SegList> results = std::vector<SegList>(1);
     std::vector<int32_t> ts_prompt;     // prompt rows of the last timestamp window, [rows][np] (debug read 19; ragged rows:
@@ -2392,8 +2402,16 @@ bool prefill_on(const wmi_context *ctx, int np) {
 // the pass ends behind the last layer's QKV product (nothing later is read by a step); with it the final LayerNorm
 // and the vocabulary product follow, into pf_logits [M][n_vocab].
 // kbase / vbase: the cache the pass writes, [L][cache_rows][tctx][n] (null: the context's 8-row caches).
+// cross_q (the forced pass of the alignment, al_pass_rows): called behind the store of every layer's cross-attention
+// query with the layer and the numbered recordings; the pass then does not end at the last layer's QKV product, and
+// ends behind the call that sets *last (nothing later is read).  Null: every launch is what it was.
+struct PfCrossQHook {
+    int (*fn)(wmi_context *ctx, void *arg, int l, const PfRecs &recs, bool *last);
+    void *arg;
+};
 int prefill_pass(wmi_context *ctx, PfRecs recs, int feed_stride, bool logits, uint16_t *kbase = nullptr,
-                 uint16_t *vbase = nullptr, int cache_rows = DEC_ROWS, const int32_t *feed = nullptr) {
+                 uint16_t *vbase = nullptr, int cache_rows = DEC_ROWS, const int32_t *feed = nullptr,
+                 const PfCrossQHook *cross_q = nullptr) {
     const wmi_hparams &hp = ctx->hp;
     const int n = hp.n_text_state, H = hp.n_text_head, T = ctx->enc_T, Bt = ctx->enc_clips, tctx = hp.n_text_ctx;
     int M = 0;
@@ -2431,7 +2449,7 @@ int prefill_pass(wmi_context *ctx, PfRecs recs, int feed_stride, bool logits, ui
         qa.v = (vbase ? vbase : ctx->vcache) + (size_t)l * cache_rows * tctx * n;
         qa.M = M; qa.N = 3 * n; qa.n = n; qa.qscale = qs;
         HIPCHK(ctx, launch_pf_qkv_store(s, qa));
-        if (!logits && l == ctx->dec_layers - 1) break;
+        if (!logits && !cross_q && l == ctx->dec_layers - 1) break;
         at.K = qa.k; at.V = qa.v;
         HIPCHK(ctx, launch_pf_self_attn(s, at));
         g = gemm(ctx->pf_att16, n, d.wo, d.bo, n);
@@ -2443,6 +2461,11 @@ int prefill_pass(wmi_context *ctx, PfRecs recs, int feed_stride, bool logits, ui
         HIPCHK(ctx, dense_product(ctx, s, EPI_F32, g, ql ? &ql->wcq : nullptr));
         qa.bias = d.bcq; qa.N = n;  // (the q part alone)
         HIPCHK(ctx, launch_pf_qkv_store(s, qa));
+        if (cross_q) {
+            bool last = false;
+            rc = cross_q->fn(ctx, cross_q->arg, l, recs, &last);
+            if (rc || last) return rc;
+        }
         at.K = ctx->ck + (size_t)l * Bt * T * n; at.V = ctx->cv + (size_t)l * Bt * T * n;
         HIPCHK(ctx, launch_pf_cross_attn(s, at));
         g = gemm(ctx->pf_att16, n, d.wco, d.bco, n);
@@ -2984,8 +3007,9 @@ int tt_energy_of_clips(wmi_context *ctx, int n_clips) {
 
 // ---- token times from cross-attention alignment (wmi_set_dtw) --------------------
 // the cost matrix, the trace and the small words of a DTW over R x M
-int al_ensure_dtw(wmi_context *ctx, int R, int M) {
-    const size_t cells = (size_t)R * (size_t)M, tb = dtw_trace_bytes(R, M);
+int al_ensure_dtw(wmi_context *ctx, int R, int M, size_t cells = 0, size_t tb = 0) {
+    // (a forced pass of several recordings gives the sums of its matrices' cells and trace bytes)
+    if (!cells) { cells = (size_t)R * (size_t)M; tb = dtw_trace_bytes(R, M); }
     if (cells > ctx->al_cq_cap) {
         if (ctx->al_cq) HIPCHK(ctx, hipFree(ctx->al_cq));
         ctx->al_cq = nullptr; ctx->al_cq_cap = 0;
@@ -3003,18 +3027,8 @@ int al_ensure_dtw(wmi_context *ctx, int R, int M) {
     return WMI_OK;
 }
 
-// S1 - S6 for the clip in encoder slot `slot`: F = P ++ x (p + n ids) teacher-
-// forced on the kernel chain with the capture behind every selected layer's
-// cross-attention, the matrix kernels, the DTW; frames[0 .. n] = f.  One
-// synchronisation, at the end.  The pass leaves the self-attention cache, the
-// step state and the feed as a forced run of F does.
-int al_pass(wmi_context *ctx, int slot, const std::vector<int32_t> &F, int p, int M, int32_t *frames) {
-    const int A = (int)ctx->al_heads.size() / 2, Np = (int)F.size(), n = Np - p, T = ctx->enc_T, R = n + 1;
-    if (A < 1) return set_err(ctx, WMI_E_INVALID_ARG, "no (layer, head) pairs set (wmi_set_dtw)");
-    if (T > AL_COLS_MAX || R > AL_ROWS_MAX)
-        return set_err(ctx, WMI_E_UNSUPPORTED, "alignment takes at most %d frames and %d text tokens (%d, %d)", AL_COLS_MAX,
-                       AL_ROWS_MAX - 1, T, n);
-    const size_t need = (size_t)A * (size_t)Np * (size_t)T;
+// s [A][p + n][T] and, al_cap floats behind it, w: `need` floats each
+int al_ensure_scores(wmi_context *ctx, size_t need) {
     if (need > ctx->al_cap) {  // (the captured steps hold the buffer's address)
         if (ctx->al_s) HIPCHK(ctx, hipFree(ctx->al_s));
         ctx->al_s = nullptr; ctx->al_cap = 0;
@@ -3022,7 +3036,178 @@ int al_pass(wmi_context *ctx, int slot, const std::vector<int32_t> &F, int p, in
         ctx->al_cap = 2 * need;
         ctx->clear_graphs();
     }
-    int rc = al_ensure_dtw(ctx, R, M);
+    return WMI_OK;
+}
+
+void al_add_timing(wmi_context *ctx) {
+    for (int k = 0; k < 3; ++k) {
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, ctx->al_ev[k], ctx->al_ev[k + 1]);
+        ctx->al_ms[k] += (double)ms;
+    }
+    ctx->al_ms[3] += 1.0;
+}
+
+// ---- the forced pass (wmi_set_dtw_pass, wmi_align_tokens_rows; DESIGN.md "Token times in one forced pass") ----
+// one recording of a pass: encoder slot clip, F = P ++ x (Np ids, the first p the prompt), M frames, frames [Np - p + 1]
+struct AlRec {
+    int clip;
+    const int32_t *F;
+    int Np, p, M;
+    int32_t *frames;
+};
+
+// the forced pass takes a recording of Np positions (else the chain pass)
+bool al_pass_fits(const wmi_context *ctx, int Np) { return !ctx->wf32 && Np <= PF_MAX_KEYS; }
+
+struct AlHook {
+    AlPassArgs pa;
+    int last_layer;
+    int keep_np;  // positions of the last recording (WMI_ALIGN_KEEP)
+};
+
+// behind the store of layer l's cross-attention query: the scores of the layer's selected heads, and under
+// WMI_ALIGN_KEEP the last recording's operands as the kernel read them (strided device-to-device copies)
+int al_cross_q(wmi_context *ctx, void *arg, int l, const PfRecs &recs, bool *last) {
+    AlHook &hk = *(AlHook *)arg;
+    AlPassArgs &pa = hk.pa;
+    const int n = pa.n, T = pa.T, A = pa.A;
+    pa.nh = 0;
+    for (int k = 0; k < A; ++k)
+        if (ctx->al_heads[2 * k] == l) {
+            pa.head[pa.nh] = (int16_t)ctx->al_heads[2 * k + 1];
+            pa.slot[pa.nh++] = (int16_t)k;
+        }
+    *last = l >= hk.last_layer;
+    if (!pa.nh) return WMI_OK;
+    pa.recs = recs;
+    pa.K = ctx->ck + (size_t)l * ctx->enc_clips * T * n;
+    HIPCHK(ctx, launch_align_scores(ctx->stream, pa));
+    if (ctx->al_keep_on) {
+        const PfRec &rec = recs.r[recs.n - 1];
+        const int Np = hk.keep_np;
+        for (int g = 0; g < pa.nh; ++g) {
+            uint16_t *qd = ctx->al_keep + (size_t)pa.slot[g] * Np * 64;
+            uint16_t *kd = ctx->al_keep + (size_t)A * Np * 64 + (size_t)pa.slot[g] * T * 64;
+            HIPCHK(ctx, hipMemcpy2DAsync(qd, 128, pa.q + (size_t)rec.row0 * n + pa.head[g] * 64, (size_t)n * 2, 128, Np,
+                                         hipMemcpyDeviceToDevice, ctx->stream));
+            HIPCHK(ctx, hipMemcpy2DAsync(kd, 128, pa.K + (size_t)rec.clip * T * n + pa.head[g] * 64, (size_t)n * 2, 128, T,
+                                         hipMemcpyDeviceToDevice, ctx->stream));
+        }
+    }
+    return WMI_OK;
+}
+
+// S1 - S6 for nr <= DEC_ROWS recordings in one pass: every F through prefill_pass (cache row r, no logits) as far
+// as the last selected layer's cross-attention query, k_align_scores behind the query of every layer that has a
+// selected head, then per recording the matrix kernels and the DTW on its own blocks.  One synchronisation, at the
+// end.  The self-attention cache rows and the feed are what the pass left; the step state is untouched.
+int al_pass_rows(wmi_context *ctx, const AlRec *rs, int nr) {
+    const wmi_hparams &hp = ctx->hp;
+    const int A = (int)ctx->al_heads.size() / 2, T = ctx->enc_T;
+    if (A < 1) return set_err(ctx, WMI_E_INVALID_ARG, "no (layer, head) pairs set (wmi_set_dtw)");
+    if (nr < 1 || nr > DEC_ROWS) return set_err(ctx, WMI_E_INVALID_ARG, "%d recordings in a forced pass", nr);
+    if (T > AL_COLS_MAX) return set_err(ctx, WMI_E_UNSUPPORTED, "alignment takes at most %d frames (%d)", AL_COLS_MAX, T);
+    AlHook hk{};
+    size_t need = 0, cells = 0, tb = 0, cq_off[DEC_ROWS], tb_off[DEC_ROWS];
+    int np_max = 0;
+    for (int r = 0; r < nr; ++r) {
+        const int R = rs[r].Np - rs[r].p + 1;
+        if (!al_pass_fits(ctx, rs[r].Np) || rs[r].p < 1 || R < 2 || rs[r].M < 1 || rs[r].M > T || rs[r].clip < 0 ||
+            rs[r].clip >= ctx->enc_clips)
+            return set_err(ctx, WMI_E_INVALID_ARG, "internal: recording %d does not fit a forced pass", r);
+        hk.pa.off[r] = (int64_t)need;
+        cq_off[r] = cells;
+        tb_off[r] = tb;
+        need += (size_t)A * rs[r].Np * T;
+        cells += (size_t)R * rs[r].M;
+        tb += dtw_trace_bytes(R, rs[r].M);
+        np_max = std::max(np_max, rs[r].Np);
+    }
+    int rc = al_ensure_scores(ctx, need);
+    if (rc) return rc;
+    rc = al_ensure_dtw(ctx, 0, 0, cells, tb);
+    if (rc) return rc;
+    if (!ctx->al_rows_f) HIPCHK(ctx, hipMalloc(&ctx->al_rows_f, (size_t)DEC_ROWS * AL_ROWS_MAX * 4));
+    rc = ensure_decode_buffers(ctx, DEC_ROWS * np_max, 1);
+    if (rc) return rc;
+    const AlRec &lr = rs[nr - 1];
+    const size_t keep = (size_t)A * ((size_t)lr.Np + T) * 64;
+    if (ctx->al_keep_on && keep > ctx->al_keep_cap) {
+        if (ctx->al_keep) HIPCHK(ctx, hipFree(ctx->al_keep));
+        ctx->al_keep = nullptr; ctx->al_keep_cap = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->al_keep, 2 * keep * 2));
+        ctx->al_keep_cap = 2 * keep;
+    }
+    PfRecs recs{};
+    recs.n = nr;
+    for (int r = 0; r < nr; ++r) {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->dfeed + (size_t)r * np_max, rs[r].F, (size_t)rs[r].Np * 4, hipMemcpyHostToDevice,
+                                   ctx->stream));
+        recs.r[r].slot = r;
+        recs.r[r].clip = rs[r].clip;
+        recs.r[r].len = rs[r].Np;
+    }
+    hk.pa.s = ctx->al_s;
+    hk.pa.n = hp.n_text_state; hk.pa.H = hp.n_text_head; hk.pa.T = T; hk.pa.A = A;
+    hk.keep_np = lr.Np;
+    for (int k = 0; k < A; ++k) hk.last_layer = std::max(hk.last_layer, (int)ctx->al_heads[2 * k]);
+    int rows = 0;
+    for (int r = 0; r < nr; ++r) rows += rs[r].Np;
+    rc = ensure_pf_buffers(ctx, rows, false);
+    if (rc) return rc;
+    hk.pa.q = ctx->pf_q16;  // (the pass's buffers are there: prefill_pass will not move them)
+    const PfCrossQHook hook{al_cross_q, &hk};
+    const bool timed = ctx->al_ev[0] != nullptr;
+    hipStream_t s = ctx->stream;
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->al_ev[0], s));
+    rc = prefill_pass(ctx, recs, np_max, false, nullptr, nullptr, DEC_ROWS, nullptr, &hook);
+    if (rc) return rc;
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->al_ev[1], s));
+    for (int r = 0; r < nr; ++r) {
+        AlMatArgs ma{};
+        ma.s = ctx->al_s + hk.pa.off[r]; ma.w = ctx->al_s + ctx->al_cap + hk.pa.off[r]; ma.cq = ctx->al_cq + cq_off[r];
+        ma.A = A; ma.Np = rs[r].Np; ma.T = T; ma.M = rs[r].M; ma.p = rs[r].p; ma.n = rs[r].Np - rs[r].p; ma.width = ctx->al_width;
+        HIPCHK(ctx, launch_align_cost(s, ma));
+    }
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->al_ev[2], s));
+    for (int r = 0; r < nr; ++r)
+        HIPCHK(ctx, launch_dtw(s, ctx->al_cq + cq_off[r], rs[r].Np - rs[r].p + 1, rs[r].M, ctx->al_trace + tb_off[r],
+                               ctx->al_rows_f + (size_t)r * AL_ROWS_MAX));
+    if (timed) HIPCHK(ctx, hipEventRecord(ctx->al_ev[3], s));
+    for (int r = 0; r < nr; ++r)
+        HIPCHK(ctx, hipMemcpyAsync(rs[r].frames, ctx->al_rows_f + (size_t)r * AL_ROWS_MAX, (size_t)(rs[r].Np - rs[r].p + 1) * 4,
+                                   hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    const int last[5] = {A, lr.Np, T, lr.Np - lr.p, lr.M};
+    memcpy(ctx->al_last, last, sizeof last);
+    ctx->al_last_s = ctx->al_s + hk.pa.off[nr - 1];
+    ctx->al_last_cq = ctx->al_cq + cq_off[nr - 1];
+    ctx->al_last_f = ctx->al_rows_f + (size_t)(nr - 1) * AL_ROWS_MAX;
+    ctx->al_keep_have = ctx->al_keep_on ? keep : 0;
+    if (timed) al_add_timing(ctx);
+    return WMI_OK;
+}
+
+// S1 - S6 for the clip in encoder slot `slot`: F = P ++ x (p + n ids) teacher-
+// forced on the kernel chain with the capture behind every selected layer's
+// cross-attention, the matrix kernels, the DTW; frames[0 .. n] = f.  One
+// synchronisation, at the end.  The pass leaves the self-attention cache, the
+// step state and the feed as a forced run of F does.  Under wmi_set_dtw_pass(1)
+// a recording the forced pass takes goes through al_pass_rows instead.
+int al_pass(wmi_context *ctx, int slot, const std::vector<int32_t> &F, int p, int M, int32_t *frames) {
+    const int A = (int)ctx->al_heads.size() / 2, Np = (int)F.size(), n = Np - p, T = ctx->enc_T, R = n + 1;
+    if (A < 1) return set_err(ctx, WMI_E_INVALID_ARG, "no (layer, head) pairs set (wmi_set_dtw)");
+    if (T > AL_COLS_MAX || R > AL_ROWS_MAX)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "alignment takes at most %d frames and %d text tokens (%d, %d)", AL_COLS_MAX,
+                       AL_ROWS_MAX - 1, T, n);
+    if (ctx->al_pass_mode == 1 && al_pass_fits(ctx, Np)) {  // (else the chain pass, silently)
+        const AlRec rec{slot, F.data(), Np, p, M, frames};
+        return al_pass_rows(ctx, &rec, 1);
+    }
+    int rc = al_ensure_scores(ctx, (size_t)A * (size_t)Np * (size_t)T);
+    if (rc) return rc;
+    rc = al_ensure_dtw(ctx, R, M);
     if (rc) return rc;
     rc = ensure_decode_buffers(ctx, Np, 1);
     if (rc) return rc;
@@ -3049,14 +3234,9 @@ int al_pass(wmi_context *ctx, int slot, const std::vector<int32_t> &F, int p, in
     if (rc) return rc == RERUN_ON_CHAIN ? set_err(ctx, WMI_E_HIP, "internal: an aligned pass ran off the kernel chain") : rc;
     const int last[5] = {A, Np, T, n, M};
     memcpy(ctx->al_last, last, sizeof last);
-    if (timed) {
-        for (int k = 0; k < 3; ++k) {
-            float ms = 0.0f;
-            (void)hipEventElapsedTime(&ms, ctx->al_ev[k], ctx->al_ev[k + 1]);
-            ctx->al_ms[k] += (double)ms;
-        }
-        ctx->al_ms[3] += 1.0;
-    }
+    ctx->al_last_s = ctx->al_s; ctx->al_last_cq = ctx->al_cq; ctx->al_last_f = ctx->al_small + 4;
+    ctx->al_keep_have = 0;
+    if (timed) al_add_timing(ctx);
     return WMI_OK;
 }
 
@@ -4544,6 +4724,7 @@ static int wmi_init_from_file_impl(const char *path, int device, int max_clips, 
     }
     if (const char *c = getenv("WMI_ALIGN_TIMING"); c && atoi(c))
         for (hipEvent_t &e : ctx->al_ev) HIPCHK(ctx.get(), hipEventCreate(&e));
+    if (const char *c = getenv("WMI_ALIGN_KEEP"); c && atoi(c)) ctx->al_keep_on = true;
     if (getenv("WMI_PTRACE")) {
         const size_t nb = (size_t)hp_ptrace_slots(ctx->hp) * 8;
         HIPCHK(ctx.get(), hipMalloc(&ctx->d_ptrace, nb));
@@ -4590,6 +4771,8 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->al_cq) (void)hipFree(ctx->al_cq);
     if (ctx->al_trace) (void)hipFree(ctx->al_trace);
     if (ctx->al_small) (void)hipFree(ctx->al_small);
+    if (ctx->al_rows_f) (void)hipFree(ctx->al_rows_f);
+    if (ctx->al_keep) (void)hipFree(ctx->al_keep);
     for (hipEvent_t e : ctx->al_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->d_mel) (void)hipFree(ctx->d_mel);
     if (ctx->dfeed) (void)hipFree(ctx->dfeed);
@@ -5389,6 +5572,58 @@ int wmi_align_tokens(wmi_context *ctx, int clip, const int32_t *prompt, int n_pr
     return guarded(ctx, [&] { return wmi_align_tokens_impl(ctx, clip, prompt, n_prompt, text, n_text, n_frames, frames); });
 }
 
+int wmi_set_dtw_pass(wmi_context *ctx, int mode) {
+    return guarded(ctx, [&] {
+        if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+        if (mode != 0 && mode != 1) return set_err(ctx, WMI_E_INVALID_ARG, "dtw pass mode %d outside {0, 1}", mode);
+        ctx->al_pass_mode = mode;
+        return (int)WMI_OK;
+    });
+}
+
+static int wmi_align_tokens_rows_impl(wmi_context *ctx, int clip0, int n_clips, const int32_t *prompts, const int32_t *n_prompt,
+                                      const int32_t *texts, const int32_t *n_text, const int32_t *n_frames, int32_t *frames) {
+    if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
+    if (n_clips < 1 || n_clips > DEC_ROWS) return set_err(ctx, WMI_E_INVALID_ARG, "%d clips outside [1, %d]", n_clips, DEC_ROWS);
+    if (!prompts || !n_prompt || !texts || !n_text || !n_frames || !frames) return set_err(ctx, WMI_E_INVALID_ARG, "null pointer");
+    if (ctx->enc_T <= 0) return set_err(ctx, WMI_E_INVALID_ARG, "align before encode");
+    if (clip0 < 0 || clip0 + n_clips > ctx->enc_clips)
+        return set_err(ctx, WMI_E_INVALID_ARG, "clips [%d, %d) outside the %d encoded clips", clip0, clip0 + n_clips, ctx->enc_clips);
+    std::vector<int32_t> F[DEC_ROWS];
+    AlRec rs[DEC_ROWS];
+    bool chain = ctx->wf32;
+    for (int c = 0; c < n_clips; ++c) {
+        if (n_prompt[c] < 1 || n_text[c] < 1)
+            return set_err(ctx, WMI_E_INVALID_ARG, "clip %d: %d prompt / %d text ids", c, n_prompt[c], n_text[c]);
+        if ((int64_t)n_prompt[c] + n_text[c] > ctx->hp.n_text_ctx)
+            return set_err(ctx, WMI_E_INVALID_ARG, "clip %d: %d + %d ids above n_text_ctx %d", c, n_prompt[c], n_text[c],
+                           ctx->hp.n_text_ctx);
+        if (n_frames[c] < 1 || n_frames[c] > ctx->enc_T)
+            return set_err(ctx, WMI_E_INVALID_ARG, "clip %d: %d frames outside [1, %d]", c, n_frames[c], ctx->enc_T);
+        F[c].assign(prompts, prompts + n_prompt[c]);
+        F[c].insert(F[c].end(), texts, texts + n_text[c]);
+        for (int32_t id : F[c])
+            if (id < 0 || id >= ctx->hp.n_vocab) return set_err(ctx, WMI_E_INVALID_ARG, "clip %d: token id %d", c, id);
+        chain = chain || (int)F[c].size() > PF_MAX_KEYS;
+        rs[c] = AlRec{clip0 + c, F[c].data(), (int)F[c].size(), n_prompt[c], n_frames[c], frames};
+        prompts += n_prompt[c];
+        texts += n_text[c];
+        frames += n_text[c] + 1;
+    }
+    if (chain)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "a forced pass takes an f16 or quantised file and at most %d positions a clip",
+                       PF_MAX_KEYS);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return al_pass_rows(ctx, rs, n_clips);
+}
+
+int wmi_align_tokens_rows(wmi_context *ctx, int clip0, int n_clips, const int32_t *prompts, const int32_t *n_prompt,
+                          const int32_t *texts, const int32_t *n_text, const int32_t *n_frames, int32_t *frames) {
+    return guarded(ctx, [&] {
+        return wmi_align_tokens_rows_impl(ctx, clip0, n_clips, prompts, n_prompt, texts, n_text, n_frames, frames);
+    });
+}
+
 static int wmi_dtw_path_impl(wmi_context *ctx, const int32_t *cost, int rows, int cols, int32_t *first) {
     if (!valid(ctx)) return set_err(ctx, WMI_E_INVALID_ARG, "null or uninitialised context");
     if (!cost || !first || rows < 1 || rows > AL_ROWS_MAX || cols < 1 || cols > AL_COLS_MAX)
@@ -6173,9 +6408,13 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
         case 26:  // ... its cost matrix Cq, int32 [n + 1][M]
         case 27:  // ... and its path f, int32 [n + 1]
             if (!ctx->al_last[0]) return WMI_E_INVALID_ARG;
-            if (which == 25) { src = ctx->al_s; have = (size_t)ctx->al_last[0] * ctx->al_last[1] * ctx->al_last[2] * 4; }
-            else if (which == 26) { src = ctx->al_cq; have = ((size_t)ctx->al_last[3] + 1) * ctx->al_last[4] * 4; }
-            else { src = ctx->al_small + 4; have = ((size_t)ctx->al_last[3] + 1) * 4; }
+            if (which == 25) { src = ctx->al_last_s; have = (size_t)ctx->al_last[0] * ctx->al_last[1] * ctx->al_last[2] * 4; }
+            else if (which == 26) { src = ctx->al_last_cq; have = ((size_t)ctx->al_last[3] + 1) * ctx->al_last[4] * 4; }
+            else { src = ctx->al_last_f; have = ((size_t)ctx->al_last[3] + 1) * 4; }
+            break;
+        case 43:  // WMI_ALIGN_KEEP: the last forced pass's operands for its last recording, f16 [A][p + n][64] then [A][T][64]
+            if (!ctx->al_keep_on || !ctx->al_keep_have) return WMI_E_INVALID_ARG;
+            src = ctx->al_keep; have = ctx->al_keep_have * 2;
             break;
         case 28: {  // host: WMI_ALIGN_TIMING's summed ms of the passes' steps, matrix kernels and DTW, and the passes, double [4]
             memcpy(out, ctx->al_ms, std::min(sizeof ctx->al_ms, bytes));

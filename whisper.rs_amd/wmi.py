@@ -76,6 +76,7 @@ EXPORTS = (
     "wmi_set_wide_rounds", "wmi_decode_timestamps_sampled_rows", "wmi_set_wide_fallback",
     "wmi_is_non_speech_token", "wmi_set_token_timestamps", "wmi_token_times",
     "wmi_set_dtw", "wmi_align_tokens", "wmi_dtw_path", "wmi_dtw_path_host", "wmi_get_segment_dtw_of",
+    "wmi_set_dtw_pass", "wmi_align_tokens_rows",
     "wmi_audio_to_mel_batch", "wmi_stage_audio", "wmi_transcribe_audio", "wmi_transcribe_audio_batch", "wmi_get_pcm",
     "wmi_get_audio_timing", "wmi_resample_plan", "wmi_resample_taps", "wmi_resampled_length",
     "wmi_set_chunking", "wmi_set_chunk_spans", "wmi_get_chunk_count", "wmi_get_chunk", "wmi_plan_chunks",
@@ -279,6 +280,9 @@ def lib():
             L.wmi_dtw_path.argtypes = [vp, vp, C.c_int, C.c_int, vp]
             L.wmi_dtw_path_host.argtypes = [vp, C.c_int, C.c_int, vp]
             L.wmi_get_segment_dtw_of.argtypes = [vp, C.c_int, C.c_int, vp, sz, C.POINTER(i32)]
+        if hasattr(L, "wmi_set_dtw_pass"):  # (as above: an older build has no forced pass)
+            L.wmi_set_dtw_pass.argtypes = [vp, C.c_int]
+            L.wmi_align_tokens_rows.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
         if hasattr(L, "wmi_set_chunking"):  # (as above: an older build has no chunking)
             L.wmi_set_chunking.argtypes = [vp, C.POINTER(ChunkParams)]
             L.wmi_set_chunk_spans.argtypes = [vp, C.c_int, vp, C.c_int]
@@ -951,6 +955,25 @@ class WhisperContext:
         _raise(lib().wmi_align_tokens(self._h, clip, _ptr(prompt) if prompt.size else None, prompt.size,
                                       _ptr(text) if text.size else None, text.size, int(n_frames), _ptr(out)), self._h)
         return out
+
+    def set_dtw_pass(self, mode: int) -> None:
+        """How an aligned pass feeds its tokens (wmi_set_dtw_pass): 0 the chain
+        pass, a decoder step a position (default); 1 the forced pass, all
+        positions at once, where the file and the length allow it."""
+        _raise(lib().wmi_set_dtw_pass(self._h, int(mode)), self._h)
+
+    def align_tokens_rows(self, prompts, texts, n_frames, clip0: int = 0):
+        """align_tokens() for the encoded clips clip0 .. in one forced pass
+        (wmi_align_tokens_rows): a list of int32 [len(text) + 1], one a clip."""
+        n_p = np.array([len(p) for p in prompts], np.int32)
+        n_t = np.array([len(t) for t in texts], np.int32)
+        flat_p = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int32) for p in prompts] + [np.zeros(1, np.int32)]))
+        flat_t = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int32) for t in texts] + [np.zeros(1, np.int32)]))
+        n_f = np.ascontiguousarray(n_frames, dtype=np.int32)
+        out = np.full(int(n_t.sum()) + len(texts) + 1, -1, np.int32)
+        _raise(lib().wmi_align_tokens_rows(self._h, clip0, len(texts), _ptr(flat_p), _ptr(n_p), _ptr(flat_t), _ptr(n_t),
+                                           _ptr(n_f), _ptr(out)), self._h)
+        return [a.copy() for a in np.split(out[:-1], np.cumsum(n_t + 1)[:-1])]
 
     def dtw_path(self, cost):
         """S6 on the device (wmi_dtw_path): cost int32 [rows][cols] -> the
