@@ -619,6 +619,44 @@ int wmi_prefill_logits(wmi_context *ctx, int clip, const int32_t *tokens, int n_
 int wmi_set_quant_gemm(wmi_context *ctx, int enable);
 int wmi_dequant_blocks(int type, const void *raw, int64_t nel, uint16_t *out_f16);
 
+/* MXFP8 cross-attention keys and values for the wide decoder step.  With
+ * wmi_set_cross_fp8(ctx, 1) every encode from the next one on quantises the
+ * cross keys and values it produced: per block of 32 consecutive elements
+ * along the state dimension of a key or value row, a shared exponent s, the
+ * smallest integer in [-15, 7] with amax * 2^-s <= 448 (an all-zero block:
+ * -15), stored as the byte s + 127 (E8M0), and the elements x * 2^-s rounded
+ * to nearest even into OCP e4m3fn, saturated at +-448.  Every e4m3 * 2^s of
+ * that range is an f16 number, and the quantiser writes these values, the
+ * rendering, back over the f16 keys and values: the context holds one set of
+ * cross K/V values, wmi_get_cross_kv returns them, and every decoder path reads
+ * them.  The wide step (wmi_decode_timestamps_beam_rows and its kin, the batch
+ * calls under wmi_set_batch_beam / wmi_set_wide_rounds) reads the 8-bit planes
+ * instead, 66 bytes a key and head where the f16 planes are 128, on kernels of
+ * its own (wmi_cross_fp8.hip): k_wd_cross_attn1_f8 at one hypothesis a
+ * recording, whatever wmi_set_wide_rounds says, and k_wd_cross_attn_f8 at two
+ * and more; debug read 44 names the last wide run's kernel.  The option
+ * changes values (keys and values keep 4 significant bits), and it costs
+ * memory: the f16 planes stay, so cross K/V take about 52 % more, allocated
+ * for max_clips clips with the first switch-on, which also drops the cached
+ * wide-step graphs.  0 (the default): the next encode leaves plain f16 again
+ * and every call launches what it launched before this interface.  An f32
+ * file: WMI_E_UNSUPPORTED.  enable outside {0, 1} or a null context:
+ * WMI_E_INVALID_ARG.  What was measured is in DESIGN.md, "MXFP8 cross keys and
+ * values".
+ * wmi_get_cross_kv_fp8: the planes of encoded clip `clip` in canonical order,
+ * k8 / v8 [n_text_layer][n_ctx][n_text_state] e4m3 bytes (cap: their size) and
+ * k_scale / v_scale [n_text_layer][n_ctx][n_text_state / 32] scale bytes,
+ * whatever the device layout; WMI_E_INVALID_ARG unless the last encode ran
+ * under the option.
+ * wmi_fp8_quantise: the same quantiser kernel over a caller's host array
+ * f16_in [rows][n] (f16 bits, finite; n a multiple of 32): q_out [rows][n],
+ * scale_out [rows][n / 32], f16_rendered_out [rows][n]. */
+int wmi_set_cross_fp8(wmi_context *ctx, int enable);
+int wmi_get_cross_kv_fp8(const wmi_context *ctx, int clip, uint8_t *k8, uint8_t *v8, uint8_t *k_scale, uint8_t *v_scale,
+                         size_t cap);
+int wmi_fp8_quantise(wmi_context *ctx, const uint16_t *f16_in, int rows, int n, uint8_t *q_out, uint8_t *scale_out,
+                     uint16_t *f16_rendered_out);
+
 /* OpenAI's decoding rules (SuppressTokens and ApplyTimestampRules restated)
  * for every window of wmi_transcribe / wmi_transcribe_batch and for
  * wmi_decode_timestamps_ruled, in the place of the whisper.cpp-1.0.3 rule.
@@ -1163,7 +1201,9 @@ int wmi_get_checksums(const wmi_context *ctx, float *out5);
  * operands of the last forced pass (wmi_set_dtw_pass) for its last recording as
  * the score kernel read them: f16 [A][p + n][64] query rows, then f16
  * [A][T][64] key rows (WMI_E_INVALID_ARG without the variable, or when the
- * last aligned pass was a chain pass). */
+ * last aligned pass was a chain pass).  44: host, int32, the cross-attention
+ * kernel of the last wide run: 0 none yet, 1 k_wd_cross_attn, 2
+ * k_wd_cross_attn1, 3 k_wd_cross_attn_f8, 4 k_wd_cross_attn1_f8. */
 int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes);
 
 /* ---- parity getters (copy device results into caller-owned buffers) --- */

@@ -195,6 +195,13 @@ struct wmi_context {
     // The table's blocks and the rule block hold wd_tab_recs / wd_rt_recs recordings: 8 until a round asks for more
     int wide_rows = 0;
     int wd_tab_recs = 0, wd_rt_recs = 0;
+    // MXFP8 cross keys and values (wmi_set_cross_fp8; wmi_cross_fp8.hip).  The planes come with the first switch-on,
+    // one allocation for max_clips clips of n_audio_ctx keys: payload K, payload V, scales K, scales V.  f8_live: the
+    // last encode ran under the option, so ck / cv hold the rendering, the planes its bytes, and the wide step reads them
+    bool cross_fp8 = false, f8_live = false;
+    uint8_t *f8_k = nullptr, *f8_v = nullptr, *f8_ks = nullptr, *f8_vs = nullptr;
+    int wd_cross_kernel = 0;  // the last wide run's cross-attention (debug read 44): 0 none yet, 1 k_wd_cross_attn,
+                              // 2 k_wd_cross_attn1, 3 k_wd_cross_attn_f8, 4 k_wd_cross_attn1_f8
     // the wide step under the decoding rules (wmi_wide_rules.hip): the rule block, an allocation of its own made with
     // the first ruled wide window: the hypotheses' histories [recs][8], then the parts [recs][8][16]
     WdRuleTable wd_rt{};
@@ -1200,6 +1207,36 @@ int run_mel(wmi_context *ctx) {
     return WMI_OK;
 }
 
+// ---- MXFP8 cross keys and values (wmi_set_cross_fp8; wmi_cross_fp8.hip) ----
+// the planes for max_clips clips of n_audio_ctx keys, an allocation of their own made with the first switch-on
+int ensure_f8_planes(wmi_context *ctx) {
+    if (ctx->f8_k) return WMI_OK;
+    const wmi_hparams &hp = ctx->hp;
+    const size_t L = hp.n_text_layer, Bt = ctx->max_clips;
+    const size_t pay = (size_t)up((int64_t)(L * Bt * hp.n_audio_ctx * hp.n_text_state), 256);
+    const size_t sc = L * Bt * (size_t)f8_scale_plane_bytes(hp.n_audio_ctx, hp.n_text_state);
+    uint8_t *p = nullptr;
+    HIPCHK(ctx, hipMalloc(&p, 2 * pay + 2 * sc));
+    hipError_t e = hipMemset(p, 0, 2 * pay + 2 * sc);
+    if (e != hipSuccess) { (void)hipFree(p); HIPCHK(ctx, e); }
+    ctx->f8_k = p; ctx->f8_v = p + pay; ctx->f8_ks = p + 2 * pay; ctx->f8_vs = p + 2 * pay + sc;
+    return WMI_OK;
+}
+
+// the last encode's ck / cv into the planes, and the rendering back over them
+int quantise_cross_kv(wmi_context *ctx) {
+    const int rc = ensure_f8_planes(ctx);
+    if (rc) return rc;
+    F8QuantArgs a{};
+    a.rows = (int64_t)ctx->hp.n_text_layer * ctx->enc_clips * ctx->enc_T;
+    a.T = ctx->enc_T; a.Tp = f8_tp(ctx->enc_T); a.n = ctx->hp.n_text_state;
+    a.x = ctx->ck; a.q = ctx->f8_k; a.sc = ctx->f8_ks;
+    HIPCHK(ctx, launch_cross_fp8_quant(ctx->stream, a));
+    a.x = ctx->cv; a.q = ctx->f8_v; a.sc = ctx->f8_vs;
+    HIPCHK(ctx, launch_cross_fp8_quant(ctx->stream, a));
+    return WMI_OK;
+}
+
 // Encode B slots.  Without src / off: the loaded clips, each at mel_offset.
 // With them (device arrays [B]): slot b holds recording src[b]'s window at
 // off[b], B <= the loaded clips (a round of run_transcribe_batch).  With end
@@ -1323,6 +1360,12 @@ int run_encode(wmi_context *ctx, int mel_offset, int slots = 0, const int32_t *s
     HIPCHK(ctx, launch_gemm(s, EPI_CROSSKV, g));
     ctx->enc_T = T;
     ctx->enc_clips = B;
+    ctx->f8_live = false;
+    if (ctx->cross_fp8) {  // (wmi_set_cross_fp8: every consumer of ck / cv reads the rendering from here on)
+        const int rc = quantise_cross_kv(ctx);
+        if (rc) return rc;
+        ctx->f8_live = true;
+    }
     return WMI_OK;
 }
 
@@ -4324,7 +4367,16 @@ int enqueue_wide_step(wmi_context *ctx, int B, int K, int chunks, int tiles, boo
         qa.bias = d.bcq; qa.N = n;  // (the q part alone)
         HIPCHK(ctx, launch_wd_qkv_store(s, qa));
         ca.K = ctx->ck + (size_t)l * Bt * T * n; ca.V = ctx->cv + (size_t)l * Bt * T * n;
-        HIPCHK(ctx, rows1 ? launch_wd_cross_attn1(s, ca) : launch_wd_cross_attn(s, ca));
+        if (ctx->f8_live) {  // (wmi_set_cross_fp8: the planes of the last encode; K = 1 whatever wmi_set_wide_rounds says)
+            WdCrossF8Args fa{};
+            fa.a = ca; fa.Tp = f8_tp(T);
+            fa.K8 = ctx->f8_k + (size_t)l * Bt * T * n; fa.V8 = ctx->f8_v + (size_t)l * Bt * T * n;
+            fa.Ksc = ctx->f8_ks + (size_t)l * Bt * f8_scale_plane_bytes(T, n);
+            fa.Vsc = ctx->f8_vs + (size_t)l * Bt * f8_scale_plane_bytes(T, n);
+            HIPCHK(ctx, K == 1 ? launch_wd_cross_attn1_f8(s, fa) : launch_wd_cross_attn_f8(s, fa));
+        } else {
+            HIPCHK(ctx, rows1 ? launch_wd_cross_attn1(s, ca) : launch_wd_cross_attn(s, ca));
+        }
         g = gemm(ctx->pf_att16, n, d.wco, d.bco, n);
         g.out32 = ctx->pf_x; g.ldo = n;
         HIPCHK(ctx, dense_product(ctx, s, EPI_RESID, g, ql ? &ql->wco : nullptr));
@@ -4516,7 +4568,10 @@ int run_wide_beam_rows(wmi_context *ctx, int b0, int B, int K, const std::vector
     else if (ruled && kl > 0 && kl < (int)sizeof key)
         kl += snprintf(key + kl, sizeof key - kl, "/ruled/%p", (void *)ctx->wd_rt.hist);
     if (p_nosp && !samp && kl > 0 && kl < (int)sizeof key) kl += snprintf(key + kl, sizeof key - kl, "/nosp/%p", (void *)ctx->wd_st.p_nosp);
-    if (rows1 && kl > 0 && kl < (int)sizeof key) snprintf(key + kl, sizeof key - kl, "/rows1");
+    // (the cross-attention kernel: under wmi_set_cross_fp8 the fp8 pair, on planes allocated once)
+    if (kl > 0 && kl < (int)sizeof key && (ctx->f8_live || rows1))
+        snprintf(key + kl, sizeof key - kl, ctx->f8_live ? (K == 1 ? "/f8rows1" : "/f8") : "/rows1");
+    ctx->wd_cross_kernel = ctx->f8_live ? (K == 1 ? 4 : 3) : rows1 ? 2 : 1;
     wmi_context::Graph *graph = nullptr;
     if (ctx->use_graph) {
         auto it = ctx->graphs.find(key);
@@ -4798,6 +4853,7 @@ void wmi_free(wmi_context *ctx) {
     if (ctx->pf_x) (void)hipFree(ctx->pf_x);
     if (ctx->pf_logits) (void)hipFree(ctx->pf_logits);
     if (ctx->d_qplanes) (void)hipFree(ctx->d_qplanes);
+    if (ctx->f8_k) (void)hipFree(ctx->f8_k);
     for (void *p : {(void *)ctx->wd_k, (void *)ctx->wd_v, ctx->wd_tab, (void *)ctx->wd_logits, (void *)ctx->wd_part,
                     (void *)ctx->wd_lgall})
         if (p) (void)hipFree(p);
@@ -6259,6 +6315,10 @@ int wmi_bench_kernel(wmi_context *ctx, int which, int iters, wmi_kernel_bench *o
     float ms = 0;
     HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]));
     out->avg_us = ms * 1000.0f / iters;
+    if (which == 3 && ctx->f8_live) {  // (the product wrote plain f16 over the rendering: the planes' values again)
+        rc = quantise_cross_kv(ctx);
+        if (rc) return rc;
+    }
     const double nt = hp.n_text_state, V = hp.n_vocab;
     if (which == 0) {
         const double b = B < 8 ? B : 8;
@@ -6467,6 +6527,12 @@ int wmi_debug_read(const wmi_context *ctx, int which, void *out, size_t bytes) {
             break;
         case 42: {  // host, int64: launch_gemm_q launches since the context was created
             const int64_t v = ctx->qgemm_launches;
+            memcpy(out, &v, std::min(sizeof v, bytes));
+            return WMI_OK;
+        }
+        case 44: {  // host, int32: the last wide run's cross-attention kernel: 0 none yet, 1 k_wd_cross_attn,
+                    // 2 k_wd_cross_attn1, 3 k_wd_cross_attn_f8, 4 k_wd_cross_attn1_f8
+            const int32_t v = ctx->wd_cross_kernel;
             memcpy(out, &v, std::min(sizeof v, bytes));
             return WMI_OK;
         }
@@ -6695,6 +6761,81 @@ static int wmi_set_quant_gemm_impl(wmi_context *ctx, int enable) {
 int wmi_set_quant_gemm(wmi_context *ctx, int enable) {
     if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
     return guarded(ctx, [&] { return wmi_set_quant_gemm_impl(ctx, enable); });
+}
+
+static int wmi_set_cross_fp8_impl(wmi_context *ctx, int enable) {
+    if (enable != 0 && enable != 1) return set_err(ctx, WMI_E_INVALID_ARG, "enable %d is neither 0 nor 1", enable);
+    if (ctx->wf32) return set_err(ctx, WMI_E_UNSUPPORTED, "MXFP8 cross keys and values quantise f16 planes: this file is f32");
+    if (enable && ctx->hp.n_text_state % 32)
+        return set_err(ctx, WMI_E_UNSUPPORTED, "n_text_state %d is no multiple of the 32-element block", ctx->hp.n_text_state);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (enable && !ctx->f8_k) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        const int rc = ensure_f8_planes(ctx);
+        if (rc) return rc;
+        ctx->clear_graphs();
+    }
+    ctx->cross_fp8 = enable != 0;  // (the next encode quantises, or leaves plain f16 again)
+    return WMI_OK;
+}
+
+int wmi_set_cross_fp8(wmi_context *ctx, int enable) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    return guarded(ctx, [&] { return wmi_set_cross_fp8_impl(ctx, enable); });
+}
+
+int wmi_get_cross_kv_fp8(const wmi_context *ctx, int clip, uint8_t *k8, uint8_t *v8, uint8_t *k_scale, uint8_t *v_scale,
+                         size_t cap) {
+    if (!ctx || !k8 || !v8 || !k_scale || !v_scale || clip < 0 || clip >= ctx->enc_clips || ctx->enc_T <= 0 || !ctx->f8_live)
+        return WMI_E_INVALID_ARG;
+    return guarded(nullptr, [&]() -> int {
+        const int T = ctx->enc_T, n = ctx->hp.n_text_state, L = ctx->hp.n_text_layer, nb = n / 32, Tp = f8_tp(T);
+        const size_t per = (size_t)T * n, plane = (size_t)f8_scale_plane_bytes(T, n);
+        if (cap < per * L) return WMI_E_NO_SPACE;
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess) return WMI_E_HIP;
+        std::vector<uint8_t> sc(plane);
+        for (int l = 0; l < L; ++l) {
+            const size_t p = (size_t)l * ctx->enc_clips + clip;
+            if (hipMemcpy(k8 + l * per, ctx->f8_k + p * per, per, hipMemcpyDeviceToHost) != hipSuccess) return WMI_E_HIP;
+            if (hipMemcpy(v8 + l * per, ctx->f8_v + p * per, per, hipMemcpyDeviceToHost) != hipSuccess) return WMI_E_HIP;
+            for (int kv = 0; kv < 2; ++kv) {  // the device's [head][Tp][2] into [T][n / 32]
+                if (hipMemcpy(sc.data(), (kv ? ctx->f8_vs : ctx->f8_ks) + p * plane, plane, hipMemcpyDeviceToHost) != hipSuccess)
+                    return WMI_E_HIP;
+                uint8_t *dst = (kv ? v_scale : k_scale) + (size_t)l * T * nb;
+                for (int t = 0; t < T; ++t)
+                    for (int j = 0; j < nb; ++j) dst[(size_t)t * nb + j] = sc[((size_t)(j >> 1) * Tp + t) * 2 + (j & 1)];
+            }
+        }
+        return WMI_OK;
+    });
+}
+
+int wmi_fp8_quantise(wmi_context *ctx, const uint16_t *f16_in, int rows, int n, uint8_t *q_out, uint8_t *scale_out,
+                     uint16_t *f16_rendered_out) {
+    if (!ctx) return set_err(nullptr, WMI_E_INVALID_ARG, "null context");
+    return guarded(ctx, [&]() -> int {
+        if (!f16_in || !q_out || !scale_out || !f16_rendered_out || rows < 1 || n < 32 || n % 32)
+            return set_err(ctx, WMI_E_INVALID_ARG, "wmi_fp8_quantise: %d rows of %d elements", rows, n);
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        const size_t nel = (size_t)rows * n, plane = (size_t)f8_scale_plane_bytes(rows, n);
+        const size_t o_q = (size_t)up((int64_t)nel * 2, 256), o_sc = o_q + (size_t)up((int64_t)nel, 256);
+        uint8_t *d = nullptr;
+        HIPCHK(ctx, hipMalloc(&d, o_sc + plane));
+        F8QuantArgs a{};
+        a.x = (uint16_t *)d; a.q = d + o_q; a.sc = d + o_sc; a.rows = rows; a.T = rows; a.Tp = f8_tp(rows); a.n = n;
+        std::vector<uint8_t> sc(plane);
+        hipError_t e = hipMemcpy(d, f16_in, nel * 2, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = launch_cross_fp8_quant(nullptr, a);
+        if (e == hipSuccess) e = hipMemcpy(f16_rendered_out, d, nel * 2, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(q_out, d + o_q, nel, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(sc.data(), d + o_sc, plane, hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        if (e != hipSuccess) return set_err(ctx, WMI_E_HIP, "wmi_fp8_quantise: %s", hipGetErrorString(e));
+        const int nb = n / 32;
+        for (int t = 0; t < rows; ++t)
+            for (int j = 0; j < nb; ++j) scale_out[(size_t)t * nb + j] = sc[((size_t)(j >> 1) * a.Tp + t) * 2 + (j & 1)];
+        return WMI_OK;
+    });
 }
 
 int wmi_dequant_blocks(int type, const void *raw, int64_t nel, uint16_t *out_f16) {

@@ -614,6 +614,28 @@ hipError_t launch_wd_cross_combine(hipStream_t s, const WdCrossArgs &a);
 // wmi_wide_rows.hip (wmi_set_wide_rounds): Kb = 1, one query a (recording, head); k_wd_cross_attn1 writes row 0 of a
 // chunk's 16 partial rows, then k_wd_cross_combine
 hipError_t launch_wd_cross_attn1(hipStream_t s, const WdCrossArgs &a);
+// ---- MXFP8 cross keys and values (wmi_cross_fp8.hip; wmi_set_cross_fp8; DESIGN.md "MXFP8 cross keys and values"):
+// e4m3 elements with an E8M0 scale byte per 32 along the state dimension.  The payload planes keep the f16 planes'
+// order [L][clips][T][n]; a (layer, clip) plane's scale bytes are [ceil(n / 64)][Tp][2], Tp = T rounded up to 64
+constexpr int f8_tp(int T) { return (T + 63) / 64 * 64; }
+constexpr int64_t f8_scale_plane_bytes(int T, int n) { return (int64_t)((n + 63) / 64) * f8_tp(T) * 2; }
+struct F8QuantArgs {
+    uint16_t *x;             // [rows][n] f16 in, the rendering (e4m3 * 2^s, exact in f16) out
+    uint8_t *q;              // [rows][n] e4m3
+    uint8_t *sc;             // [rows / T] scale planes
+    int64_t rows;
+    int T, Tp, n;            // rows a plane, f8_tp(T), elements a row (a multiple of 32)
+};
+hipError_t launch_cross_fp8_quant(hipStream_t s, const F8QuantArgs &a);
+struct WdCrossF8Args {
+    WdCrossArgs a;           // (K, V unused)
+    const uint8_t *K8, *V8;  // a layer's payload [Bt][T][n]
+    const uint8_t *Ksc, *Vsc;  // a layer's scale planes [Bt]
+    int Tp;
+};
+// k_wd_cross_attn1_f8 (Kb = 1) / k_wd_cross_attn_f8, then k_wd_cross_combine
+hipError_t launch_wd_cross_attn1_f8(hipStream_t s, const WdCrossF8Args &a);
+hipError_t launch_wd_cross_attn_f8(hipStream_t s, const WdCrossF8Args &a);
 struct WdBeamArgs {
     WdTable tb;
     const float *logits;     // [R][V]

@@ -74,6 +74,7 @@ EXPORTS = (
     "wmi_set_prefill", "wmi_prefill_logits", "wmi_set_quant_gemm", "wmi_dequant_blocks",
     "wmi_set_batch_beam", "wmi_decode_timestamps_beam_rows", "wmi_decode_timestamps_ruled_beam_rows",
     "wmi_set_wide_rounds", "wmi_decode_timestamps_sampled_rows", "wmi_set_wide_fallback",
+    "wmi_set_cross_fp8", "wmi_get_cross_kv_fp8", "wmi_fp8_quantise",
     "wmi_is_non_speech_token", "wmi_set_token_timestamps", "wmi_token_times",
     "wmi_set_dtw", "wmi_align_tokens", "wmi_dtw_path", "wmi_dtw_path_host", "wmi_get_segment_dtw_of",
     "wmi_set_dtw_pass", "wmi_align_tokens_rows",
@@ -261,6 +262,10 @@ def lib():
             L.wmi_decode_timestamps_sampled_rows.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_uint64, vp,
                                                              vp, vp, vp, vp, vp]
             L.wmi_set_wide_fallback.argtypes = [vp, C.c_int]
+        if hasattr(L, "wmi_set_cross_fp8"):  # (as above: an older build has no MXFP8 cross keys and values)
+            L.wmi_set_cross_fp8.argtypes = [vp, C.c_int]
+            L.wmi_get_cross_kv_fp8.argtypes = [vp, C.c_int, vp, vp, vp, vp, sz]
+            L.wmi_fp8_quantise.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
         if hasattr(L, "wmi_set_token_timestamps"):  # (as above: an older build has no token-level timestamps)
             L.wmi_set_token_timestamps.argtypes = [vp, C.POINTER(TokenTsParams)]
             L.wmi_token_times.argtypes = [vp, vp, sz, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int]
@@ -707,6 +712,40 @@ class WhisperContext:
         """Debug read 38: (B, K, steps, [p_c]) of the last wide run."""
         v = np.frombuffer(self.debug_read(38, (3 + 64) * 4), np.int32)
         return int(v[0]), int(v[1]), int(v[2]), v[3:3 + int(v[0])].tolist()
+
+    def wide_cross_kernel(self) -> str:
+        """Debug read 44: the cross-attention kernel of the last wide run ("" before the first)."""
+        names = ("", "k_wd_cross_attn", "k_wd_cross_attn1", "k_wd_cross_attn_f8", "k_wd_cross_attn1_f8")
+        return names[int(np.frombuffer(self.debug_read(44, 4), np.int32)[0])]
+
+    def set_cross_fp8(self, enable=1) -> None:
+        """1: from the next encode() on the cross keys and values are held as
+        MXFP8 (e4m3 elements, a power-of-two scale per 32) for the wide decoder
+        step's cross-attention, and cross_kv() returns their f16 rendering,
+        which every other decoder path reads.  0, the default: the next encode
+        leaves plain f16.  An f32 file: Unsupported.  Neither: InvalidArgument."""
+        _raise(lib().wmi_set_cross_fp8(self._h, int(enable)), self._h)
+
+    def cross_kv_fp8(self, clip: int = 0):
+        """(k8, v8, k_scale, v_scale) of an encode under set_cross_fp8(1): e4m3
+        bytes [n_text_layer][n_ctx][n_text_state] and E8M0 scale bytes
+        [n_text_layer][n_ctx][n_text_state // 32]."""
+        L, n = self.hparams["n_text_layer"], self.hparams["n_text_state"]
+        k8, v8 = np.zeros((L, self.n_ctx, n), np.uint8), np.zeros((L, self.n_ctx, n), np.uint8)
+        ks, vs = np.zeros((L, self.n_ctx, n // 32), np.uint8), np.zeros((L, self.n_ctx, n // 32), np.uint8)
+        _raise(lib().wmi_get_cross_kv_fp8(self._h, clip, _ptr(k8), _ptr(v8), _ptr(ks), _ptr(vs), k8.size), self._h)
+        return k8, v8, ks, vs
+
+    def fp8_quantise(self, x):
+        """The quantiser kernel over x [rows][n] (f16 bits as uint16, n a
+        multiple of 32): (e4m3 bytes [rows][n], scale bytes [rows][n // 32],
+        f16 rendering [rows][n])."""
+        x = np.ascontiguousarray(x, dtype=np.uint16)
+        rows, n = x.shape
+        q, r = np.zeros((rows, n), np.uint8), np.zeros((rows, n), np.uint16)
+        sc = np.zeros((rows, max(1, n // 32)), np.uint8)
+        _raise(lib().wmi_fp8_quantise(self._h, _ptr(x), rows, n, _ptr(q), _ptr(sc), _ptr(r)), self._h)
+        return q, sc, r
 
     def wide_logits(self, max_tokens: int) -> np.ndarray:
         """Debug read 39 (WMI_LOGITS_ALL): the last wide run's logits
