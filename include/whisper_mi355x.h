@@ -46,7 +46,7 @@ enum wmi_status {
     WMI_E_UNEXPECTED = 10,    /* WsError::Unexpected        main.rs:52-53 */
     WMI_E_HIP = 11,           /* HIP runtime / kernel launch failure */
     WMI_E_RCCL = 12,          /* RCCL failure */
-    WMI_E_UNSUPPORTED = 13,   /* valid file, feature not built (e.g. a ggml type other than f32 / f16 / q4_0 / q4_1 / q5_0 / q5_1 / q8_0) */
+    WMI_E_UNSUPPORTED = 13,   /* valid file, feature not built (e.g. a ggml type other than f32 / f16 / q4_0 / q4_1 / q5_0 / q5_1 / q8_0 / q4_K / q5_K / q6_K: q2_K and q3_K are not built) */
     WMI_E_INVALID_ARG = 14    /* bad pointer / size / state order */
 };
 
@@ -89,7 +89,14 @@ typedef struct wmi_context wmi_context;
  * filters, vocab (+extra tokens), weights; then upload to `device`.
  * max_clips sizes the device workspace for batched calls (>= 1).  Weight
  * types: f16 and f32 files (hparams.f16 = 1 / 0, main.rs:817-821; f32
- * matrices are kept f32 on the device) and the ggml quantised types.
+ * matrices are kept f32 on the device) and the ggml quantised types: the
+ * 32-weight blocks q4_0, q4_1, q5_0, q5_1, q8_0 and the 256-weight K-quant
+ * super-blocks q4_K, q5_K, q6_K (ggml types 12, 13, 14; as a record's own type
+ * and, at QNT version 2, as the header's ftype).  Every quantised matrix is
+ * dequantised to an f16 copy at load, record by record, so a file may mix
+ * them with f16 records.  A K-quant record whose row length is no multiple of
+ * 256 is WMI_E_WRONG_BYTES; q2_K and q3_K (types 10, 11) stay
+ * WMI_E_UNSUPPORTED.
  * Shapes: n_text_state == n_audio_state, a multiple of 128 up to 1280 with
  * 64-wide heads, n_text_ctx <= 512, any depths and n_audio_ctx; anything
  * else is WMI_E_UNSUPPORTED as soon as the header is parsed (before a tensor
@@ -611,11 +618,19 @@ int wmi_prefill_logits(wmi_context *ctx, int clip, const int32_t *tokens, int n_
  * recordings' packed rows) stays on the f16 kernels, which reuse the weights
  * across row tiles; what was measured is in DESIGN.md, "Quantised-weight
  * GEMM".  A switch drops the cached wide-step graphs.
+ * A K-quant file (q4_K, q5_K, q6_K) takes the same switch onto a kernel of its
+ * own (wmi_gemm_qk.hip; DESIGN.md, "K-quant GEMM"): it reads the 256-weight
+ * super-blocks, makes each sub-block's effective scale d * sc and offset
+ * dmin * m in f32 and expands a weight to the copy's value, w = f16(fmaf(q,
+ * d * sc, -(dmin * m))) (q6_K: the f32 product (d * S)(q - 32)), the f32 result
+ * rounded once more to f16; the same launch rule, the same fixed K order.
  * enable outside {0, 1} or a null context: WMI_E_INVALID_ARG.  Debug read 42
  * counts the kernel's launches.
  * wmi_dequant_blocks: nel / 32 raw ggml blocks of `type` (2 q4_0, 3 q4_1, 6
- * q5_0, 7 q5_1, 8 q8_0) expanded on the current device with the kernel's own
- * device function into out_f16 [nel] (f16 bits); needs a device, no context. */
+ * q5_0, 7 q5_1, 8 q8_0), or nel / 256 super-blocks (12 q4_K, 13 q5_K, 14
+ * q6_K; nel a multiple of 256), expanded on the current device with their
+ * kernel's own device function into out_f16 [nel] (f16 bits); needs a device,
+ * no context. */
 int wmi_set_quant_gemm(wmi_context *ctx, int enable);
 int wmi_dequant_blocks(int type, const void *raw, int64_t nel, uint16_t *out_f16);
 

@@ -7,6 +7,10 @@ runs its call once untimed (the wide step is captured again there) and then
 times a window of INNER calls in a row, all of them graph replays; INNER is
 what fills --window-ms at the warm-up's pace, one count for both settings.
 
+QUANT may be a K-quant (q4_K, q5_K, q6_K; MODEL's width a multiple of 256): `on`
+is then wmi_gemm_qk.hip on the super-blocks, `off` the same f16 kernels on the
+f16 copies as for every other file.
+
 On eight 30 s recordings of the synthetic MODEL written in QUANT:
   wide      one wide window (wmi_decode_timestamps_beam_rows) at R = 40 and
             R = 64 rows (8 x 5, 8 x 8): host time per wide step, graph replay

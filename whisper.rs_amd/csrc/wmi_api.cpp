@@ -31,6 +31,7 @@
 #include "wmi_host.h"
 #include "wmi_internal.h"
 #include "wmi_gemm_q.h"
+#include "wmi_gemm_qk.h"
 #include "wmi_align_pass.h"
 
 #pragma clang fp contract(off)
@@ -172,15 +173,16 @@ struct wmi_context {
     bool batch_beam = false;
     // the quantised-weight GEMM of the prefill pass and the wide step (wmi_set_quant_gemm; wmi_gemm_q.hip).  The planes
     // come with the first switch-on, one allocation built from the file's blocks read again (model_path): per decoder
-    // layer the six products' matrices, then the token embedding for the logits (qtype 0: f16 in the file, no planes)
-    struct QMat { int qtype = 0; const uint8_t *qn = nullptr; const uint32_t *side = nullptr; };
+    // layer the six products' matrices, then the token embedding for the logits (qtype 0: f16 in the file, no planes).
+    // A K-quant matrix (qtype 12 to 14) holds the planes of wmi_gemm_qk.hip: hi, its high bits, besides.
+    struct QMat { int qtype = 0; const uint8_t *qn = nullptr; const uint32_t *side = nullptr, *hi = nullptr; };
     struct QLayer { QMat wqkv, wo, wcq, wco, w0, w1; };
     std::string model_path;
     bool qgemm = false, qplanes_built = false;
     void *d_qplanes = nullptr;
     std::vector<QLayer> qdec;
     QMat qte;
-    int64_t qgemm_launches = 0;  // launch_gemm_q launches since the context was created (debug read 42)
+    int64_t qgemm_launches = 0;  // launch_gemm_q and launch_gemm_qk launches since the context was created (debug read 42)
     int qgemm_max_rows = 0;      // the launch rule's row count (QGEMM_MAX_ROWS, or WMI_QGEMM_MAX_ROWS)
     uint16_t *wd_k = nullptr, *wd_v = nullptr;
     int wd_rows = 0;
@@ -2351,12 +2353,21 @@ constexpr int QGEMM_MAX_ROWS = 64;
 // are there, else launch_gemm as before
 hipError_t dense_product(wmi_context *ctx, hipStream_t s, int epi, const GemmArgs &g, const wmi_context::QMat *qm) {
     if (!ctx->qgemm || !qm || !qm->qn || g.M > ctx->qgemm_max_rows) return launch_gemm(s, epi, g);
+    ++ctx->qgemm_launches;
+    if (qblock_weights(qm->qtype) == 256) {  // a K-quant matrix: the super-block kernel
+        GemmQKArgs k{};
+        k.g = g;
+        k.qtype = qm->qtype;
+        k.qn = qm->qn;
+        k.hi = qm->hi;
+        k.side = qm->side;
+        return launch_gemm_qk(s, epi, k);
+    }
     GemmQArgs q{};
     q.g = g;
     q.qtype = qm->qtype;
     q.qn = qm->qn;
     q.side = qm->side;
-    ++ctx->qgemm_launches;
     return launch_gemm_q(s, epi, q);
 }
 const wmi_context::QLayer *qlayer_of(const wmi_context *ctx, int l) {
@@ -2372,20 +2383,35 @@ int build_qplanes(wmi_context *ctx) {
     if (rc) return set_err(ctx, rc, "%s", err.c_str());
     const int Lt = ctx->hp.n_text_layer;
     std::vector<uint8_t> stage;
-    struct Off { int qtype; size_t qn, side; };
+    struct Off { int qtype; size_t qn, side, hi; };
     // the planes of `names` one behind the other (a [sum rows][K] matrix); qtype 0 unless all share one block format
     auto add = [&](std::initializer_list<std::string> names) {
-        Off o{0, 0, 0};
+        Off o{0, 0, 0, 0};
         int64_t nblocks = 0;
         int t = -1;
         for (const std::string &nm : names) {
             const HostTensor &ht = pm.tensors.at(nm);
             if (!ht.qtype || ht.qraw.empty() || (t >= 0 && ht.qtype != t)) return o;
             t = ht.qtype;
-            nblocks += ht.nel() / 32;
+            nblocks += ht.nel() / qblock_weights(t);
+        }
+        o.qtype = t;
+        if (qblock_weights(t) == 256) {  // super-blocks: nibbles, high bits, scales (repack_kblocks)
+            const size_t HW = (size_t)kplane_hi_words(t);
+            o.qn = (size_t)up((int64_t)stage.size(), 256);
+            o.hi = (size_t)up((int64_t)(o.qn + nblocks * 128), 256);
+            o.side = (size_t)up((int64_t)(o.hi + nblocks * 8 * HW * 4), 256);
+            stage.resize(o.side + nblocks * 5 * 4, 0);
+            int64_t b0 = 0;
+            for (const std::string &nm : names) {
+                const HostTensor &ht = pm.tensors.at(nm);
+                repack_kblocks(t, ht.qraw.data(), ht.nel() / 256, stage.data() + o.qn + b0 * 128,
+                               (uint32_t *)(stage.data() + o.hi) + b0 * 8 * HW, (uint32_t *)(stage.data() + o.side) + b0 * 5);
+                b0 += ht.nel() / 256;
+            }
+            return o;
         }
         const size_t QB = (size_t)qplane_qbytes(t), SW = (size_t)qplane_side_words(t);
-        o.qtype = t;
         o.qn = (size_t)up((int64_t)stage.size(), 256);
         o.side = (size_t)up((int64_t)(o.qn + nblocks * QB), 256);
         stage.resize(o.side + nblocks * SW * 4, 0);
@@ -2426,6 +2452,7 @@ int build_qplanes(wmi_context *ctx) {
     auto Q = [&](const Off &o) {
         wmi_context::QMat m;
         if (o.qtype) { m.qtype = o.qtype; m.qn = base + o.qn; m.side = (const uint32_t *)(base + o.side); }
+        if (o.qtype && qblock_weights(o.qtype) == 256) m.hi = (const uint32_t *)(base + o.hi);
         return m;
     };
     ctx->qdec.resize(Lt);
@@ -6840,8 +6867,27 @@ int wmi_fp8_quantise(wmi_context *ctx, const uint16_t *f16_in, int rows, int n, 
 
 int wmi_dequant_blocks(int type, const void *raw, int64_t nel, uint16_t *out_f16) {
     return guarded(nullptr, [&]() -> int {
-        if (!raw || !out_f16 || !qblock_bytes(type) || nel <= 0 || nel % 32 != 0 || nel > (int64_t)1 << 31)
+        if (!raw || !out_f16 || !qblock_bytes(type) || nel <= 0 || nel % qblock_weights(type) != 0 || nel > (int64_t)1 << 31)
             return set_err(nullptr, WMI_E_INVALID_ARG, "wmi_dequant_blocks: type %d, %lld elements", type, (long long)nel);
+        if (qblock_weights(type) == 256) {  // super-blocks: the K-quant GEMM's planes and device function
+            const int64_t nsb = nel / 256;
+            const size_t o_hi = (size_t)nsb * 128, o_side = o_hi + (size_t)nsb * 8 * kplane_hi_words(type) * 4;
+            const size_t o_out = (size_t)up((int64_t)(o_side + nsb * 5 * 4), 256);
+            std::vector<uint8_t> planes(o_out, 0);
+            repack_kblocks(type, (const uint8_t *)raw, nsb, planes.data(), (uint32_t *)(planes.data() + o_hi),
+                           (uint32_t *)(planes.data() + o_side));
+            uint8_t *d = nullptr;
+            if (hipMalloc(&d, o_out + (size_t)nel * 2) != hipSuccess)
+                return set_err(nullptr, WMI_E_HIP, "wmi_dequant_blocks: no device memory");
+            hipError_t e = hipMemcpy(d, planes.data(), planes.size(), hipMemcpyHostToDevice);
+            if (e == hipSuccess)
+                e = launch_dequant_qk(nullptr, type, d, (const uint32_t *)(d + o_hi), (const uint32_t *)(d + o_side), nsb,
+                                      (uint16_t *)(d + o_out));
+            if (e == hipSuccess) e = hipMemcpy(out_f16, d + o_out, (size_t)nel * 2, hipMemcpyDeviceToHost);
+            (void)hipFree(d);
+            if (e != hipSuccess) return set_err(nullptr, WMI_E_HIP, "wmi_dequant_blocks: %s", hipGetErrorString(e));
+            return WMI_OK;
+        }
         const int64_t nblocks = nel / 32;
         const size_t qb = (size_t)up(nblocks * qplane_qbytes(type), 256), sb = (size_t)nblocks * qplane_side_words(type) * 4;
         std::vector<uint8_t> planes(qb + sb, 0);

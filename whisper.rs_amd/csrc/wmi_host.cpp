@@ -118,11 +118,77 @@ int qblock_bytes(int t) {
         case 6: return 22;  // q5_0 {d, qh, qs[16]}
         case 7: return 24;  // q5_1 {d, m, qh, qs[16]}
         case 8: return 34;  // q8_0 {d, qs[32]}
+        // the K-quant super-blocks of 256 weights (q2_K and q3_K, types 10 and 11, are not built)
+        case 12: return 144;  // q4_K {d, dmin, scales[12], qs[128]}
+        case 13: return 176;  // q5_K {d, dmin, scales[12], qh[32], qs[128]}
+        case 14: return 210;  // q6_K {ql[128], qh[64], scales[16], d}
         default: return 0;
+    }
+}
+int qblock_weights(int t) { return t >= 12 && t <= 14 ? 256 : 32; }
+
+// sub-block j's 6-bit scale and minimum of a q4_K / q5_K scales[12] field
+static void k_scale_min(const uint8_t *s, int j, int *sc, int *m) {
+    if (j < 4) {
+        *sc = s[j] & 63;
+        *m = s[j + 4] & 63;
+    } else {
+        *sc = (s[j + 4] & 15) | ((s[j - 4] >> 6) << 4);
+        *m = (s[j + 4] >> 4) | ((s[j] >> 6) << 4);
+    }
+}
+
+// K-quant super-blocks to f16: d * sc and dmin * m are exact in f32 (11 bits by at most 8), the weight is one f32
+// fused multiply-add, fmaf(q, d * sc, -(dmin * m)) (q6_K: fmaf(q, d * S, -32 (d * S)), the f32 product (d * S)(q - 32)
+// rounded once), rounded once more to f16: ggml's float expression with the fusion pinned, and the value
+// dqk_half8 (wmi_gemm_qk.hip) makes on the device
+static void dequant_k_f16(int t, const uint8_t *src, int64_t nel, uint16_t *dst) {
+    const int bs = qblock_bytes(t);
+    for (int64_t ib = 0; ib < nel / 256; ++ib) {
+        const uint8_t *b = src + ib * bs;
+        uint16_t *y = dst + ib * 256;
+        uint16_t hd, hm;
+        if (t == 14) {
+            const uint8_t *ql = b, *qh = b + 128;
+            const int8_t *S = (const int8_t *)(b + 192);
+            memcpy(&hd, b + 208, 2);
+            const float d = f16_to_f32(hd);
+            for (int h = 0; h < 2; ++h)
+                for (int l = 0; l < 32; ++l) {
+                    const uint8_t *L = ql + 64 * h, H = qh[32 * h + l];
+                    const int q[4] = {(L[l] & 15) | ((H & 3) << 4), (L[l + 32] & 15) | (((H >> 2) & 3) << 4),
+                                      (L[l] >> 4) | (((H >> 4) & 3) << 4), (L[l + 32] >> 4) | (((H >> 6) & 3) << 4)};
+                    for (int i = 0; i < 4; ++i) {
+                        const float a = d * (float)S[8 * h + l / 16 + 2 * i];
+                        y[128 * h + 32 * i + l] = f32_to_f16(fmaf((float)q[i], a, -32.0f * a));
+                    }
+                }
+            continue;
+        }
+        memcpy(&hd, b, 2);
+        memcpy(&hm, b + 2, 2);
+        const float d = f16_to_f32(hd), dmin = f16_to_f32(hm);
+        const uint8_t *qh = b + 16, *qs = b + (t == 13 ? 48 : 16);
+        for (int p = 0; p < 4; ++p) {
+            int sc0, m0, sc1, m1;
+            k_scale_min(b + 4, 2 * p, &sc0, &m0);
+            k_scale_min(b + 4, 2 * p + 1, &sc1, &m1);
+            const float a0 = d * (float)sc0, b0 = -(dmin * (float)m0), a1 = d * (float)sc1, b1 = -(dmin * (float)m1);
+            for (int l = 0; l < 32; ++l) {
+                int q0 = qs[32 * p + l] & 15, q1 = qs[32 * p + l] >> 4;
+                if (t == 13) {
+                    q0 += (qh[l] >> (2 * p) & 1) << 4;
+                    q1 += (qh[l] >> (2 * p + 1) & 1) << 4;
+                }
+                y[64 * p + l] = f32_to_f16(fmaf((float)q0, a0, b0));
+                y[64 * p + 32 + l] = f32_to_f16(fmaf((float)q1, a1, b1));
+            }
+        }
     }
 }
 
 void dequant_f16(int t, const uint8_t *src, int64_t nel, uint16_t *dst) {
+    if (qblock_weights(t) == 256) return dequant_k_f16(t, src, nel, dst);
     const int bs = qblock_bytes(t);
     for (int64_t ib = 0; ib < nel / 32; ++ib) {
         const uint8_t *b = src + ib * bs;
@@ -160,8 +226,8 @@ void dequant_f16(int t, const uint8_t *src, int64_t nel, uint16_t *dst) {
 // The planes of the quantised-weight GEMM (wmi_gemm_q.hip): block i's quants at qn + i * QB in natural k order
 // (nibble byte j = weights 2j, 2j + 1; q8_0: its 32 bytes), its side record at side + i * SIDE: {d | m << 16}
 // (m = +0 where the format has none), for q5_x {fifth bits (bit j = weight j), d | m << 16}
-int qplane_qbytes(int t) { return t == 8 ? 32 : qblock_bytes(t) ? 16 : 0; }
-int qplane_side_words(int t) { return t == 6 || t == 7 ? 2 : qblock_bytes(t) ? 1 : 0; }
+int qplane_qbytes(int t) { return t == 8 ? 32 : qblock_bytes(t) && qblock_weights(t) == 32 ? 16 : 0; }
+int qplane_side_words(int t) { return t == 6 || t == 7 ? 2 : qblock_bytes(t) && qblock_weights(t) == 32 ? 1 : 0; }
 void repack_blocks(int t, const uint8_t *src, int64_t nblocks, uint8_t *qn, uint32_t *side) {
     const int bs = qblock_bytes(t), QB = qplane_qbytes(t), SIDE = qplane_side_words(t);
     const bool has_m = t == 3 || t == 7, has_h = t == 6 || t == 7;
@@ -183,6 +249,61 @@ void repack_blocks(int t, const uint8_t *src, int64_t nblocks, uint8_t *qn, uint
         }
         if (has_h) memcpy(&side[i * SIDE], b + 2 + (has_m ? 2 : 0), 4);  // (bit j = weight j in the file as well)
         side[i * SIDE + SIDE - 1] = (uint32_t)d | ((uint32_t)m << 16);
+    }
+}
+
+// The planes of the K-quant GEMM (wmi_gemm_qk.hip), per super-block i.  qn + 128 i: the file's 128 nibble bytes (qs;
+// q6_K: ql) as they are; 16-byte slot 2 w + lh is wave w's, half-wave lh's: byte 4 dw + p of a slot holds, in its
+// low and high nibble (n = 0, 1), weights kb + 4 dw + p and kb + HI + 4 dw + p, with kb = 64 w + 16 lh, HI = 32
+// (q6_K: kb = 128 (w >> 1) + 32 (w & 1) + 16 lh, HI = 64).  hi + 8 HW i: a slot's high bits where a shift and a
+// mask put them over a dword's nibbles: q5_K (HW = 1) bit 8 p + dw + 4 n, q6_K (HW = 2) word n, bits 8 p + 2 dw, + 1.
+// side + 5 i: {d | dmin << 16} (q6_K: d), then a word a wave, the fields of its two sub-blocks unpacked to bytes:
+// {sc, m, sc', m'}, q6_K the four int8 sub-scales {S[lh = 0], S[1], S'[0], S'[1]} of its low and high nibbles.
+int kplane_hi_words(int t) { return t == 13 ? 1 : t == 14 ? 2 : 0; }
+void repack_kblocks(int t, const uint8_t *src, int64_t nsb, uint8_t *qn, uint32_t *hi, uint32_t *side) {
+    const int bs = qblock_bytes(t), HW = kplane_hi_words(t);
+    for (int64_t i = 0; i < nsb; ++i) {
+        const uint8_t *b = src + i * bs;
+        uint32_t *sd = side + i * 5, *h = hi + i * 8 * HW;
+        uint16_t d, dmin = 0;
+        if (t == 14) {
+            const uint8_t *qh = b + 128, *S = b + 192;
+            memcpy(qn + i * 128, b, 128);
+            memcpy(&d, b + 208, 2);
+            for (int w = 0; w < 4; ++w) {
+                const int hf = w >> 1, j = w & 1;
+                const uint8_t *s8 = S + 8 * hf + 2 * j;
+                sd[1 + w] = (uint32_t)s8[0] | (uint32_t)s8[1] << 8 | (uint32_t)s8[4] << 16 | (uint32_t)s8[5] << 24;
+                for (int lh = 0; lh < 2; ++lh)
+                    for (int n = 0; n < 2; ++n) {
+                        uint32_t v = 0;
+                        for (int dw = 0; dw < 4; ++dw)
+                            for (int p = 0; p < 4; ++p)
+                                v |= (uint32_t)((qh[32 * hf + 16 * lh + 4 * dw + p] >> (2 * j + 4 * n)) & 3) << (8 * p + 2 * dw);
+                        h[(2 * w + lh) * 2 + n] = v;
+                    }
+            }
+        } else {
+            const uint8_t *qh = b + 16;
+            memcpy(qn + i * 128, b + (t == 13 ? 48 : 16), 128);
+            memcpy(&d, b, 2);
+            memcpy(&dmin, b + 2, 2);
+            for (int w = 0; w < 4; ++w) {
+                int sc0, m0, sc1, m1;
+                k_scale_min(b + 4, 2 * w, &sc0, &m0);
+                k_scale_min(b + 4, 2 * w + 1, &sc1, &m1);
+                sd[1 + w] = (uint32_t)sc0 | (uint32_t)m0 << 8 | (uint32_t)sc1 << 16 | (uint32_t)m1 << 24;
+                for (int lh = 0; t == 13 && lh < 2; ++lh) {
+                    uint32_t v = 0;
+                    for (int dw = 0; dw < 4; ++dw)
+                        for (int p = 0; p < 4; ++p)
+                            for (int n = 0; n < 2; ++n)
+                                v |= (uint32_t)((qh[16 * lh + 4 * dw + p] >> (2 * w + n)) & 1) << (8 * p + dw + 4 * n);
+                    h[2 * w + lh] = v;
+                }
+            }
+        }
+        sd[0] = (uint32_t)d | ((uint32_t)dmin << 16);
     }
 }
 
@@ -366,8 +487,15 @@ int parse_file(const char *path, ParsedModel &pm, std::string &err, bool decoder
                 err = b;
                 return WMI_E_WRONG_SHAPE;
             }
-        const int qb = (t.dtype == 1 && t.n_dims == 2 && ne[0] % 32 == 0) ? qblock_bytes(ftype) : 0;
-        const int64_t file_bytes = qb ? nel / 32 * qb : nel * (ftype == 0 ? 4 : 2);
+        const int qw = qblock_weights(ftype);
+        if (qw == 256 && (t.dtype != 1 || t.n_dims != 2 || ne[0] % 256 != 0)) {  // (ggml writes no such record)
+            snprintf(b, sizeof b, "tensor %s has wrong bytes in model file: a K-quant record (type %d) of rows of %lld",
+                     name.c_str(), ftype, (long long)ne[0]);
+            err = b;
+            return WMI_E_WRONG_BYTES;
+        }
+        const int qb = (t.dtype == 1 && t.n_dims == 2 && ne[0] % qw == 0) ? qblock_bytes(ftype) : 0;
+        const int64_t file_bytes = qb ? nel / qw * qb : nel * (ftype == 0 ? 4 : 2);
         if (decoder_blocks) {  // the decoder's quantised matrices as read; every other record is stepped over
             t.qtype = qb ? ftype : 0;
             if (qb && name.compare(0, 8, "decoder.") == 0) {
@@ -399,7 +527,8 @@ int parse_file(const char *path, ParsedModel &pm, std::string &err, bool decoder
     }
     {
         const int ft = hp.f16 % 1000, qv = hp.f16 / 1000;
-        const bool ok = ft == 0 || ft == 1 || ((ft == 2 || ft == 3 || ft == 7 || ft == 8 || ft == 9) && qv == 2);
+        const bool ok = ft == 0 || ft == 1 ||
+                        ((ft == 2 || ft == 3 || ft == 7 || ft == 8 || ft == 9 || ft == 12 || ft == 13 || ft == 14) && qv == 2);
         if (!ok) {
             char b[160];
             snprintf(b, sizeof b, "model ftype %d (hparams.f16 = %d) is not supported by this build", ft, hp.f16);

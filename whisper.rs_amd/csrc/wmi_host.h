@@ -33,7 +33,7 @@ void build_tables(std::vector<uint16_t> &gelu, std::vector<uint16_t> &expt);
 
 struct HostTensor {
     int dtype = 0;  // 0 f32, 1 f16 (quantised matrices are dequantised to f16)
-    int qtype = 0;  // ggml type of a quantised matrix in the file (7 = q5_1), else 0
+    int qtype = 0;  // ggml type of a quantised matrix in the file (7 = q5_1, 12 = q4_K, ..), else 0
     std::vector<uint8_t> qraw;  // its blocks as read (q5_1: the decoder GEMVs read them; every format under decoder_blocks)
     int n_dims = 0;
     int64_t ne[3] = {1, 1, 1};
@@ -57,7 +57,11 @@ struct ParsedModel {
     std::map<std::string, HostTensor> tensors;
 };
 
+// bytes and weights of a block of ggml type t: the 32-weight blocks 2 q4_0, 3 q4_1, 6 q5_0, 7 q5_1, 8 q8_0 and the
+// 256-weight K-quant super-blocks 12 q4_K, 13 q5_K, 14 q6_K; 0 bytes for every other type (10 q2_K and 11 q3_K
+// included: a file of theirs is WMI_E_UNSUPPORTED)
 int qblock_bytes(int t);
+int qblock_weights(int t);
 void dequant_f16(int t, const uint8_t *src, int64_t nel, uint16_t *dst);
 int check_shape(const wmi_hparams &hp, std::string &err);
 // decoder_blocks: nothing but the blocks of the decoder's quantised matrices is read (qtype and qraw; no tensor holds
@@ -67,6 +71,10 @@ int parse_file(const char *path, ParsedModel &pm, std::string &err, bool decoder
 int qplane_qbytes(int t);
 int qplane_side_words(int t);
 void repack_blocks(int t, const uint8_t *src, int64_t nblocks, uint8_t *qn, uint32_t *side);
+// the planes of the K-quant GEMM, per super-block: 128 bytes of nibbles, 8 kplane_hi_words(t) words of high bits
+// (none for q4_K), 5 words of scales
+int kplane_hi_words(int t);
+void repack_kblocks(int t, const uint8_t *src, int64_t nsb, uint8_t *qn, uint32_t *hi, uint32_t *side);
 void init_specials(int32_t n_vocab, wmi_special_tokens &sp);
 int read_wav(const char *path, int16_t *samples, size_t cap, size_t *n_samples, int32_t *sample_rate, int32_t *channels,
              std::string &err);

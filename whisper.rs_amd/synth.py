@@ -188,7 +188,10 @@ def _vocab_tokens(n: int):
 # ggml quantisation (QNT version 2 block layouts)
 # ----------------------------------------------------------------------------
 GGML_QNT_VERSION = 2
-QUANT_TYPES = {"q4_0": (2, 2), "q4_1": (3, 3), "q5_0": (6, 8), "q5_1": (7, 9), "q8_0": (8, 7)}  # -> (ttype, ftype)
+QUANT_TYPES = {"q4_0": (2, 2), "q4_1": (3, 3), "q5_0": (6, 8), "q5_1": (7, 9), "q8_0": (8, 7),
+               "q4_K": (12, 12), "q5_K": (13, 13), "q6_K": (14, 14)}  # -> (ttype, ftype)
+QK_K = 256
+K_BLOCK_BYTES = {12: 144, 13: 176, 14: 210}  # ttype -> bytes of a 256-weight super-block
 
 
 def _absmax_signed(x):
@@ -207,10 +210,98 @@ def _qh_bits(q):
     return ((((q & 0x10) >> 4).astype(np.uint64) << bits).sum(axis=1)).astype("<u4")
 
 
+def _rint_clip(x, hi):
+    return np.clip(np.rint(x), 0, hi).astype(np.int64)
+
+
+def quantize_k(w: np.ndarray, qtype: str) -> bytes:
+    """Valid q4_K / q5_K / q6_K super-blocks of 256 weights that use the whole range of every field; ggml's scale
+    search (make_qkx2_quants, make_qx_quants) is not restated, a plain min / max fit takes its place.
+    q4_K / q5_K: a sub-block of 32 has scale (max - min) / 15 (or 31) and minimum max(0, -min); d and dmin are the
+    largest of each over 63, so the 6-bit fields reach 63 (both halves of the packing) and dmin is non-zero.
+    q6_K: a sub-block of 16 has the scale (signed value of largest magnitude) / -32, so sub-scales of both signs."""
+    x = np.ascontiguousarray(w, dtype=np.float32).reshape(-1, QK_K)
+    nb = x.shape[0]
+    if qtype == "q6_K":
+        xs = x.reshape(nb, 16, 16)
+        i = np.abs(xs).argmax(axis=2)
+        s = np.take_along_axis(xs, i[:, :, None], 2)[:, :, 0] / np.float32(-32.0)
+        d = (np.abs(s).max(axis=1) / np.float32(127.0)).astype(np.float16)
+        S = np.clip(np.rint(s * _inv(d.astype(np.float32))[:, None]), -127, 127).astype(np.int8)
+        q = _rint_clip(xs * _inv(d.astype(np.float32)[:, None] * S)[:, :, None] + 32, 63).reshape(nb, 2, 4, 32)
+        blk = np.zeros(nb, dtype=[("ql", "u1", 128), ("qh", "u1", 64), ("scales", "i1", 16), ("d", "<f2")])
+        lo, hb = q & 15, q >> 4  # [half][quant i = weights 32 i + l][l]
+        blk["ql"] = np.stack([lo[:, :, 0] | lo[:, :, 2] << 4, lo[:, :, 1] | lo[:, :, 3] << 4], 2).reshape(nb, 128)
+        blk["qh"] = (hb[:, :, 0] | hb[:, :, 1] << 2 | hb[:, :, 2] << 4 | hb[:, :, 3] << 6).reshape(nb, 64)
+        blk["scales"], blk["d"] = S, d
+        return blk.tobytes()
+    qmax = 15 if qtype == "q4_K" else 31
+    xs = x.reshape(nb, 8, 32)
+    mn = np.minimum(xs.min(axis=2), 0)
+    s = (xs.max(axis=2) - mn) / np.float32(qmax)
+    d, dmin = ((v.max(axis=1) / np.float32(63.0)).astype(np.float16) for v in (s, -mn))
+    sc = _rint_clip(s * _inv(d.astype(np.float32))[:, None], 63)
+    m = _rint_clip(-mn * _inv(dmin.astype(np.float32))[:, None], 63)
+    a, b = d.astype(np.float32)[:, None] * sc, dmin.astype(np.float32)[:, None] * m
+    q = _rint_clip((xs + b[:, :, None]) * _inv(a)[:, :, None], qmax).reshape(nb, 4, 2, 32)
+    scales = np.concatenate([sc[:, :4] | (sc[:, 4:] >> 4) << 6, m[:, :4] | (m[:, 4:] >> 4) << 6,
+                             (sc[:, 4:] & 15) | (m[:, 4:] & 15) << 4], axis=1)
+    fields = [("d", "<f2"), ("dmin", "<f2"), ("scales", "u1", 12)] + ([("qh", "u1", 32)] if qtype == "q5_K" else [])
+    blk = np.zeros(nb, dtype=fields + [("qs", "u1", 128)])
+    blk["d"], blk["dmin"], blk["scales"] = d, dmin, scales
+    blk["qs"] = ((q[:, :, 0] & 15) | (q[:, :, 1] & 15) << 4).reshape(nb, 128)
+    if qtype == "q5_K":
+        blk["qh"] = ((q >> 4) << (2 * np.arange(4)[:, None, None] + np.arange(2)[:, None])).sum(axis=(1, 2))
+    return blk.tobytes()
+
+
+def _fma_f32(q, a, b):
+    """fmaf(q, a, b) for small integers q and float32 a, b: q a is exact in float64, the sum is rounded to odd there
+    (the rounding error by two-sum), and 53 bits rounded to odd round to float32 as the exact value does."""
+    p, b = q.astype(np.float64) * a.astype(np.float64), b.astype(np.float64)
+    s = p + b
+    t = s - p
+    e = (p - (s - t)) + (b - t)
+    odd = np.nextafter(s, np.where(e > 0, np.inf, -np.inf))
+    return np.where((e != 0) & (s.view(np.int64) & 1 == 0), odd, s).astype(np.float32)
+
+
+def _to_f16(x):
+    with np.errstate(over="ignore"):  # (a large d times a large scale is inf in f16, on every side)
+        return x.astype(np.float16)
+
+
+def dequant_k(ttype: int, raw: bytes, nel: int) -> np.ndarray:
+    """nel / 256 K-quant super-blocks (12 q4_K, 13 q5_K, 14 q6_K) to float16 [nel] by the loader's rule: d sc and
+    dmin m exact in float32, w = fmaf(q, d sc, -(dmin m)) (q6_K: the float32 product (d S)(q - 32)), then float16."""
+    blk = np.frombuffer(raw, np.uint8, nel // QK_K * K_BLOCK_BYTES[ttype]).reshape(-1, K_BLOCK_BYTES[ttype])
+    nb = blk.shape[0]
+    f16 = lambda o: blk[:, o:o + 2].copy().view("<f2")[:, 0].astype(np.float32)
+    if ttype == 14:
+        ql, H = blk[:, :128].reshape(nb, 2, 2, 32).astype(np.int64), blk[:, 128:192].reshape(nb, 2, 32).astype(np.int64)
+        S = blk[:, 192:208].copy().view(np.int8).reshape(nb, 2, 8).astype(np.float32)
+        q = np.stack([(ql[:, :, 0] & 15) | (H & 3) << 4, (ql[:, :, 1] & 15) | (H >> 2 & 3) << 4,
+                      (ql[:, :, 0] >> 4) | (H >> 4 & 3) << 4, (ql[:, :, 1] >> 4) | (H >> 6) << 4], axis=2)
+        a = f16(208)[:, None, None, None] * S[:, :, np.arange(32) // 16 + 2 * np.arange(4)[:, None]]
+        return _to_f16(_fma_f32(q, a, np.float32(-32) * a)).reshape(-1)
+    s = blk[:, 4:16].astype(np.int64)
+    sc = np.concatenate([s[:, :4] & 63, (s[:, 8:] & 15) | (s[:, :4] >> 6) << 4], axis=1).astype(np.float32)
+    m = np.concatenate([s[:, 4:8] & 63, (s[:, 8:] >> 4) | (s[:, 4:8] >> 6) << 4], axis=1).astype(np.float32)
+    qs = blk[:, -128:].reshape(nb, 4, 32).astype(np.int64)
+    q = np.stack([qs & 15, qs >> 4], axis=2)  # [pair p][nibble][l]: weight 64 p + 32 nibble + l
+    if ttype == 13:
+        qh = blk[:, 16:48].astype(np.int64)[:, None, None, :]
+        q = q + ((qh >> (2 * np.arange(4)[:, None, None] + np.arange(2)[:, None]) & 1) << 4)
+    a, b = f16(0)[:, None] * sc, -(f16(2)[:, None] * m)
+    return _to_f16(_fma_f32(q.reshape(nb, 8, 32), a[:, :, None], b[:, :, None])).reshape(-1)
+
+
 def quantize(w: np.ndarray, qtype: str) -> bytes:
-    """ggml quantize_row_<type>_ref (QNT v2 layouts) over rows of 32 weights."""
+    """ggml quantize_row_<type>_ref (QNT v2 layouts) over rows of 32 weights; the K-quants: quantize_k."""
     if qtype == "q5_1":
         return quantize_q5_1(w)
+    if qtype in ("q4_K", "q5_K", "q6_K"):
+        return quantize_k(w, qtype)
     x = np.ascontiguousarray(w, dtype=np.float32).reshape(-1, 32)
     nb = x.shape[0]
     if qtype == "q8_0":
@@ -272,7 +363,7 @@ def quantize_q5_1(w: np.ndarray) -> bytes:
 
 def write_ggml(path: str, model: str = "base", hp_override: dict | None = None,
                wscale: float = 0.02, n_vocab_file: int | None = None, tensor_hook=None,
-               quant: str | None = None, vocab_replace: dict | None = None, filters=None) -> dict:
+               quant: str | None = None, vocab_replace: dict | None = None, filters=None, twin: bool = False) -> dict:
     """Write a synthetic ggml-v1 Whisper file; returns the hparams used.
     tensor_hook(name, array) -> array may edit tensors before they are written.
     vocab_replace {id: bytes} replaces those entries of the file's vocabulary.
@@ -281,12 +372,17 @@ def write_ggml(path: str, model: str = "base", hp_override: dict | None = None,
     kernel f32, main.rs:817-821); "q5_1", "q8_0", ... store every 2-D weight matrix in that ggml block format,
     as whisper.cpp's quantize tool does (conv kernels, biases, LN parameters
     and positional embeddings keep their type); hparams.f16 then carries the
-    file ftype + 1000 * GGML_QNT_VERSION."""
+    file ftype + 1000 * GGML_QNT_VERSION.  A K-quant ("q4_K", "q5_K", "q6_K") takes the matrices whose rows are
+    a multiple of 256 long; the others stay f16, as ggml leaves them.  twin (K-quants): the f16 file of the same
+    model, every K-type matrix stored as the f16 values its blocks decode to (dequant_k), for readers without
+    K-quants."""
     hp = dict(MODEL_DIMS[model])
     wf32 = quant == "f32"
     if wf32:
         quant = None
-    hp["f16"] = (0 if wf32 else 1) if quant is None else QUANT_TYPES[quant][1] + 1000 * GGML_QNT_VERSION
+    kq = quant in ("q4_K", "q5_K", "q6_K")
+    assert kq or not twin
+    hp["f16"] = (0 if wf32 else 1) if quant is None or twin else QUANT_TYPES[quant][1] + 1000 * GGML_QNT_VERSION
     if hp_override:
         hp.update(hp_override)
     n_vocab_file = 50257 if n_vocab_file is None else n_vocab_file
@@ -311,9 +407,11 @@ def write_ggml(path: str, model: str = "base", hp_override: dict | None = None,
             ftype = 1 if arr.dtype == np.float16 else 0
             ne = tuple(reversed(shape))
             nb = name.encode()
-            if quant is not None and kind == "w" and len(shape) == 2:
+            if quant is not None and kind == "w" and len(shape) == 2 and not (kq and shape[1] % QK_K):
                 ftype = QUANT_TYPES[quant][0]
                 payload = quantize(arr.astype(np.float32), quant)
+                if twin:
+                    ftype, payload = 1, dequant_k(QUANT_TYPES[quant][0], payload, arr.size).astype("<f2").tobytes()
             else:
                 payload = arr.astype("<f2" if ftype else "<f4").tobytes()
             f.write(struct.pack("<iii", len(ne), len(nb), ftype))

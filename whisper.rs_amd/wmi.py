@@ -1393,10 +1393,19 @@ def best_of_key(seed: int, n: int, c: int) -> int:
     return k.value
 
 
+# ggml type -> (weights, bytes) of a block
+QBLOCK = {2: (32, 18), 3: (32, 20), 6: (32, 22), 7: (32, 24), 8: (32, 34), 12: (256, 144), 13: (256, 176), 14: (256, 210)}
+
+
 def dequant_blocks(qtype: int, raw: bytes, nel: int) -> np.ndarray:
-    """nel / 32 raw ggml blocks of type qtype expanded on the device by the quantised-weight GEMM's own
-    dequantisation (wmi_dequant_blocks): the f16 bits as uint16 [nel]."""
+    """nel / 32 raw ggml blocks of type qtype (nel / 256 super-blocks of the K-quants 12 q4_K, 13 q5_K, 14 q6_K)
+    expanded on the device by their quantised-weight GEMM's own dequantisation (wmi_dequant_blocks): the f16 bits
+    as uint16 [nel]."""
     buf = np.frombuffer(raw, np.uint8).copy()
+    if qtype in QBLOCK:  # (any other type is the library's to refuse)
+        weights, size = QBLOCK[qtype]
+        if nel % weights or buf.size != nel // weights * size:
+            raise ValueError(f"dequant_blocks: {buf.size} bytes are not {nel} weights of ggml type {qtype}")
     out = np.zeros(nel, np.uint16)
     _raise(lib().wmi_dequant_blocks(int(qtype), _ptr(buf), nel, _ptr(out)), None)
     return out
